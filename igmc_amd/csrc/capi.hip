@@ -910,6 +910,29 @@ extern "C" int igmc_model_step_form(const igmc_model* m, const igmc_batch* b, in
   return 0;
 }
 
+extern "C" int igmc_model_step_geometry(const igmc_model* m, const igmc_batch* b, int B, int32_t* out, int n) {
+  if (!m || !b || !out || n < 0) IGMC_FAIL("bad arguments");
+  if (B < 1 || B > b->d.graph_cap) IGMC_FAIL("batch size outside the arena's capacity");
+  StepPlan sp;
+  igmc_step_plan(m->d, b->d, B, &sp);
+  const int g2 = sp.family == IGMC_FAM_G2, dense = sp.family == IGMC_FAM_DLF || sp.family == IGMC_FAM_DL;
+  int nqu = 0, nqv = 0;
+  if (dense) igmc_dl_split(b->d.cap_u, b->d.cap_v, B, &nqu, &nqv);
+  const int32_t v[IGMC_GEOM_N] = {igmc_model_step_form(m, b, B),
+                                  sp.family,
+                                  g2 ? sp.cs : 0,
+                                  g2 ? sp.grid : 0,
+                                  nqu,
+                                  nqv,
+                                  sp.family == IGMC_FAM_ROWS ? 0 : sp.wide ? g2_groups(m->d.R, m->d.L) : 1,
+                                  sp.wide && igmc_dl_wide_gsplit(m->d, b->d, B),
+                                  g2 || sp.dlts,
+                                  g2 ? sp.lay.kp : 0,
+                                  dense && sp.dlb};
+  for (int i = 0; i < n && i < IGMC_GEOM_N; ++i) out[i] = v[i];
+  return 0;
+}
+
 static int check_fit(igmc_model* m, const igmc_batch* b, std::string* why) {
   if (!m || !b) { *why = "null model or batch"; return 1; }
   if (b->last_B <= 0) { *why = "batch is empty (run igmc_extract_batch first)"; return 1; }

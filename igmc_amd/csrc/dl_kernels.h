@@ -2024,6 +2024,11 @@ void igmc_launch_dl_fwd(const ModelDev& m, const BatchDev& b, const float* P, in
 // nothing (the per-layer kernels k_dl_layer0 / k_dl_layer stop at G2_NR relations)
 // 1 = ... and in the group-split form (dl_gsplit): both relation groups at once on the halves of a workgroup
 int igmc_dl_wide_gsplit(const ModelDev& m, const BatchDev& b, int B) { return igmc_dl_wide(m, b, B) && dl_gsplit(m, b, B); }
+void igmc_dl_split(int cap_u, int cap_v, int B, int* nqu, int* nqv) {
+  const DlSplit sq = dl_split(cap_u, cap_v, B);
+  *nqu = sq.nqu;
+  *nqv = sq.nqv;
+}
 
 int igmc_dl_wide(const ModelDev& m, const BatchDev& b, int B) {
   if (!igmc_g2_xcd_ok()) return 0;      // (the members' exchange goes through the L2 of one XCD)

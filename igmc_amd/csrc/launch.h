@@ -104,6 +104,23 @@ int igmc_dl_fwd_eligible(const ModelDev& m, const BatchDev& b, int B);
 int igmc_dl_bwd_eligible(const ModelDev& m, const BatchDev& b, int B);
 int igmc_dl_wide(const ModelDev& m, const BatchDev& b, int B);
 int igmc_dl_wide_gsplit(const ModelDev& m, const BatchDev& b, int B);
+void igmc_dl_split(int cap_u, int cap_v, int B, int* nqu, int* nqv);      // workgroups of a subgraph's two sides (dl_split)
+
+// What a training step on (arena, B) launches: the one decision igmc_launch_loss_grad takes its branches from, and what
+// igmc_model_step_geometry reports (model.hip)
+#define IGMC_FAM_ROWS 0      // the CSR row walkers (k_l0_fwd / k_rgcn_layer4)
+#define IGMC_FAM_G2 1        // the subgraph kernel (k_graph_step)
+#define IGMC_FAM_DLF 2       // the one-launch dense layers (k_dl_fwd)
+#define IGMC_FAM_DL 3        // the per-layer dense layers (k_dl_layer0 / k_dl_layer)
+struct StepPlan {
+  int fast_head;             // 0: the generic sequence (igmc_launch_forward + igmc_launch_backward)
+  int family;                // IGMC_FAM_*
+  int cs, grid;              // subgraph kernel: workgroups per subgraph, grid
+  G2Layout lay;              // ... its LDS plan
+  int wide, dl, dlts, dlf, dlb;      // dense layers: relation groups, per-layer / one-launch eligible, relation-space tables,
+                                     // one-launch forward, one-launch backward
+};
+void igmc_step_plan(const ModelDev& m, const BatchDev& b, int B, StepPlan* p);
 // (head != NULL: the launch runs the subgraphs' loss head itself -- no k_head_sub launch in front of it)
 struct DlHead {
   const float* P;

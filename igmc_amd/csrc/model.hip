@@ -2369,6 +2369,31 @@ static int igmc_conv_bwd_tables(const ModelDev& m, const BatchDev& b, int B) {
          igmc_dl_bwd_eligible(m, b, B);
 }
 
+void igmc_step_plan(const ModelDev& m, const BatchDev& b, int B, StepPlan* p) {
+  memset(p, 0, sizeof(*p));
+  const int ny = (m.D / 16 + 3) / 4;
+  const int l0_mfma = m.R * m.L + m.L + 1 <= 32;
+  p->fast_head = (m.D % 16 == 0) && 8 * ny <= IGMC_WG_BLOCKS;
+  if (!p->fast_head) {      // generic sequence: igmc_launch_conv_forward / igmc_launch_conv_backward
+    p->wide = igmc_dl_wide(m, b, B);
+    p->dl = p->wide || igmc_dl_eligible(m, b, B);
+    p->dlf = p->wide || (p->dl && igmc_dl_fwd_eligible(m, b, B));
+    p->dlts = p->dlb = igmc_conv_bwd_tables(m, b, B);
+  } else if (l0_mfma && igmc_g2_eligible(m, b, B, &p->lay, &p->cs)) {
+    p->family = IGMC_FAM_G2;      // (p->cs: igmc_gs_cluster)
+    p->grid = (p->cs > 1) ? p->cs * ((B + 7) & ~7) : igmc_gs_grid(B);
+    return;
+  } else {
+    const int fts_pre = igmc_fin_mode() && m.fin_stash && m.datt_part && m.R <= G2_NR * G2_NG_MAX;
+    p->wide = fts_pre && igmc_dl_wide(m, b, B);
+    p->dl = p->wide || igmc_dl_eligible(m, b, B);
+    p->dlts = p->wide || (p->dl && l0_mfma && fts_pre && m.R <= 8 && igmc_dl_ts_eligible(m, b, B));
+    p->dlf = p->wide || (p->dl && igmc_dl_fwd_eligible(m, b, B));
+    p->dlb = p->dlts && (p->wide || (p->dlf && igmc_dl_bwd_eligible(m, b, B)));
+  }
+  p->family = p->dlf ? IGMC_FAM_DLF : p->dl ? IGMC_FAM_DL : IGMC_FAM_ROWS;
+}
+
 // The four conv layers alone (h_0..h_3 left in HBM): the per-layer kernels, whatever the readout that follows
 // (centre-node readout of IGMC: igmc_launch_forward; sort-pool readout of DGCNN_RS: sortpool.hip)
 void igmc_launch_conv_forward(const ModelDev& m, const BatchDev& b, const float* P, int B, int training, int use_flags,
@@ -2524,14 +2549,15 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const ModelAux& ax, const BatchD
   const int gy = igmc_rows_grid(m.node_cap, 128, 512);
   const int hb = (B + 15) / 16;
   const int ny = (m.D / 16 + 3) / 4;
-  const bool fast_head = (m.D % 16 == 0) && 8 * ny <= IGMC_WG_BLOCKS;
+  StepPlan sp;      // (the branches below: igmc_step_plan)
+  igmc_step_plan(m, b, B, &sp);
   const int64_t n_lin = m.n_params - m.off_l1w;      // lin1 / lin2 are the tail of the flat parameter vector
   AdamTail at;
   memset(&at, 0, sizeof(at));
   if (adam) at = *adam;
   at.use_flags = use_flags;
   at.skip = xch ? xch->failed : nullptr;
-  if (!fast_head) {      // generic sequence
+  if (!sp.fast_head) {      // generic sequence
     igmc_launch_forward(m, ax, b, P, B, 1, use_flags, inj_mask, seed, step, mult, out, stream);
     igmc_launch_backward(m, ax, b, P, B, use_flags, nullptr, 1, grad_scale, mult, 2.f, ARR * arr_scale, grad, stream);
     if (adam) {
@@ -2542,15 +2568,13 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const ModelAux& ax, const BatchD
     }
     return 0;
   }
-  G2Layout lay2;
-  int cs2 = 1;
-  if (l0_mfma && igmc_g2_eligible(m, b, B, &lay2, &cs2)) {
+  if (sp.family == IGMC_FAM_G2) {
     // one workgroup (cluster) per subgraph: forward, residual and backward down to the per-workgroup gradient partials
-    const int cs = igmc_gs_cluster(B);
+    const int cs = sp.cs;
     const int gstride = (cs > 1) ? ((B + 7) & ~7) : IGMC_TS_BLOCKS;
-    const int gg = (cs > 1) ? cs * gstride : igmc_gs_grid(B);
+    const int gg = sp.grid;
     int bump_seq = 0;       // 1: k_tail_ts advances the launch sequence number of the subgraph kernel's exchange tags
-    bump_seq = igmc_launch_graph_step2(m, b, P, B, 1, use_flags, lay2, cs2, inj_mask, seed, step, mult, grad_scale, out, stream);
+    bump_seq = igmc_launch_graph_step2(m, b, P, B, 1, use_flags, sp.lay, cs, inj_mask, seed, step, mult, grad_scale, out, stream);
     // IGMC_FIN_MODE=0: the hand-off version of the gradient / Adam tail (k_finalize) instead of k_finalize_ts
     const int fts = igmc_fin_mode() && m.fin_stash && m.datt_part && m.R <= 8;
     IGMC_PLAUNCH("k_tail_ts", k_tail_ts, 8 * ny + (4 * m.ts_stride + 63) / 64 + (fts ? 4 : 0), IGMC_BLOCK, 0, stream, b, m,
@@ -2583,12 +2607,8 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const ModelAux& ax, const BatchD
   // k_dl_layer) from the blocks alone -- no edge list is read
   // ... and all four of them as ONE launch where the members of a subgraph can hand h_l to each other (k_dl_fwd); the launch
   // sequence number of its exchange tags is advanced by k_tail_ts (tables path) -- else by the launch's last workgroup
-  const int fts_pre = igmc_fin_mode() && m.fin_stash && m.datt_part && m.R <= G2_NR * G2_NG_MAX;
   // more than five relations (igmc_dl_wide): the one-launch forward / backward in relation groups + the tables' tail, or nothing
-  const int wide = fts_pre && igmc_dl_wide(m, b, B);
-  const int dl = wide || igmc_dl_eligible(m, b, B);
-  const int dlts = wide || (dl && l0_mfma && fts_pre && m.R <= 8 && igmc_dl_ts_eligible(m, b, B));
-  const int dlf = wide || (dl && igmc_dl_fwd_eligible(m, b, B));
+  const int dl = sp.dl, dlts = sp.dlts, dlf = sp.dlf;
   if (dlf) {
     igmc_launch_g2_compose(m, (const float*)P, stream);
     igmc_launch_dl_fwd(m, b, (const float*)P, B, 1, use_flags, m.dpre[3], dlts ? 0 : 1, stream);
@@ -2614,7 +2634,7 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const ModelAux& ax, const BatchD
   // -- k_tail_ts sums the workgroups' tables and forms d lin1 / d lin2, k_finalize_ts turns them into gradients (+ Adam) --
   // replaces the Y products, G, the weight-gradient products and their reduction
   if (dlts) {
-    if (wide || (dlf && igmc_dl_bwd_eligible(m, b, B))) {
+    if (sp.dlb) {
       // the three backward layers as ONE launch, the loss head of each subgraph (side features included) in its set-up
       // (IGMC_DL_HEAD=0: the head as a launch of its own in front of it)
       const char* eh = getenv("IGMC_DL_HEAD");

@@ -277,6 +277,21 @@ class ModelWorkspace(object):
         group-split form, 0 per-layer kernels (igmc_model_step_form)."""
         return int(self.lib.igmc_model_step_form(self.handle, batch.handle, int(B)))
 
+    GEOMETRY_KEYS = ('form', 'family', 'wg_per_graph', 'grid', 'nqu', 'nqv', 'groups', 'gsplit', 'tables', 'kp', 'dl_bwd')
+    FAMILIES = ('rows', 'subgraph', 'dense_fused', 'dense_layer')
+
+    def step_geometry(self, batch, B):
+        """Launch geometry of a training step on (batch arena, B) (igmc_model_step_geometry): ``family`` is one of
+        FAMILIES; ``wg_per_graph`` / ``grid`` of the subgraph kernel, ``nqu`` / ``nqv`` workgroups of a subgraph's sides
+        in the dense layers, ``groups`` relation groups and ``gsplit`` both at once, ``tables`` a backward that leaves
+        relation-space tables, ``kp`` the subgraph kernel's padded plane extent, ``dl_bwd`` the one-launch dense backward."""
+        n = len(self.GEOMETRY_KEYS)
+        out = (C.c_int32 * n)()
+        self.lib.call('igmc_model_step_geometry', self.handle, batch.handle, int(B), C.cast(out, C.c_void_p), n)
+        g = dict(zip(self.GEOMETRY_KEYS, [int(x) for x in out]))
+        g['family'] = self.FAMILIES[g['family']]
+        return g
+
     def adam_step(self, params, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999, eps=1e-8,
                   weight_decay=0.0, stream=None):
         self.lib.call('igmc_adam_step', _p(params), _p(grad), _p(exp_avg), _p(exp_avg_sq), self.n_params, int(step),

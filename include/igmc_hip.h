@@ -366,6 +366,21 @@ int igmc_model_dense_path(const igmc_model* m, const igmc_batch* b, int B);
  * 2 = the one-launch dense-layer kernels, 3 = those in their group-split form (two relation groups at once), 0 = the
  * per-layer kernels.  No reference counterpart. */
 int igmc_model_step_form(const igmc_model* m, const igmc_batch* b, int B);
+/* The launch geometry of a training step on (this arena, batch size B), from the same decision the launch sequence takes its
+ * branches from.  Writes min(n, IGMC_GEOM_N) values to out[]:
+ *   [0] igmc_model_step_form
+ *   [1] kernel family: 0 = CSR row walkers, 1 = subgraph kernel, 2 = one-launch dense layers, 3 = per-layer dense layers
+ *   [2] subgraph kernel: workgroups per subgraph (4, 2, 1), else 0
+ *   [3] subgraph kernel: grid (fewer workgroups than subgraphs at 1 per subgraph: each loops over several), else 0
+ *   [4] [5] dense layers: workgroups of a subgraph's user side / item side, else 0
+ *   [6] relation groups (0 for the row walkers)
+ *   [7] 1 = the two relation groups at once (group split), 0 = group after group or one group
+ *   [8] 1 = the backward leaves relation-space tables (k_tail_ts -> k_finalize_ts)
+ *   [9] subgraph kernel: padded k extent of its planes (kp), else 0
+ *   [10] dense layers: 1 = the backward as one launch (k_dl_bwd)
+ * Fails when B is outside 1 .. the arena's max_graphs.  No reference counterpart. */
+#define IGMC_GEOM_N 11
+int igmc_model_step_geometry(const igmc_model* m, const igmc_batch* b, int B, int32_t* out, int n);
 /* Clears the row / plane exchange regions of the subgraph and dense-layer kernels (enqueued on `stream`).  They must only ever
  * hold finite values (a consumer copies whole plane images, stale rows of earlier launches included, and multiplies them by
  * zero block entries): call it after steps that ran on non-finite parameters, e.g. when parameters are restored. */

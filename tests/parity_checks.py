@@ -219,13 +219,16 @@ GRAD_TOL = 5e-5                      # every gradient tensor, max error relative
 
 
 def run_model_parity(be, case, R, ARR=0.001, use_dropout=True, multiply_by=1.0, seed=3, check_eval=True,
-                     rtol=None, atol=None, n_side=0, lean=False):
+                     rtol=None, atol=None, n_side=0, lean=False, max_graphs=None, out_pad=0, on_step=None):
     """Engine forward / loss+grad on one extracted batch vs the PyG-1.4.2 restatement (oracle/pyg_ref.py)
-    on IDENTICAL inputs: same subgraphs, same weights, same dropout masks."""
+    on IDENTICAL inputs: same subgraphs, same weights, same dropout masks.
+    ``max_graphs``: arena + workspace capacity (default: the batch); ``out_pad``: NaN sentinels behind the batch's ``B``
+    outputs that no launch may touch; ``on_step(ws, batch, B)``: called before the training step, returns a callable
+    (or None) called right after it."""
     import torch
     from oracle import pyg_ref
     out_tol = OUT_TOL if rtol is None else rtol
-    g, b, d = extract_case(be, case, replay=False, lean=lean)
+    g, b, d = extract_case(be, case, replay=False, lean=lean, max_graphs=max_graphs)
     L = 2 * case['h'] + 2
     ws = engine.ModelWorkspace(be.lib, be.device, R, 4, L, n_side, b.node_capacity, b.edge_capacity, b.max_graphs)
     ref = make_ref_model(L, R, n_side=n_side, seed=seed, adj_dropout=0.2 if use_dropout else 0.0,
@@ -233,7 +236,12 @@ def run_model_parity(be, case, R, ARR=0.001, use_dropout=True, multiply_by=1.0, 
     flat = flatten_params(ws, ref)
     P = be.dev(flat)
     B = d['B']
-    out = be.dev(np.zeros(B, np.float32))
+    out = be.dev(np.concatenate([np.zeros(B, np.float32), np.full(out_pad, np.nan, np.float32)]))
+
+    def untouched_tail(o):
+        assert np.isnan(o[B:]).all(), 'an output beyond the batch was written: %s' % o[B:][~np.isnan(o[B:])][:8]
+        assert np.isfinite(o[:B]).all(), 'non-finite outputs'
+        return o[:B]
     pyg = batch_to_pyg(d, L)
     side_buf = None
     if n_side:        # side features of the two target nodes (reference models.py:208-209)
@@ -246,7 +254,7 @@ def run_model_parity(be, case, R, ARR=0.001, use_dropout=True, multiply_by=1.0, 
     if check_eval:
         ws.forward(be.ptr(P), b, be.ptr(out), training=False, multiply_by=multiply_by)
         sse, ref_out = pyg_ref.eval_sse(ref, pyg)
-        got = be.host(out)
+        got = untouched_tail(be.host(out))
         res['eval_err'] = rel_err(got, ref_out.numpy())
         assert res['eval_err'] < out_tol, 'eval outputs: max error relative to the peak %.3e' % res['eval_err']
         res['eval_out'] = got
@@ -266,12 +274,17 @@ def run_model_parity(be, case, R, ARR=0.001, use_dropout=True, multiply_by=1.0, 
     lm = be.dev(lin_mask.astype(np.uint8).reshape(-1))
     grad = be.dev(np.zeros(ws.n_params, np.float32))
     loss = be.dev(np.zeros(2, np.float32))
+    after = on_step(ws, b, B) if on_step else None
     ws.loss_grad(be.ptr(P), b, be.ptr(out), be.ptr(grad), be.ptr(loss), use_edge_flags=use_dropout,
                  lin_mask=be.ptr(lm), multiply_by=multiply_by, ARR=ARR)
+    if after:
+        after()
     rl, ro, rg = pyg_ref.loss_and_grads(ref, pyg, ARR=ARR, edge_mask=edge_mask,
                                         lin_mask=torch.from_numpy(lin_mask))
-    got_out, got_loss = be.host(out), be.host(loss)
-    gg = unflatten_grads(ws, be.host(grad))
+    got_out, got_loss = untouched_tail(be.host(out)), be.host(loss)
+    flat_grad = be.host(grad)
+    assert np.isfinite(flat_grad).all() and np.isfinite(got_loss).all(), 'non-finite gradient or loss'
+    gg = unflatten_grads(ws, flat_grad)
     worst, worst_key = 0.0, ''
     for key, ref_g in rg.items():
         rgn = ref_g.numpy()
@@ -461,7 +474,7 @@ TRAJ_P_ATOL, TRAJ_P_RTOL, TRAJ_FRAC_OFF = 2e-5, 2e-3, 2e-4
 TRAJ_P_MAX = 3e-4                              # largest parameter difference after the steps
 
 
-def run_fused_train_trajectory(be, case, R, steps=5, batch=None, use_dropout=False, lr=1e-3, ARR=0.001, seed=4):
+def run_fused_train_trajectory(be, case, R, steps=5, batch=None, use_dropout=False, lr=1e-3, ARR=0.001, seed=4, sizes=None):
     """The trajectory check below with the ORACLE on one torch thread: the order of its CPU scatter-adds then does not depend
     on the host (128 / 8 / 1 threads moved flixster's exp_avg deviation between 8e-6 and 1.3e-4 with the engine's bits
     unchanged -- one parameter whose gradient is within float noise of zero takes its Adam step the other way:
@@ -470,23 +483,31 @@ def run_fused_train_trajectory(be, case, R, steps=5, batch=None, use_dropout=Fal
     nt = torch.get_num_threads()
     torch.set_num_threads(1)
     try:
-        return _run_fused_train_trajectory(be, case, R, steps, batch, use_dropout, lr, ARR, seed)
+        return _run_fused_train_trajectory(be, case, R, steps, batch, use_dropout, lr, ARR, seed, sizes)
     finally:
         torch.set_num_threads(nt)
 
 
-def _run_fused_train_trajectory(be, case, R, steps=5, batch=None, use_dropout=False, lr=1e-3, ARR=0.001, seed=4):
+def _run_fused_train_trajectory(be, case, R, steps=5, batch=None, use_dropout=False, lr=1e-3, ARR=0.001, seed=4, sizes=None):
     """``igmc_train_step`` (the fused single-GPU step: k_graph_step -> k_tail_ts -> k_finalize_ts with Adam, or the
     per-layer kernels + k_finalize where the subgraph kernel is not eligible) for ``steps`` consecutive steps on
     DIFFERENT batches with injected masks, against ``pyg_ref.train_step`` + ``torch.optim.Adam`` on the same batches
-    (reference train_eval.py:158-177).  Returns per-step losses and the final parameter / Adam-state comparison."""
+    (reference train_eval.py:158-177).  Returns per-step losses and the final parameter / Adam-state comparison.
+    ``sizes``: the batch size of every step instead (``steps`` x ``batch``), on ONE arena and workspace sized for the
+    largest: full-sized steps through ``igmc_train_step``, smaller ones as ``StepGraph`` runs an epoch's ragged last batch
+    (``igmc_model_loss_grad`` with grad_scale 1 / B, then ``igmc_step_finish``) -- or, given as ``(B, 'train_step')``,
+    through ``igmc_train_step`` at that size.  Outputs beyond each step's batch are NaN sentinels no launch may touch."""
     import torch
     from oracle import pyg_ref
     A = case['A']
     L = 2 * case['h'] + 2
     n = len(case['links'])
-    B = batch or n // steps
-    assert B * steps <= n
+    if sizes is None:
+        sizes = [batch or n // steps] * steps
+    B = max(s if isinstance(s, int) else s[0] for s in sizes)
+    plan = [(s, 'train_step' if s == B else 'finish') if isinstance(s, int) else (int(s[0]), s[1]) for s in sizes]
+    steps = len(plan)
+    assert sum(s for s, _ in plan) <= n
     g = engine.Graph(A, device=be.device, lib=be.lib)
     b = engine.Batch(g, max_graphs=B, hop=case['h'], max_nodes_per_hop=case['mnph'])
     ys = case['class_values'][case['link_labels']].astype(np.float32)
@@ -497,15 +518,20 @@ def _run_fused_train_trajectory(be, case, R, steps=5, batch=None, use_dropout=Fa
     n_p = ws.n_params
     P = be.dev(flatten_params(ws, ref))
     M1, M2, G = be.dev(np.zeros(n_p, np.float32)), be.dev(np.zeros(n_p, np.float32)), be.dev(np.zeros(n_p, np.float32))
-    out, loss, total = be.dev(np.zeros(B, np.float32)), be.dev(np.zeros(2, np.float32)), be.dev(np.zeros(1, np.float64))
+    loss, total = be.dev(np.zeros(2, np.float32)), be.dev(np.zeros(1, np.float64))
     rng = np.random.default_rng(seed)
-    losses = []
-    for s in range(steps):
-        b.extract(be.ptr(lu), be.ptr(lv), be.ptr(ly), None, s * B, B, sample_ratio=case['sample_ratio'], seed=2, epoch=1)
+    losses, geoms = [], []
+    first = 0
+    for s, (Bs, how) in enumerate(plan):
+        out = be.dev(np.concatenate([np.zeros(Bs, np.float32), np.full(B - Bs + 8, np.nan, np.float32)]))
+        b.extract(be.ptr(lu), be.ptr(lv), be.ptr(ly), None, first, Bs, sample_ratio=case['sample_ratio'], seed=2, epoch=1)
+        first += Bs
         be.sync()
         d = b.download()
+        assert d['B'] == Bs
         pyg = batch_to_pyg(d, L)
-        lm = rng.random((B, 128)) < 0.5
+        geoms.append(ws.step_geometry(b, Bs))
+        lm = rng.random((Bs, 128)) < 0.5
         LM = be.dev(lm.astype(np.uint8).reshape(-1))
         edge_mask = None
         if use_dropout:
@@ -513,13 +539,24 @@ def _run_fused_train_trajectory(be, case, R, steps=5, batch=None, use_dropout=Fa
             rev = reverse_positions(d)
             b.set_edge_flags(keep.astype(np.uint8) | (keep[rev].astype(np.uint8) << 1))
             edge_mask = torch.from_numpy(keep)
-        be.lib.call('igmc_train_step', ws.handle, engine._p(be.ptr(P)), b.handle, int(use_dropout), engine._p(be.ptr(LM)),
-                    0, 0, 1.0, ARR, engine._p(be.ptr(out)), engine._p(be.ptr(G)), engine._p(be.ptr(M1)),
-                    engine._p(be.ptr(M2)), engine._p(be.ptr(loss)), engine._p(be.ptr(total)), None, s + 1, lr, 0.9, 0.999,
-                    1e-8, 0.0, None)
+        if how == 'train_step':
+            be.lib.call('igmc_train_step', ws.handle, engine._p(be.ptr(P)), b.handle, int(use_dropout), engine._p(be.ptr(LM)),
+                        0, 0, 1.0, ARR, engine._p(be.ptr(out)), engine._p(be.ptr(G)), engine._p(be.ptr(M1)),
+                        engine._p(be.ptr(M2)), engine._p(be.ptr(loss)), engine._p(be.ptr(total)), None, s + 1, lr, 0.9,
+                        0.999, 1e-8, 0.0, None)
+        else:
+            assert how == 'finish', how
+            ws.loss_grad(be.ptr(P), b, be.ptr(out), be.ptr(G), None, use_edge_flags=use_dropout, lin_mask=be.ptr(LM),
+                         ARR=ARR, grad_scale=1.0 / Bs)
+            be.lib.call('igmc_step_finish', ws.handle, b.handle, engine._p(be.ptr(P)), engine._p(be.ptr(G)),
+                        engine._p(be.ptr(M1)), engine._p(be.ptr(M2)), ARR, engine._p(be.ptr(loss)),
+                        engine._p(be.ptr(total)), None, s + 1, lr, 0.9, 0.999, 1e-8, 0.0, None)
         be.sync()
         ref_loss = pyg_ref.train_step(ref, opt, pyg, ARR=ARR, edge_mask=edge_mask, lin_mask=torch.from_numpy(lm))
         got = float(be.host(loss)[0])
+        o = be.host(out)
+        assert np.isnan(o[Bs:]).all(), 'step %d (B = %d): an output beyond the batch was written' % (s, Bs)
+        assert np.isfinite(o[:Bs]).all() and np.isfinite(got), 'step %d (B = %d): non-finite outputs or loss' % (s, Bs)
         losses.append((got, ref_loss))
     be.lib.call('igmc_model_check', ws.handle, None)
     # Adam state: exp_avg is LINEAR in the gradients -> tight, per tensor relative to its peak
@@ -538,7 +575,9 @@ def _run_fused_train_trajectory(be, case, R, steps=5, batch=None, use_dropout=Fa
     # the other direction, so a handful of elements can be off by up to 2 * lr * steps; everything else must track
     bad = diff > tol
     loss_rel = max(abs(a - b) / max(abs(b), 1e-12) for a, b in losses)
-    record_observed('fused_trajectory', R=R, steps=steps, batch=int(B), dropout=bool(use_dropout), loss_rel=loss_rel,
+    assert np.isfinite(got_p).all(), 'non-finite parameters after the steps'
+    record_observed('fused_trajectory', R=R, steps=steps, batch=int(B), sizes=[int(s) for s, _ in plan],
+                    forms=[how for _, how in plan], dropout=bool(use_dropout), loss_rel=loss_rel,
                     exp_avg_rel=worst_m1, exp_avg_sq_rel=worst_m2, params_frac_off=float(bad.mean()),
                     params_max_diff=float(diff.max()), lr_steps=lr * steps)
     assert loss_rel < TRAJ_LOSS_RTOL, losses
@@ -546,7 +585,7 @@ def _run_fused_train_trajectory(be, case, R, steps=5, batch=None, use_dropout=Fa
     assert bad.mean() < TRAJ_FRAC_OFF, 'too many parameters off the oracle trajectory: %g' % bad.mean()
     assert diff.max() <= TRAJ_P_MAX, diff.max()
     return dict(losses=losses, frac_off=float(bad.mean()), max_diff=float(diff.max()), total=float(be.host(total)[0]),
-                params=got_p, m1=be.host(M1), m2=be.host(M2), ws=ws)
+                params=got_p, m1=be.host(M1), m2=be.host(M2), ws=ws, geometries=geoms)
 
 
 # ====================================================================== DGCNN_RS (sort-pool readout family)

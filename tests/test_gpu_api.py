@@ -405,10 +405,11 @@ def test_full_size_headline_config_properties(monkeypatch):
     assert float(diff.max()) < 2e-3 and float(diff.mean()) < 2e-5, (float(diff.max()), float(diff.mean()))
 
 
-@pytest.mark.parametrize('batch', [100, 130])
-def test_graph_step_other_cluster_sizes(monkeypatch, batch):
-    """Batch 100 -> 2 workgroups per subgraph, batch 130 -> one workgroup per subgraph with workgroups looping over
-    subgraphs (accumulating partial tables): both must walk the per-layer kernels' trajectory."""
+@pytest.mark.parametrize('batch,mnph', [(100, 63), (130, 31)], ids=['100', '130'])
+def test_graph_step_other_cluster_sizes(monkeypatch, batch, mnph):
+    """Batch 100 -> 2 workgroups per subgraph (slots of <= 64 nodes a side), batch 130 -> one workgroup per subgraph
+    (<= 32 a side) with workgroups looping over subgraphs (accumulating partial tables): both must walk the trajectory of
+    the kernels IGMC_GRAPH_STEP=0 takes instead."""
     import torch
     from igmc_amd import preprocessing
     from igmc_amd.models import IGMC
@@ -417,7 +418,7 @@ def test_graph_step_other_cluster_sizes(monkeypatch, batch):
     from igmc_amd.util_functions import MyDynamicDataset
     split = preprocessing.create_trainvaltest_split('ml_1m', 1234, True, verbose=False)
     (_, _, A, tr_l, tr_u, tr_v, _, _, _, _, _, _, cv) = split
-    ds = MyDynamicDataset('data/t/full2', A, (tr_u, tr_v), tr_l, 1, 1.0, 100, None, None, cv, device=0, seed=1)
+    ds = MyDynamicDataset('data/t/full2', A, (tr_u, tr_v), tr_l, 1, 1.0, mnph, None, None, cv, device=0, seed=1)
     perm = torch.randperm(len(ds), generator=torch.Generator().manual_seed(4))[:batch * 4]
     losses = {}
     for name, env in (('per_layer', '0'), ('per_graph', '1')):
@@ -435,6 +436,14 @@ def test_graph_step_other_cluster_sizes(monkeypatch, batch):
             out.append(float(sg.loss[0].item()))
         sg.check()
         losses[name] = out
+        geo = sg.ws.step_geometry(sg._arena(0, 0), batch)
+        if name == 'per_graph':
+            assert geo['family'] == 'subgraph', geo
+            assert geo['wg_per_graph'] == (2 if batch <= 112 else 1), geo
+            if batch > 112:
+                assert geo['grid'] < batch, geo          # workgroups loop over subgraphs
+        else:
+            assert geo['family'] != 'subgraph', geo
     np.testing.assert_allclose(losses['per_layer'], losses['per_graph'], rtol=5e-5)
 
 
