@@ -10,7 +10,8 @@ Multi-GPU (one process per GPU, RCCL gradient all-reduce):
 
 Differences from the reference script, on purpose: the crash paths it has as shipped (``rmse`` undefined
 without ``--ensemble``, ``args.epoch``: ``Main.py:471-472``) are fixed -- the value returned by
-``train_multiple_epochs`` is used; ``--visualize`` is out of scope; MovieLens is read from ``raw_data/`` when an
+``train_multiple_epochs`` is used; ``--visualize`` (reference ``Main.py:423-435``) scores the test links on the GPU and
+keeps the scores there, selects the extremes on the device and draws the subgraphs it scored; MovieLens is read from ``raw_data/`` when an
 operator provides it and otherwise replaced by the MovieLens-shaped synthetic generator (no network here).
 """
 from __future__ import print_function
@@ -35,7 +36,7 @@ torch.set_num_threads(int(os.environ['OMP_NUM_THREADS']))
 from igmc_amd import parallel  # noqa: E402
 from igmc_amd.models import IGMC
 from igmc_amd.preprocessing import create_trainvaltest_split, load_data_monti, load_official_trainvaltest_split
-from igmc_amd.train_eval import test_once, train_multiple_epochs
+from igmc_amd.train_eval import test_once, train_multiple_epochs, visualize
 from igmc_amd.util_functions import MyDataset, MyDynamicDataset
 
 
@@ -243,10 +244,21 @@ def main(argv=None):
                                      lr_decay_step_size=args.lr_decay_step_size, weight_decay=0, ARR=args.ARR,
                                      test_freq=args.test_freq, logger=logger, continue_from=args.continue_from,
                                      res_dir=args.res_dir)
-    if args.visualize:
-        raise NotImplementedError('--visualize (networkx/matplotlib plots) is outside the accelerated path')
     # only rank 0 writes checkpoints (inside `logger`): nobody may look for them before it is done
     parallel.barrier()
+
+    if args.visualize:
+        # reference Main.py:423-435: the checkpoint's highest / lowest scored test subgraphs as a PDF (and nothing else of
+        # what follows).  Rank 0 scores the whole test set and draws; the other ranks wait at the barrier.
+        model.load_state_dict(torch.load(args.model_pos, map_location='cpu'))
+        if rank == 0:
+            visualize(model, test_graphs, args.res_dir, args.data_name, class_values, sort_by='prediction')
+        parallel.barrier()
+        if args.transfer:
+            rmse = test_once(test_graphs, model, args.batch_size, logger)
+            if rank == 0:
+                print('Transfer learning rmse is: {:.6f}'.format(rmse))
+        return rmse
 
     epoch_info = 'epoch {}'.format(args.epochs)
     if args.ensemble:

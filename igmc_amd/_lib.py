@@ -68,6 +68,9 @@ SIGNATURES = {
     'igmc_sortpool_step_finish': (i32, [vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp]),
     'igmc_sse_accumulate': (i32, [vp, vp, vp, vp]),
     'igmc_sse_accumulate_tick': (i32, [vp, vp, vp, vp, vp]),
+    'igmc_scores_store': (i32, [vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]),
+    'igmc_select_scratch_bytes': (i64, [i64, i32, i32]),
+    'igmc_select_extremes': (i32, [vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, i32, vp]),
     'igmc_comm_unique_id': (i32, [vp]),
     'igmc_comm_create': (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
     'igmc_comm_destroy': (None, [vp]),

@@ -1019,6 +1019,41 @@ extern "C" int igmc_sse_accumulate_tick(const float* d_out, const igmc_batch* b,
   return 0;
 }
 
+// ------------------------------------------------------------------ scores kept on the device + their extremes (scores.hip)
+extern "C" int igmc_scores_store(const float* d_out, const igmc_batch* b, double* d_acc, float* d_scores, float* d_labels,
+                                 int64_t n, int64_t first_or_minus1, int64_t* d_ctrl, int32_t* d_err, void* stream) {
+  if (!d_out || !b || !d_acc || !d_scores || !d_labels || !d_err) IGMC_FAIL("null argument");
+  if (n < 1 || n > (int64_t)INT32_MAX) IGMC_FAIL("n must be in [1, 2^31)");
+  if (first_or_minus1 < -1 || first_or_minus1 >= n) IGMC_FAIL("first must be -1 (the arena's stamp) or a position below n");
+  igmc_launch_scores_store(b->d, d_out, d_acc, d_ctrl, d_scores, d_labels, n, first_or_minus1, d_err, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+static int select_grid(int64_t n, int num, int grid) {
+  if (n < 1 || n > (int64_t)INT32_MAX || num < 1 || num > IGMC_SELECT_MAX_NUM || grid < 0 || grid > IGMC_SELECT_MAX_GRID) return -1;
+  return grid > 0 ? grid : igmc_select_default_grid(n);
+}
+extern "C" int64_t igmc_select_scratch_bytes(int64_t n, int num, int grid) {
+  const int g = select_grid(n, num, grid);
+  if (g < 0) {
+    g_err = std::string(__func__) + ": n must be in [1, 2^31), num in [1, 64], grid in [0, 1024]";
+    return -1;
+  }
+  return (int64_t)2 * g * num * (int64_t)sizeof(uint64_t);
+}
+extern "C" int igmc_select_extremes(const float* d_keys, int64_t n, int num, int32_t* d_idx_low, int32_t* d_idx_high,
+                                    float* d_key_low, float* d_key_high, int32_t* d_count, void* d_scratch,
+                                    int64_t scratch_bytes, int grid, void* stream) {
+  if (!d_keys || !d_idx_low || !d_idx_high || !d_scratch) IGMC_FAIL("null argument");
+  const int g = select_grid(n, num, grid);
+  if (g < 0) IGMC_FAIL("n must be in [1, 2^31), num in [1, 64], grid in [0, 1024]");
+  if (scratch_bytes < (int64_t)2 * g * num * (int64_t)sizeof(uint64_t)) IGMC_FAIL("scratch too small (igmc_select_scratch_bytes)");
+  if (((uintptr_t)d_scratch & 7) != 0) IGMC_FAIL("scratch must be 8-byte aligned");
+  igmc_launch_select(d_keys, n, num, g, d_scratch, d_idx_low, d_idx_high, d_key_low, d_key_high, d_count, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
 // ------------------------------------------------------------------ device-side step control
 extern "C" int igmc_ctrl_tick(int64_t* d_ctrl, void* stream) {
   if (!d_ctrl) IGMC_FAIL("null ctrl");

@@ -74,6 +74,14 @@ int igmc_launch_train_step(const ModelDev& m, const ModelAux& ax, const BatchDev
                            void* stream, float grad_scale = 0.f, const StepExchange* xch = nullptr, int* img_emitted = nullptr);
 void igmc_launch_loss(const ModelDev& m, const BatchDev& b, float ARR, float* loss, void* stream);
 void igmc_launch_sse(const BatchDev& b, const float* out, double* acc, int64_t* ctrl, void* stream);
+// scores.hip: the scoring step's tail (k_sse_acc + the outputs / labels filed at their positions) and the extremes of a key array
+#define IGMC_SELECT_MAX_GRID 1024
+#define IGMC_SELECT_MAX_NUM 64
+void igmc_launch_scores_store(const BatchDev& b, const float* out, double* acc, int64_t* ctrl, float* scores, float* labels,
+                              int64_t n, int64_t first, int32_t* err, void* stream);
+int igmc_select_default_grid(int64_t n);
+void igmc_launch_select(const float* keys, int64_t n, int num, int grid, void* scratch, int32_t* idx_low, int32_t* idx_high,
+                        float* key_low, float* key_high, int32_t* count, void* stream);
 int igmc_model_prepare(const ModelDev& m);
 void igmc_launch_adam(float* p, const float* g, float* m1, float* m2, int64_t n, float step_size,
                       float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd, int64_t* ctrl, int tick,

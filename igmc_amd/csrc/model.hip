@@ -1577,27 +1577,7 @@ struct FinishArgs {
   double* total;
 };
 
-// End of a step (igmc_hip.h, device-side step control): counters, Adam bias corrections, and -- at the end of a GROUP of M
-// steps -- the cursor of the group's parity moves on by two groups and the parity flips.  Only the cursor of the group that
-// just finished is written: the one a concurrent prefetch of the next group reads never changes while it may be read.
-__device__ __forceinline__ void ctrl_advance(int64_t* ctrl) {
-  double* d = (double*)ctrl;
-  const int64_t M = ctrl[IGMC_CTRL_GROUP] > 0 ? ctrl[IGMC_CTRL_GROUP] : 1;
-  const int64_t gq = ctrl[IGMC_CTRL_GQ] & 1, gk = ctrl[IGMC_CTRL_GK] + 1;
-  ctrl[IGMC_CTRL_STEP] += 1;
-  ctrl[IGMC_CTRL_K] += 1;
-  if (gk >= M) {
-    ctrl[gq ? IGMC_CTRL_FIRST_ODD : IGMC_CTRL_FIRST] += 2 * M * ctrl[IGMC_CTRL_BATCH];
-    ctrl[IGMC_CTRL_GK] = 0;
-    ctrl[IGMC_CTRL_GQ] = gq ^ 1;
-  } else {
-    ctrl[IGMC_CTRL_GK] = gk;
-  }
-  ctrl[IGMC_CTRL_ADAM_T] += 1;
-  const double t = (double)ctrl[IGMC_CTRL_ADAM_T];
-  d[IGMC_CTRL_STEP_SIZE] = d[IGMC_CTRL_LR] / (1.0 - pow(d[IGMC_CTRL_BETA1], t));
-  d[IGMC_CTRL_INV_SQRT_BC2] = 1.0 / sqrt(1.0 - pow(d[IGMC_CTRL_BETA2], t));
-}
+// (ctrl_advance, the end of a step: model.h -- shared with the scoring tail of scores.hip)
 // ... after checking that the arena the step consumed held the batch of its cursor (and, under edge dropout, that batch's
 // draws): every extraction stamps its arena with the `first` it resolved.  A mismatch means a batch extracted from a stale
 // cursor or an arena overwritten too early; it sets sync_err instead of training on silently.

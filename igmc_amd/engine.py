@@ -304,6 +304,12 @@ class ModelWorkspace(object):
         else:
             self.lib.call('igmc_sse_accumulate', _p(out), batch.handle, _p(acc), _p(stream))
 
+    def scores_store(self, out, batch, acc, scores, labels, n, err, first=-1, stream=None, ctrl=None):
+        """``sse_accumulate`` that also files the batch's outputs / labels at ``first + g`` of ``scores`` / ``labels``
+        (``igmc_scores_store``); ``first`` = -1: the position the batch's extraction left in its arena."""
+        self.lib.call('igmc_scores_store', _p(out), batch.handle, _p(acc), _p(scores), _p(labels), int(n), int(first),
+                      _p(ctrl), _p(err), _p(stream))
+
     def close(self):
         if getattr(self, 'handle', None):
             self.lib.igmc_model_destroy(self.handle)
@@ -321,6 +327,30 @@ def adam_step(lib, params, grad, exp_avg, exp_avg_sq, n, step, lr, beta1=0.9, be
     """Fused Adam over a flat buffer (no model workspace needed)."""
     lib.call('igmc_adam_step', _p(params), _p(grad), _p(exp_avg), _p(exp_avg_sq), int(n), int(step), float(lr),
              float(beta1), float(beta2), float(eps), float(weight_decay), _p(stream))
+
+
+def select_extremes(keys, num, grid=0, lib=None, stream=None):
+    """The ``num`` first and the ``num`` last (reversed) of the stable ascending order of a device float32 vector
+    (``igmc_select_extremes``; reference ``train_eval.py:262-272``).  Returns device tensors ``(idx_low, idx_high, key_low,
+    key_high)`` of ``min(len(keys), num)`` entries; the keys never leave the device."""
+    import torch
+    lib = lib or _lib.load()
+    if keys.dtype != torch.float32 or keys.dim() != 1 or not keys.is_cuda or not keys.is_contiguous():
+        raise ValueError('keys: a contiguous 1-D float32 device tensor')
+    n, num = keys.numel(), int(num)
+    nbytes = lib.igmc_select_scratch_bytes(n, num, int(grid))
+    if nbytes < 0:
+        raise RuntimeError('igmc_select_scratch_bytes failed: %s' % lib.cdll.igmc_last_error().decode())
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=keys.device)
+    idx = torch.empty(2, num, dtype=torch.int32, device=keys.device)
+    key = torch.empty(2, num, dtype=torch.float32, device=keys.device)
+    count = torch.zeros(1, dtype=torch.int32, device=keys.device)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    lib.call('igmc_select_extremes', _p(keys.data_ptr()), n, num, _p(idx[0].data_ptr()), _p(idx[1].data_ptr()),
+             _p(key[0].data_ptr()), _p(key[1].data_ptr()), _p(count.data_ptr()), _p(scratch.data_ptr()), nbytes, int(grid),
+             _p(st))
+    c = min(n, num)
+    return idx[0, :c], idx[1, :c], key[0, :c], key[1, :c]
 
 
 def profile_enable(lib, on):

@@ -866,3 +866,57 @@ class EvalGraph(StepGraph):
         self.detach()
         self.check()
         return self.acc
+
+
+class ScoreGraph(EvalGraph):
+    """The scoring pass of ``visualize`` (reference ``train_eval.py:253-261``) through the grouped pipeline: an
+    :class:`EvalGraph` whose step keeps what it computed -- forward of a batch + ``igmc_scores_store`` (the squared-error
+    accumulation and tick of an evaluation step, which also files the batch's outputs and labels at their positions of the
+    pass).  Grouping, overlap, the ragged last batch and the sort-pool refusal are :class:`EvalGraph`'s; the position of a
+    replayed step's batch is the one its extraction resolved from the control block and left in the arena."""
+    SLOT = 'scoregraph'
+
+    def __init__(self, model, dataset, batch_size, use_graph=None, overlap=None, group=None):
+        EvalGraph.__init__(self, model, dataset, batch_size, use_graph=use_graph, overlap=overlap, group=group)
+        n = max(len(dataset), 1)
+        self.scores = torch.zeros(n, dtype=torch.float32, device=self.dev)
+        self.labels = torch.zeros(n, dtype=torch.float32, device=self.dev)
+        self.err = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        # the captured launches hold this address: a caller that keeps the object across calls compares it (model.to()
+        # re-creates the flat parameter buffer)
+        self.params_ptr = model.flat_parameters().data_ptr()
+
+    def _enqueue_step(self, arena, B):
+        m, st = self.model, torch.cuda.current_stream().cuda_stream
+        self.ws.forward(self.params_ptr, arena, self.out.data_ptr(), training=False,
+                        multiply_by=float(m.multiply_by), stream=st)
+        self.ws.scores_store(self.out.data_ptr(), arena, self.acc.data_ptr(), self.scores.data_ptr(),
+                             self.labels.data_ptr(), self.scores.numel(), self.err.data_ptr(), first=-1, stream=st,
+                             ctrl=self.ctrl.data_ptr())
+
+    def run(self, perm, epoch):
+        """Scores the links ``perm`` in that order: (scores, labels) of ``len(perm)`` entries -- views of buffers the next
+        pass overwrites -- and the device float64[2] (sum of squared errors, count) of ``EvalGraph.run``."""
+        if len(perm) > self.scores.numel():
+            raise ValueError('more positions than the dataset has links')
+        if self.params_ptr != self.model.flat_parameters().data_ptr():
+            raise RuntimeError('the model\'s flat parameter buffer was re-created (model.to()): build a new ScoreGraph')
+        self.err.zero_()
+        acc = EvalGraph.run(self, perm, epoch)
+        return self.scores[:len(perm)], self.labels[:len(perm)], acc
+
+    def check(self):
+        EvalGraph.check(self)
+        check_score_positions(self.err)
+
+
+def check_score_positions(err):
+    """Raises if a scoring step (``igmc_scores_store``) had no place for its batch (synchronises)."""
+    e = int(err.item())
+    if e:
+        what = []
+        if e & 1:
+            what.append('a batch reached past the end of the score buffers')
+        if e & 2:
+            what.append('a batch whose position in the pass is unknown (arena without a stamp)')
+        raise RuntimeError('scoring pass: %s (err=%d); the scores are incomplete' % ('; '.join(what), e))

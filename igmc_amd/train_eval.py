@@ -6,6 +6,7 @@ arguments, return values, log strings and checkpoint formats --
 * ``train``                      reference ``:149-179``
 * ``eval_loss`` / ``eval_rmse``  reference ``:182-205``
 * ``eval_loss_ensemble`` / ``eval_rmse_ensemble``   reference ``:208-245``
+* ``visualize``                  reference ``:248-322`` (``score_links``: its scoring loop with the scores kept on the GPU)
 
 What differs by design: the ``DataLoader`` yields device-resident batches extracted by HIP kernels (no
 worker processes / pickling / H2D); one optimisation step = extract -> forward -> loss (+ARR) -> backward
@@ -22,7 +23,7 @@ import torch.nn.functional as F
 
 from . import _lib, engine, parallel
 from .models import IGMC
-from .stepgraph import EvalGraph, StepGraph, _group_size_for
+from .stepgraph import EvalGraph, ScoreGraph, StepGraph, _group_size_for, check_score_positions
 from .util_functions import DeviceBatch
 
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
@@ -332,5 +333,160 @@ def eval_rmse_ensemble(model, checkpoints, loader, device, show_progress=False):
     return math.sqrt(eval_loss_ensemble(model, checkpoints, loader, device, True, show_progress))
 
 
-def visualize(*args, **kwargs):
-    raise NotImplementedError('visualize (reference train_eval.py:248-322) is a plotting helper and out of scope')
+SCORE_EPOCH = 1      # sampling key of a scoring pass: the one a fresh loader's first pass has (what ``test_once`` evaluates)
+
+
+def score_links(model, graphs, batch_size=50):
+    """Predictions for every link of ``graphs``, kept on the device (reference ``train_eval.py:253-261`` without the two
+    ``.tolist()`` round trips per batch): ``(R, Y, sse_cnt)`` -- ``R`` / ``Y`` float32 device tensors of ``len(graphs)``
+    predictions / labels in DATASET order (the reference scores with ``shuffle=False``), ``sse_cnt`` the float64 pair
+    (sum of squared errors, count) ``eval_loss`` accumulates over the same batches, bit for bit.  The whole set is scored
+    by the calling process (no sharding over ranks); the subgraphs are sampled under the key ``SCORE_EPOCH``."""
+    model.eval()
+    flat = model.flat_parameters()
+    n, B = len(graphs), int(batch_size)
+    if n < 1:
+        raise ValueError('score_links: the dataset has no links')
+    perm = torch.arange(n)
+    if not hasattr(model, 'forward_into') and n // B >= 8 and os.environ.get('IGMC_NO_EVAL_GRAPH', '0') != '1':
+        sg = getattr(graphs, '_scoregraph', None)
+        # (a captured launch holds the ADDRESS of the flat parameter buffer: model.to() re-creates that buffer, and the
+        #  graphs captured before it would read freed memory)
+        if sg is None or sg.model is not model or sg.B != B or sg.params_ptr != flat.data_ptr():
+            if sg is not None:
+                sg.detach()
+            sg = ScoreGraph(model, graphs, B, group=_group_size_for(n // B))
+            graphs._scoregraph = sg
+        R, Y, acc = sg.run(perm, SCORE_EPOCH)
+        R, Y, acc = R.clone(), Y.clone(), acc.clone()
+        _check_workspaces(model)
+        return R, Y, acc
+    dev = flat.device
+    R = torch.zeros(n, dtype=torch.float32, device=dev)
+    Y = torch.zeros(n, dtype=torch.float32, device=dev)
+    acc = torch.zeros(2, dtype=torch.float64, device=dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    pos = perm.to(device=dev, dtype=torch.int32)
+    for first in range(0, n, B):
+        data = graphs.extract(pos, first, min(B, n - first), epoch=SCORE_EPOCH, max_graphs=B)
+        ws = model._workspace(data)
+        st = torch.cuda.current_stream().cuda_stream
+        if hasattr(model, 'forward_into'):           # readout families other than IGMC's (DGCNN_RS)
+            model.forward_into(data, out, training=False, stream=st)
+        else:
+            ws.forward(flat.data_ptr(), data.arena, out.data_ptr(), training=False,
+                       multiply_by=float(model.multiply_by), stream=st)
+        ws.scores_store(out.data_ptr(), data.arena, acc.data_ptr(), R.data_ptr(), Y.data_ptr(), n, err.data_ptr(),
+                        first=first, stream=st)
+    check_score_positions(err)
+    _check_workspaces(model)
+    return R, Y, acc
+
+
+def scored_subgraphs(graphs, idx):
+    """The enclosing subgraphs of links ``idx`` (dataset positions) AS A SCORING PASS SAW THEM: one batch extracted under the
+    pass's sampling key (the sampler is keyed by (seed, epoch, link), not by the batch a link sits in), downloaded and
+    split into PyG-style ``Data`` objects.  Returns ``(list of Data, DeviceBatch)``; only these ``len(idx)`` subgraphs leave
+    the device."""
+    from .util_functions import _batch_to_tuples, construct_pyg_graph
+    idx = [int(i) for i in idx]
+    pos = torch.tensor(idx, dtype=torch.int32, device=graphs.link_y.device)
+    db = graphs.extract(pos, 0, len(idx), epoch=SCORE_EPOCH, slot='visualize', max_graphs=len(idx))
+    d = db._materialise()['raw']
+    out = []
+    for k, (u, v, r, labs, ml, y, un, vn) in enumerate(_batch_to_tuples(d, 2 * graphs.h + 2)):
+        out.append(construct_pyg_graph(u, v, r, labs, ml, y, None))
+    return out, db
+
+
+NODE_COLORS = ('xkcd:red', 'xkcd:blue', 'xkcd:orange', 'xkcd:lightblue', 'y', 'g')      # by node label (reference :277-278)
+
+
+def _target_pair_layout(nx, g):
+    """Bipartite layout (users in the left column, items in the right) with the target user (node 0) and the target item
+    (the first item node) moved to the lowest place of their columns (reference ``train_eval.py:286-295``)."""
+    users = [v for v, t in g.nodes(data='type') if t % 2 == 0]
+    targets = (0, len(users))
+    pos = nx.bipartite_layout(g, users)
+    lowest = (min(pos, key=lambda v: (pos[v][0], pos[v][1])), min(pos, key=lambda v: (-pos[v][0], pos[v][1])))
+    for tgt, low in zip(targets, lowest):
+        if tgt != low:
+            pos[tgt], pos[low] = pos[low], pos[tgt]
+    return pos, targets
+
+
+def draw_subgraphs(nx_graphs, scores, ys, path, class_values, num):
+    """The drawing third of ``visualize`` (reference ``train_eval.py:274-322``), callable without a GPU: a 2 x ``num`` grid
+    of subgraphs (first row: the ``num`` highest, second row: the ``num`` lowest), each in the layout of
+    :func:`_target_pair_layout`, nodes coloured by label, edges by their rating on the ``rainbow`` map over
+    ``class_values``, one colour bar (at most 20 ticks) and the title ``'{:.4f} ({:})'.format(score, y)`` under each.
+    Saves to ``path``; returns the (closed) figure."""
+    import matplotlib
+    if not os.environ.get('DISPLAY') and not os.environ.get('MPLBACKEND'):
+        matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    import networkx as nx
+    values = np.asarray(class_values).tolist()
+    cmap = matplotlib.colormaps['rainbow']
+    lo, hi = min(values), max(values)
+    fig = plt.figure(figsize=(20, 10))
+    axes = np.asarray(fig.subplots(2, num)).reshape(-1)
+    for ax in axes:
+        ax.axis('off')
+    for ax, g, score, y in zip(axes, nx_graphs, scores, ys):
+        pos, targets = _target_pair_layout(nx, g)
+        colours = [NODE_COLORS[t] for _, t in g.nodes(data='type')]
+        ratings = [values[rel] for _, _, rel in g.edges(data='type')]
+        nx.draw_networkx(g, pos, ax=ax, with_labels=False, node_size=150, node_color=colours, edge_color=ratings,
+                         edge_cmap=cmap, edge_vmin=lo, edge_vmax=hi)
+        for tgt in targets:         # the target pair drawn again, on top of the others
+            nx.draw_networkx_nodes(g, {tgt: pos[tgt]}, nodelist=[tgt], node_size=150, node_color=NODE_COLORS[tgt != 0], ax=ax)
+        ax.set_title('{:.4f} ({:})'.format(score, y), x=0.5, y=-0.05, fontsize=20)
+    fig.subplots_adjust(right=0.85)
+    ticks = values if len(values) <= 20 else np.linspace(lo, hi, 20, dtype=int).tolist()
+    scale = plt.cm.ScalarMappable(cmap=cmap, norm=plt.Normalize(vmin=lo, vmax=hi))
+    scale.set_array([])
+    bar = fig.colorbar(scale, cax=fig.add_axes([0.88, 0.15, 0.02, 0.7]), ticks=ticks)
+    bar.ax.tick_params(labelsize=22)
+    fig.savefig(path, bbox_inches='tight')
+    plt.close(fig)
+    return fig
+
+
+def visualize(model, graphs, res_dir, data_name, class_values, num=5, sort_by='prediction'):
+    """reference ``train_eval.py:248-322``: score every link of ``graphs``, take the ``num`` highest and the ``num`` lowest
+    by prediction (``'prediction'``), by label (``'true'``) or ``num`` + ``num`` at random (``'random'``), and draw their
+    enclosing subgraphs into ``<res_dir>/visualization_<data_name>_<sort_by>.pdf``.
+
+    The scores stay on the device (:func:`score_links`: the graph-replayed evaluation pipeline), the extremes are selected
+    there (``igmc_select_extremes``: the stable ascending order -- among EQUAL keys the lower index comes first, where the
+    reference's ``np.argsort`` leaves the pick to its sort), and only the ``2 * num`` selected subgraphs are downloaded.
+    THE DRAWN SUBGRAPH IS THE SCORED ONE: the selected links are re-extracted under the sampling key of the scoring pass
+    (:func:`scored_subgraphs`), which yields the node sets the pass scored; the reference indexes ``graphs[i]`` again, which
+    re-samples a dynamic dataset and can draw another subgraph than the one whose score is in the title.
+
+    Returns (the reference returns ``None``) ``{'highest': idx, 'lowest': idx, 'scores': [...], 'ys': [...], 'path': ...}``
+    with ``scores`` / ``ys`` in the order highest + lowest, as the titles are."""
+    from .util_functions import PyGGraph_to_nx
+    if sort_by not in ('prediction', 'true', 'random'):
+        raise ValueError("sort_by must be 'prediction', 'true' or 'random', not %r" % (sort_by,))
+    num = int(num)
+    if not 1 <= num <= 64:
+        raise ValueError('num must be in [1, 64]')
+    if model.flat_parameters().device.type != device.type:
+        model.to(device)
+    R, Y, _ = score_links(model, graphs, 50)
+    if sort_by == 'random':
+        order = np.random.permutation(range(len(graphs))).tolist()
+        highest, lowest = order[-num:][::-1], order[:num]
+    else:
+        low, high, _, _ = engine.select_extremes(R if sort_by == 'prediction' else Y, num)
+        highest, lowest = high.tolist(), low.tolist()
+    sel = torch.tensor(highest + lowest, dtype=torch.long, device=R.device)
+    scores, ys = R.index_select(0, sel).tolist(), Y.index_select(0, sel).tolist()
+    datas, _ = scored_subgraphs(graphs, highest + lowest)
+    nx_graphs = [PyGGraph_to_nx(d) for d in datas]
+    path = os.path.join(res_dir, 'visualization_{}_{}.pdf'.format(data_name, sort_by))
+    draw_subgraphs(nx_graphs, scores, ys, path, class_values, num)
+    return {'highest': highest, 'lowest': lowest, 'scores': scores, 'ys': ys, 'path': path}

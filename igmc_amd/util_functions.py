@@ -6,6 +6,7 @@ gfx950 engine.  Same names, argument meaning and return shapes as the reference:
 * ``links2subgraphs``                             reference ``:148-205``
 * ``subgraph_extraction_labeling``                reference ``:208-277``
 * ``construct_pyg_graph``                         reference ``:280-297``
+* ``PyGGraph_to_nx``                              reference ``:314-324``
 
 What differs by design: the rating graph lives in HBM once; a *batch* of links is
 extracted, labelled and collated by HIP kernels (``igmc_amd/csrc/extract.hip``) -- there are no
@@ -460,3 +461,21 @@ def links2subgraphs(Arow, Acol, links, labels, h=1, sample_ratio=1.0, max_nodes_
                 nf = [s[:nu], s[nu:]]
             out.append(construct_pyg_graph(u, v, r, labs, ml, y, nf))
     return out
+
+
+def PyGGraph_to_nx(data):
+    """reference ``:314-324``: a PyG-style subgraph as an undirected ``networkx`` graph.  Nodes are ``range(num_nodes)``,
+    isolated ones included, with attribute ``type`` = node label (argmax of the one-hot row); every edge carries ``type`` =
+    its relation id (both directed entries of a pair hold the same one in every graph this package builds; were they to
+    differ, the later entry would win, as in the reference); ``graph['rating']`` is the label.  networkx is imported
+    here, so the package imports without it."""
+    import networkx as nx
+    g = nx.Graph()
+    src, dst = data.edge_index[0].tolist(), data.edge_index[1].tolist()
+    for a, b, rel in zip(src, dst, data.edge_type.tolist()):
+        g.add_edge(a, b, type=rel)
+    g.add_nodes_from(range(data.num_nodes))
+    for node, label in enumerate(data.x.argmax(1).tolist()):
+        g.nodes[node]['type'] = label
+    g.graph['rating'] = data.y.item()
+    return g

@@ -344,6 +344,36 @@ int igmc_sse_accumulate(const float* d_out, const igmc_batch* b, double* d_acc, 
  * is then the forward launch + this one. */
 int igmc_sse_accumulate_tick(const float* d_out, const igmc_batch* b, double* d_acc, int64_t* d_ctrl, void* stream);
 
+/* ---- Scores kept on the device, and their extremes (reference train_eval.py:248-272: `visualize` scores every link of a
+ * dataset batch by batch, argsorts the scores -- or the labels -- and takes `num` links at both ends).
+ *
+ * igmc_scores_store is the tail of a SCORING step and replaces `R.extend(r.view(-1).tolist()); Y.extend(y.view(-1).tolist())`
+ * (train_eval.py:255-261) without the two host round trips per batch: igmc_sse_accumulate(_tick) -- same launch shape, same
+ * summation, same tick where d_ctrl is given, so d_acc is bit-identical to an evaluation pass's -- which also writes
+ * d_scores[first + g] = d_out[g] and d_labels[first + g] = y[g] for the batch's graphs g.  `first` is the batch's first
+ * position in the pass's link order: first_or_minus1 where it is >= 0 (eager launches), else the position the batch's
+ * extraction resolved from the device-side step control and left in its arena (captured / replayed launches: the step
+ * control's cursor is known on the device only).  n = capacity of d_scores / d_labels, in [1, 2^31).  A position outside
+ * [0, n) is not written and sets d_err[0] (int32, zeroed by the caller before the pass: bit 0 = a batch reached past n,
+ * bit 1 = no position given and the arena carries none); the caller reads d_err after the pass -- nothing is truncated
+ * silently. */
+int igmc_scores_store(const float* d_out, const igmc_batch* b, double* d_acc, float* d_scores, float* d_labels, int64_t n,
+                      int64_t first_or_minus1, int64_t* d_ctrl /* may be NULL: no tick */, int32_t* d_err, void* stream);
+/* igmc_select_extremes replaces `order = np.argsort(keys)`, `order[:num]`, `order[-num:][::-1]` (train_eval.py:262-272) for
+ * n float keys on the device, 1 <= n < 2^31, 1 <= num <= 64.
+ * THE ORDER: (key ascending, index ascending); every NaN behind every number (NaNs among themselves by index); -0.0 == 0.0.
+ * This is np.argsort(keys, kind='stable').  (The reference calls np.argsort with its default kind, which is not stable: among
+ * EQUAL keys its pick is an implementation detail; this one is defined.)
+ *   d_idx_low[i]  = order[i]              i < count = min(n, num)      d_key_low[i]  = d_keys[d_idx_low[i]]
+ *   d_idx_high[i] = order[n - 1 - i]      (the last `num` of the order, reversed)
+ * entries i >= count hold index -1, key 0; d_count[0] = count (d_key_low, d_key_high, d_count may be NULL).
+ * The result is a function of the keys alone: it does not depend on `grid`, the number of workgroups of the partial pass
+ * (0 = chosen from n; at most 1024).  d_scratch: igmc_select_scratch_bytes(n, num, grid) bytes (-1 on bad arguments), 8-byte
+ * aligned, owned by the caller -- nothing is allocated here, the two launches are capturable. */
+int64_t igmc_select_scratch_bytes(int64_t n, int num, int grid);
+int igmc_select_extremes(const float* d_keys, int64_t n, int num, int32_t* d_idx_low, int32_t* d_idx_high, float* d_key_low,
+                         float* d_key_high, int32_t* d_count, void* d_scratch, int64_t scratch_bytes, int grid, void* stream);
+
 /* Per-kernel timing of the last call (HIP events on the launch stream); names/ms arrays are
  * filled up to `cap` (ms = total over `calls` launches of that kernel since the last fetch);
  * returns the number of distinct kernels recorded, or <0 on error. */
