@@ -88,6 +88,10 @@ def build_parser():
     p.add_argument('--num-relations', type=int, default=5)
     p.add_argument('--multiply-by', type=int, default=1)
     p.add_argument('--visualize', action='store_true', default=False)
+    p.add_argument('--recommend', type=int, default=0, metavar='N',
+                   help='write the N best unseen items of every requested user (ranked on the device) and stop; 0 = off')
+    p.add_argument('--recommend-users', default=None, metavar='K|FILE',
+                   help='users to recommend for: the first K user ids, or a text file with one id per line (default: all)')
     p.add_argument('--ensemble', action='store_true', default=False)
     p.add_argument('--standard-rating', action='store_true', default=False)
     # sparsity experiment settings
@@ -114,6 +118,40 @@ def rating_maps(args):
             levels = np.arange(1, 6).tolist()
             post_rating_map = {x: int(i // (5 / args.num_relations)) for i, x in enumerate(levels)}
     return rating_map, post_rating_map
+
+
+def recommend_users(spec, n_users):
+    """``--recommend-users``: None = every user, a number K = the first K user ids, else a file with one id per line."""
+    if spec is None:
+        return None
+    if spec.isdigit():
+        return np.arange(min(int(spec), n_users), dtype=np.int32)
+    with open(spec) as f:
+        return np.asarray([int(line) for line in f if line.strip()], dtype=np.int32)
+
+
+def write_recommendations(model, train_graphs, args):
+    """``--recommend N``: ``<res_dir>/recommendations_<data_name>.tsv`` with lines ``user\trank\titem\tscore`` (ranks
+    from 1, best first; a user with fewer than N unseen items has fewer lines)."""
+    import time
+    from igmc_amd.recommend import recommend
+    users = recommend_users(args.recommend_users, train_graphs.graph.n_users)
+    stats = {}
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    items, scores, counts = recommend(model, train_graphs, users=users, n=args.recommend, batch_size=args.batch_size,
+                                      stats=stats)
+    items, scores, counts = items.cpu().numpy(), scores.cpu().numpy(), counts.cpu().numpy()      # (synchronises)
+    dt = time.perf_counter() - t0
+    ids = np.arange(train_graphs.graph.n_users) if users is None else users
+    path = os.path.join(args.res_dir, 'recommendations_{}.tsv'.format(args.data_name))
+    with open(path, 'w') as f:
+        for u, row, srow, c in zip(ids, items, scores, counts):
+            for r in range(int(c)):
+                f.write('%d\t%d\t%d\t%.6f\n' % (u, r + 1, row[r], srow[r]))
+    print('Recommended for {} users: {} candidates scored in {} pass(es), {:.0f} candidates/s; wrote {}'.format(
+        stats['users'], stats['candidates'], stats['passes'], stats['candidates'] / max(dt, 1e-9), path))
+    return path
 
 
 def main(argv=None):
@@ -246,6 +284,15 @@ def main(argv=None):
                                      res_dir=args.res_dir)
     # only rank 0 writes checkpoints (inside `logger`): nobody may look for them before it is done
     parallel.barrier()
+
+    if args.recommend > 0:
+        # no reference counterpart: the checkpoint's N best unseen items per user over adj_train, with the training set's
+        # extraction settings (and nothing else of what follows).  Rank 0 does the work; the other ranks wait at the barrier.
+        model.load_state_dict(torch.load(args.model_pos, map_location='cpu'))
+        if rank == 0:
+            write_recommendations(model, train_graphs, args)
+        parallel.barrier()
+        return rmse
 
     if args.visualize:
         # reference Main.py:423-435: the checkpoint's highest / lowest scored test subgraphs as a PDF (and nothing else of

@@ -71,6 +71,10 @@ SIGNATURES = {
     'igmc_scores_store': (i32, [vp, vp, vp, vp, vp, i64, i64, vp, vp, vp]),
     'igmc_select_scratch_bytes': (i64, [i64, i32, i32]),
     'igmc_select_extremes': (i32, [vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, i32, vp]),
+    'igmc_candidates_count': (i32, [vp, vp, i32, vp, i32, vp, vp, vp]),
+    'igmc_candidates_fill': (i32, [vp, vp, i32, vp, i32, vp, vp, vp, i64, vp, vp]),
+    'igmc_select_segments_scratch_bytes': (i64, [i32, i32, i32]),
+    'igmc_select_segments': (i32, [vp, vp, i32, i32, vp, vp, vp, vp, i64, i32, vp]),
     'igmc_comm_unique_id': (i32, [vp]),
     'igmc_comm_create': (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
     'igmc_comm_destroy': (None, [vp]),

@@ -1054,6 +1054,54 @@ extern "C" int igmc_select_extremes(const float* d_keys, int64_t n, int num, int
   return 0;
 }
 
+// ------------------------------------------------------------------ candidate links + the best of every segment (candidates.hip)
+extern "C" int igmc_candidates_count(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
+                                     int exclude_seen, int64_t* d_counts, int32_t* d_err, void* stream) {
+  if (!g || !d_users || !d_counts || !d_err) IGMC_FAIL("null argument");
+  if (nq < 1) IGMC_FAIL("nq must be at least 1");
+  igmc_launch_candidates_count(g->d, d_users, nq, d_item_ok, exclude_seen != 0, d_counts, d_err, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int igmc_candidates_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
+                                    int exclude_seen, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v,
+                                    int64_t capacity, int32_t* d_err, void* stream) {
+  if (!g || !d_users || !d_offsets || !d_link_u || !d_link_v || !d_err) IGMC_FAIL("null argument");
+  if (nq < 1) IGMC_FAIL("nq must be at least 1");
+  if (capacity < 1 || capacity > (int64_t)INT32_MAX) IGMC_FAIL("capacity must be in [1, 2^31)");
+  igmc_launch_candidates_fill(g->d, d_users, nq, d_item_ok, exclude_seen != 0, d_offsets, d_link_u, d_link_v, capacity, d_err,
+                              stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+static int segsel_split(int ns, int num, int geometry) {
+  if (ns < 1 || num < 1 || num > IGMC_SELECT_MAX_NUM || geometry < 0 || geometry > IGMC_SEGSEL_MAX_SPLIT) return -1;
+  return geometry > 0 ? geometry : igmc_segsel_default_split(ns);
+}
+static int64_t segsel_bytes(int ns, int num, int k) {      // (one workgroup per segment writes the result itself: a token word)
+  return k > 1 ? (int64_t)ns * k * num * (int64_t)sizeof(uint64_t) : (int64_t)sizeof(uint64_t);
+}
+extern "C" int64_t igmc_select_segments_scratch_bytes(int ns, int num, int geometry) {
+  const int k = segsel_split(ns, num, geometry);
+  if (k < 0) {
+    g_err = std::string(__func__) + ": ns must be at least 1, num in [1, 64], geometry in [0, 64]";
+    return -1;
+  }
+  return segsel_bytes(ns, num, k);
+}
+extern "C" int igmc_select_segments(const float* d_keys, const int64_t* d_seg_off, int ns, int num, int32_t* d_idx_out,
+                                    float* d_key_out, int32_t* d_count, void* d_scratch, int64_t scratch_bytes, int geometry,
+                                    void* stream) {
+  if (!d_keys || !d_seg_off || !d_idx_out || !d_count || !d_scratch) IGMC_FAIL("null argument");
+  const int k = segsel_split(ns, num, geometry);
+  if (k < 0) IGMC_FAIL("ns must be at least 1, num in [1, 64], geometry in [0, 64]");
+  if (scratch_bytes < segsel_bytes(ns, num, k)) IGMC_FAIL("scratch too small (igmc_select_segments_scratch_bytes)");
+  if (((uintptr_t)d_scratch & 7) != 0) IGMC_FAIL("scratch must be 8-byte aligned");
+  igmc_launch_select_segments(d_keys, d_seg_off, ns, num, k, d_scratch, d_idx_out, d_key_out, d_count, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
 // ------------------------------------------------------------------ device-side step control
 extern "C" int igmc_ctrl_tick(int64_t* d_ctrl, void* stream) {
   if (!d_ctrl) IGMC_FAIL("null ctrl");

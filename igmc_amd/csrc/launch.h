@@ -82,6 +82,18 @@ void igmc_launch_scores_store(const BatchDev& b, const float* out, double* acc, 
 int igmc_select_default_grid(int64_t n);
 void igmc_launch_select(const float* keys, int64_t n, int num, int grid, void* scratch, int32_t* idx_low, int32_t* idx_high,
                         float* key_low, float* key_high, int32_t* count, void* stream);
+// candidates.hip: the candidate links of a set of users (count, then fill at the offsets of the counts) and the `num` first of
+// every segment of a key array in the order (key descending, index ascending)
+#define IGMC_CAND_TILE_ITEMS 16384      // items of one LDS bitmap tile of the enumeration (wider graphs: tile after tile)
+#define IGMC_SEGSEL_MAX_SPLIT 64        // workgroups per segment at most (64 lists of 64 words are what the merge stages)
+void igmc_launch_candidates_count(const GraphDev& g, const int32_t* users, int nq, const uint8_t* item_ok, int exclude_seen,
+                                  int64_t* counts, int32_t* err, void* stream);
+void igmc_launch_candidates_fill(const GraphDev& g, const int32_t* users, int nq, const uint8_t* item_ok, int exclude_seen,
+                                 const int64_t* off, int32_t* link_u, int32_t* link_v, int64_t capacity, int32_t* err,
+                                 void* stream);
+int igmc_segsel_default_split(int ns);
+void igmc_launch_select_segments(const float* keys, const int64_t* seg_off, int ns, int num, int k, void* scratch,
+                                 int32_t* idx_out, float* key_out, int32_t* count, void* stream);
 int igmc_model_prepare(const ModelDev& m);
 void igmc_launch_adam(float* p, const float* g, float* m1, float* m2, int64_t n, float step_size,
                       float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd, int64_t* ctrl, int tick,

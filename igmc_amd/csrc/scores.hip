@@ -15,20 +15,7 @@
 // Selection is `num` rounds of "smallest word above the last one taken" (and its mirror): no sorting network, no atomics,
 // plain vector stores only; num <= 64 rounds over data that sits in L2 (1 M keys = 4 MB).
 #include "launch.h"
-
-#define SEL_LOW_NONE 0xFFFFFFFFFFFFFFFFull      // no word: above every word (a NaN's image is 0xFFFFFFFF, an index < 2^31)
-#define SEL_HIGH_NONE 0ull                       // no word: below every word (the image of -inf is 0x007FFFFF)
-
-// order-preserving image of a float: a < b  <=>  image(a) < image(b); -0.0 -> the image of +0.0; every NaN -> 0xFFFFFFFF
-__device__ __forceinline__ uint32_t sel_image(float f) {
-  if (f != f) return 0xFFFFFFFFu;
-  uint32_t u = __float_as_uint(f);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ unsigned long long sel_word(float f, uint32_t idx) {
-  return ((unsigned long long)sel_image(f) << 32) | (unsigned long long)idx;
-}
+#include "select.h"      // sel_image / sel_word, SEL_LOW_NONE / SEL_HIGH_NONE
 
 // (min, max) over the workgroup, result in every thread.  sm: 2 * 4 words of LDS.
 __device__ __forceinline__ void sel_block_minmax(unsigned long long& lo, unsigned long long& hi, unsigned long long* sm) {

@@ -353,6 +353,33 @@ def select_extremes(keys, num, grid=0, lib=None, stream=None):
     return idx[0, :c], idx[1, :c], key[0, :c], key[1, :c]
 
 
+def select_segments(keys, seg_off, num, geometry=0, lib=None, stream=None):
+    """The ``num`` first of every segment ``[seg_off[s], seg_off[s + 1])`` of a device float32 vector in the order (key
+    descending, index ascending, NaNs last) (``igmc_select_segments``; no reference counterpart).  ``seg_off``: device int64
+    ``[ns + 1]``.  Returns device tensors ``(idx int32 [ns, num], key float32 [ns, num], count int32 [ns])``: positions in
+    ``keys`` (-1 past the count), the keys' own bits (0 past the count); nothing leaves the device."""
+    import torch
+    lib = lib or _lib.load()
+    if keys.dtype != torch.float32 or keys.dim() != 1 or not keys.is_cuda or not keys.is_contiguous():
+        raise ValueError('keys: a contiguous 1-D float32 device tensor')
+    if seg_off.dtype != torch.int64 or seg_off.dim() != 1 or not seg_off.is_cuda or not seg_off.is_contiguous():
+        raise ValueError('seg_off: a contiguous 1-D int64 device tensor')
+    ns, num = seg_off.numel() - 1, int(num)
+    nbytes = lib.igmc_select_segments_scratch_bytes(ns, num, int(geometry))
+    if nbytes < 0:
+        raise RuntimeError('igmc_select_segments_scratch_bytes failed: %s' % lib.cdll.igmc_last_error().decode())
+    idx = torch.full((ns, num), -1, dtype=torch.int32, device=keys.device)
+    key = torch.zeros(ns, num, dtype=torch.float32, device=keys.device)
+    count = torch.zeros(ns, dtype=torch.int32, device=keys.device)
+    if keys.numel() == 0:          # (every segment is empty: nothing to launch over)
+        return idx, key, count
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=keys.device)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    lib.call('igmc_select_segments', _p(keys.data_ptr()), _p(seg_off.data_ptr()), ns, num, _p(idx.data_ptr()),
+             _p(key.data_ptr()), _p(count.data_ptr()), _p(scratch.data_ptr()), nbytes, int(geometry), _p(st))
+    return idx, key, count
+
+
 def profile_enable(lib, on):
     lib.igmc_profile_enable(int(bool(on)))
 

@@ -1,0 +1,302 @@
+"""Top-N unseen items per user, ranked on the device (no reference counterpart: the reference stops at the test RMSE).
+
+Scoring a link that is absent from the rating graph is the model's normal case (test links are not in ``adj_train``), so a
+recommendation is a scoring pass (:func:`igmc_amd.train_eval.score_links`) with two kernels around it
+(``igmc_amd/csrc/candidates.hip``):
+
+* ``igmc_candidates_count`` / ``igmc_candidates_fill`` write the unseen items of the requested users straight into device link
+  arrays -- users in the order given, item id ascending within a user;
+* ``igmc_select_segments`` takes the ``n`` best of every user's contiguous score segment in the order (score descending, item
+  id ascending, NaNs last).
+
+:class:`CandidateLinks` is the dataset-shaped object in between: it shares the rating graph and the extraction settings of an
+existing dataset, and its link buffers are device tensors of FIXED ADDRESS AND CAPACITY that every pass refills in place, so
+the hipGraph a scoring pass captured (``stepgraph.ScoreGraph``) is replayed by every later pass.
+
+SAMPLER POSITIONS.  The extraction's sampler is keyed by (seed, epoch, link position), and a candidate's position is its index
+in ITS PASS's list.  Where a per-hop cap binds (a neighbourhood larger than ``max_nodes_per_hop`` is sampled), a candidate's
+sampled subgraph -- and so its score -- depends on where it sits in its pass, hence on ``users_per_pass`` and on the users
+requested with it; every result is still a deterministic function of (seed, users, ``users_per_pass``).  Where no cap binds
+the extraction draws nothing and the scores do not depend on how the users are divided into passes.
+
+``link_y`` of a candidate list is zeros: the squared-error sums a scoring pass accumulates over candidates are MEANINGLESS and
+are dropped here.
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import engine
+from .stepgraph import ScoreGraph, _group_size_for
+from .train_eval import score_links
+
+DEFAULT_CAPACITY = 1 << 22      # candidates of one pass where the caller names no ``users_per_pass``: 4 Mi links are 48 MB of
+                                # link arrays and 48 MB of score / position buffers, and 84 000 batches of 50 per replayed pass
+_INT32_MAX = 2 ** 31 - 1
+
+_ERRORS = ((1, 'a user\'s candidates reach past the capacity of the link buffers'),
+           (2, 'a user id outside [0, n_users)'),
+           (4, 'segment offsets that are not the prefix sums of the counts'))
+
+
+def _dev_int32(x, dev, what):
+    t = torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x)
+    if t.dim() != 1:
+        raise ValueError('%s: a 1-D list of ids' % what)
+    if t.dtype not in (torch.int32, torch.int64, torch.int16, torch.uint8, torch.int8):
+        raise ValueError('%s: integer ids, not %s' % (what, t.dtype))
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+class CandidateLinks(object):
+    """Links without labels over the rating graph of an existing dataset, shaped like a dataset (``link_u``, ``link_v``,
+    ``link_y``, ``extract``, ``arena``, ``h``, ``seed``, ``max_nodes_per_hop``, ``sample_ratio``, ``num_features``,
+    ``__len__``): ``score_links`` and ``ScoreGraph`` take it as it is.
+
+    The link buffers hold ``capacity`` entries at fixed addresses; ``len()`` is the number of links the last
+    :meth:`refill` / :meth:`set_pairs` wrote.  After :meth:`refill`, ``users`` (int32 ``[nq]``) and ``offsets`` (int64
+    ``[nq + 1]``) describe the per-user segments; after :meth:`set_pairs` they are ``None``."""
+    dynamic = True          # subgraphs are extracted on the fly, under the sampling key of the pass
+
+    def __init__(self, dataset, capacity):
+        if getattr(dataset, '_side', None) is not None or getattr(dataset, 'u_features', None) is not None or \
+                getattr(dataset, 'v_features', None) is not None:
+            raise NotImplementedError('candidate links carry no side features: recommend over a dataset built without '
+                                      '--use-features (u_features / v_features)')
+        capacity = int(capacity)
+        if not 1 <= capacity <= _INT32_MAX:
+            raise ValueError('capacity must be in [1, 2^31): link positions are int32')
+        self.source = dataset
+        self.graph = dataset.graph
+        self.lib = dataset.graph.lib
+        self.device = dataset.device
+        self.h, self.sample_ratio, self.seed = dataset.h, dataset.sample_ratio, dataset.seed
+        self.max_nodes_per_hop = dataset.max_nodes_per_hop
+        self.capacity = capacity
+        dev = dataset.link_y.device
+        self.link_u = torch.zeros(capacity, dtype=torch.int32, device=dev)      # (zeros: user 0 / item 0, valid ids -- a replayed
+        self.link_v = torch.zeros(capacity, dtype=torch.int32, device=dev)      #  launch prefetches past the end of a short pass)
+        self.link_y = torch.zeros(capacity, dtype=torch.float32, device=dev)
+        self.n = 0
+        self.users, self.offsets = None, None
+        self._arenas = {}
+        self._side, self.n_side_features = None, 0
+        self._sizing = False
+
+    # ---- constructors
+    @classmethod
+    def for_users(cls, dataset, users, exclude_seen=True, item_mask=None, capacity=None):
+        """The candidates of ``users`` (ids, host or device; duplicates allowed, each gets its own segment): every item --
+        of ``item_mask`` (bool / uint8 ``[n_items]``) where given -- that the user has no entry for in the dataset's rating
+        graph (``exclude_seen``), users in the order given, item id ascending.  ``capacity``: entries of the link buffers
+        (default: what these users need)."""
+        dev = dataset.link_y.device
+        users = _dev_int32(users, dev, 'users')
+        mask = _item_mask(dataset.graph, item_mask, dev)
+        if capacity is None:
+            counts, _ = _count(dataset.graph, users, mask, exclude_seen)
+            capacity = max(1, int(counts.sum().item()))
+        self = cls(dataset, capacity)
+        self.refill(users, exclude_seen, mask)
+        return self
+
+    @classmethod
+    def from_pairs(cls, dataset, u, v, capacity=None):
+        """Arbitrary (user, item) pairs, host or device: "predict these links", no labels."""
+        self = cls(dataset, max(1, len(u)) if capacity is None else capacity)
+        self.set_pairs(u, v)
+        return self
+
+    # ---- refilling in place
+    def refill(self, users, exclude_seen=True, item_mask=None):
+        """Enumerate the candidates of ``users`` into the link buffers (two launches, one host read: the total)."""
+        dev = self.link_y.device
+        users = _dev_int32(users, dev, 'users')
+        if users.numel() < 1:
+            raise ValueError('no users')
+        mask = _item_mask(self.graph, item_mask, dev)
+        counts, err = _count(self.graph, users, mask, exclude_seen)
+        offsets = torch.zeros(users.numel() + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, out=offsets[1:])
+        total = int(offsets[-1].item())
+        if total > self.capacity:
+            raise ValueError('%d candidates do not fit the link buffers (capacity %d)' % (total, self.capacity))
+        st = torch.cuda.current_stream().cuda_stream
+        self.lib.call('igmc_candidates_fill', self.graph.handle, engine._p(users.data_ptr()), users.numel(),
+                      engine._p(None if mask is None else mask.data_ptr()), int(bool(exclude_seen)),
+                      engine._p(offsets.data_ptr()), engine._p(self.link_u.data_ptr()), engine._p(self.link_v.data_ptr()),
+                      self.capacity, engine._p(err.data_ptr()), engine._p(st))
+        e = int(err.item())
+        if e:
+            raise RuntimeError('candidate enumeration: %s (err=%d)' % ('; '.join(w for b, w in _ERRORS if e & b), e))
+        self.n, self.users, self.offsets = total, users, offsets
+        return self
+
+    def set_pairs(self, u, v):
+        dev = self.link_y.device
+        u, v = _dev_int32(u, dev, 'u'), _dev_int32(v, dev, 'v')
+        if u.numel() != v.numel():
+            raise ValueError('u and v differ in length')
+        if u.numel() > self.capacity:
+            raise ValueError('%d pairs do not fit the link buffers (capacity %d)' % (u.numel(), self.capacity))
+        if u.numel():
+            bad = ((u < 0) | (u >= self.graph.n_users) | (v < 0) | (v >= self.graph.n_items)).any()
+            if bool(bad.item()):
+                raise ValueError('a pair outside the rating graph (%d users x %d items)' % (self.graph.n_users,
+                                                                                         self.graph.n_items))
+        self.link_u[:u.numel()].copy_(u)
+        self.link_v[:v.numel()].copy_(v)
+        self.n, self.users, self.offsets = u.numel(), None, None
+        return self
+
+    # ---- dataset surface
+    def __len__(self):
+        return self.capacity if self._sizing else self.n
+
+    @property
+    def num_features(self):
+        return 2 * self.h + 2
+
+    def arena(self, max_graphs, slot=0):
+        key = (int(max_graphs), slot)
+        if key not in self._arenas:
+            self._arenas[key] = engine.Batch(self.graph, int(max_graphs), self.h, self.max_nodes_per_hop)
+        return self._arenas[key]
+
+    def extract(self, positions, first, B, epoch=0, slot=0, max_graphs=None, stream=None):
+        """Extract links ``positions[first:first+B]`` (device int32 tensor, or None = identity) into an arena."""
+        from .util_functions import DeviceBatch
+        arena = self.arena(max_graphs or B, slot)
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        arena.extract(self.link_u.data_ptr(), self.link_v.data_ptr(), self.link_y.data_ptr(),
+                      None if positions is None else positions.data_ptr(), first, B, self.sample_ratio, self.seed, epoch, st)
+        return DeviceBatch(self, arena, B, positions, first, None)
+
+
+def _item_mask(graph, item_mask, dev):
+    if item_mask is None:
+        return None
+    m = torch.as_tensor(np.asarray(item_mask) if not torch.is_tensor(item_mask) else item_mask)
+    if m.dim() != 1 or m.numel() != graph.n_items:
+        raise ValueError('item_mask: one entry per item (%d)' % graph.n_items)
+    return (m != 0).to(device=dev, dtype=torch.uint8).contiguous()
+
+
+def _count(graph, users, mask, exclude_seen):
+    """Per-user candidate counts (device int64) and the launch's error word (device int32, not read here)."""
+    counts = torch.zeros(users.numel(), dtype=torch.int64, device=users.device)
+    err = torch.zeros(1, dtype=torch.int32, device=users.device)
+    graph.lib.call('igmc_candidates_count', graph.handle, engine._p(users.data_ptr()), users.numel(),
+                   engine._p(None if mask is None else mask.data_ptr()), int(bool(exclude_seen)),
+                   engine._p(counts.data_ptr()), engine._p(err.data_ptr()),
+                   engine._p(torch.cuda.current_stream().cuda_stream))
+    return counts, err
+
+
+def _ensure_scoregraph(model, cands, B):
+    """``score_links`` builds a dataset's ``ScoreGraph`` on first use and sizes its position / score buffers by the length the
+    dataset has THEN; a candidate list has another length every pass.  So the object is built here, while the list reports
+    its capacity, and ``score_links`` finds it in place: the passes that follow replay what the first one captured."""
+    if hasattr(model, 'forward_into') or cands.capacity // B < 8 or os.environ.get('IGMC_NO_EVAL_GRAPH', '0') == '1':
+        return None
+    flat = model.flat_parameters()
+    sg = getattr(cands, '_scoregraph', None)
+    if sg is not None and sg.model is model and sg.B == B and sg.params_ptr == flat.data_ptr():
+        return sg
+    if sg is not None:
+        sg.detach()
+    cands._sizing = True
+    try:
+        # (buffers by the capacity; the group size by the pass at hand -- the steps outside whole graph launches run eagerly at
+        #  about twice the cost, and the passes of one call are of one size but the last)
+        sg = ScoreGraph(model, cands, B, group=_group_size_for(max(cands.n, 8 * B) // B))
+    finally:
+        cands._sizing = False
+    cands._scoregraph = sg
+    return sg
+
+
+def score_candidates(model, cands, batch_size=50):
+    """One prediction per candidate of ``cands``: a float32 device tensor of ``len(cands)`` entries in the list's order,
+    computed by ``score_links`` under the sampling key ``SCORE_EPOCH`` (position = index in the list)."""
+    B = int(batch_size)
+    if len(cands) < 1:
+        return torch.zeros(0, dtype=torch.float32, device=cands.link_y.device)
+    _ensure_scoregraph(model, cands, B)
+    R, _, _ = score_links(model, cands, B)          # (labels are zeros: the squared-error sums mean nothing)
+    return R
+
+
+def top_n(cands, scores, n, geometry=0):
+    """The ``n`` best candidates of every user of ``cands`` (after ``for_users`` / ``refill``) by ``scores`` (what
+    :func:`score_candidates` returned): ``(items int32 [nq, n], scores float32 [nq, n], counts int32 [nq])`` on the device.
+    Order: score descending, then item id ascending, NaNs last; a user with fewer than ``n`` candidates has ``count < n``,
+    items padded with -1 and scores with 0.  ``igmc_select_segments`` + one gather of ``link_v``."""
+    if cands.offsets is None:
+        raise ValueError('top_n needs per-user segments: a CandidateLinks filled by for_users() / refill()')
+    n = int(n)
+    if not 1 <= n <= 64:
+        raise ValueError('n must be in [1, 64]')
+    if scores.numel() != len(cands):
+        raise ValueError('one score per candidate: %d scores, %d candidates' % (scores.numel(), len(cands)))
+    idx, key, count = engine.select_segments(scores, cands.offsets, n, geometry, lib=cands.lib)
+    have = idx >= 0
+    items = torch.where(have, cands.link_v[:max(len(cands), 1)][idx.clamp(min=0).long()], torch.full_like(idx, -1))
+    return items, key, count
+
+
+def pass_plan(graph, n_users_requested, item_mask=None, users_per_pass=None):
+    """``(users_per_pass, capacity)`` of :func:`recommend`: by default the largest number of users whose WORST-CASE candidate
+    count (every item, or every item of the mask) stays within ``DEFAULT_CAPACITY`` -- at least one user, at most those
+    requested --; positions stay below 2^31 in every case."""
+    worst = max(1, graph.n_items if item_mask is None else int((torch.as_tensor(item_mask) != 0).sum().item()))
+    if users_per_pass is None:
+        upp = max(1, min(int(n_users_requested), DEFAULT_CAPACITY // worst))
+    else:
+        upp = max(1, min(int(users_per_pass), int(n_users_requested)))
+    if upp * worst > _INT32_MAX:
+        raise ValueError('%d users x %d items per pass: link positions must stay below 2^31' % (upp, worst))
+    return upp, upp * worst
+
+
+def recommend(model, dataset, users=None, n=10, batch_size=50, exclude_seen=True, item_mask=None, users_per_pass=None,
+              stats=None):
+    """Ranked top-``n`` items for ``users`` (default: every user of the rating graph) over the rating graph and with the
+    extraction settings of ``dataset`` (normally the training set): ``(items int32 [nq, n], scores float32 [nq, n], counts
+    int32 [nq])``, device tensors, rows in the order of ``users``, -1 / 0 behind a user's count.
+
+    ``exclude_seen``: items the user has an entry for in the rating graph are no candidates.  ``item_mask``: bool / uint8
+    ``[n_items]``, candidates are drawn from its items only.  The work is done in passes of ``users_per_pass`` users
+    (:func:`pass_plan`); all passes refill ONE :class:`CandidateLinks` -- kept as ``dataset._recommend_links`` and reused by
+    later calls that fit it -- and therefore replay one captured ``ScoreGraph``.  Nothing per candidate crosses to the host:
+    one total per pass does.  Works for ``DGCNN_RS`` too (``score_links``' eager path).
+
+    Where a per-hop cap binds, scores depend on ``users_per_pass`` (see the module docstring: SAMPLER POSITIONS).
+    ``stats``: a dict that receives ``users``, ``candidates`` and ``passes``."""
+    from . import train_eval
+    if model.flat_parameters().device.type != train_eval.device.type:
+        model.to(train_eval.device)
+    dev = dataset.link_y.device
+    g = dataset.graph
+    users = torch.arange(g.n_users, dtype=torch.int32, device=dev) if users is None else _dev_int32(users, dev, 'users')
+    nq = users.numel()
+    if nq < 1:
+        raise ValueError('no users')
+    mask = _item_mask(g, item_mask, dev)
+    upp, capacity = pass_plan(g, nq, mask, users_per_pass)
+    cands = getattr(dataset, '_recommend_links', None)
+    if cands is None or cands.capacity < capacity or cands.source is not dataset:
+        cands = dataset._recommend_links = CandidateLinks(dataset, capacity)
+    items, scores, counts, total = [], [], [], 0
+    for q0 in range(0, nq, upp):
+        cands.refill(users[q0:q0 + upp], exclude_seen, mask)
+        total += len(cands)
+        R = score_candidates(model, cands, batch_size)
+        i, s, c = top_n(cands, R, n)
+        items.append(i)
+        scores.append(s)
+        counts.append(c)
+    if stats is not None:
+        stats.update(users=nq, candidates=total, passes=len(items))
+    return torch.cat(items, 0), torch.cat(scores, 0), torch.cat(counts, 0)

@@ -374,6 +374,40 @@ int64_t igmc_select_scratch_bytes(int64_t n, int num, int grid);
 int igmc_select_extremes(const float* d_keys, int64_t n, int num, int32_t* d_idx_low, int32_t* d_idx_high, float* d_key_low,
                          float* d_key_high, int32_t* d_count, void* d_scratch, int64_t scratch_bytes, int grid, void* stream);
 
+/* ---- Candidate links and the best of every user's segment (no reference counterpart: the reference has no recommendation
+ * path; by hand it would be a host loop over the complement of every user's row, an upload of the pairs and a host argsort of
+ * the scores pulled back).
+ *
+ * igmc_candidates_count / igmc_candidates_fill enumerate, for the users d_users[0..nq) IN THE ORDER GIVEN (duplicates allowed:
+ * each gets a segment of its own), the items v ascending with d_item_ok[v] != 0 (uint8[n_items]; NULL = every item) and, where
+ * exclude_seen != 0, no entry (u, v) in the graph.  _count writes the segments' lengths to d_counts (int64[nq]); the caller
+ * turns them into d_offsets (int64[nq + 1], offsets[0] = 0, an inclusive prefix sum behind it) and _fill writes
+ * d_link_u[p] = u, d_link_v[p] = v (int32) for the p of [offsets[q], offsets[q + 1]).  capacity = entries of d_link_u /
+ * d_link_v, in [1, 2^31): nothing is written at or past it.  d_err[0] (int32, zeroed by the caller, read after the launches):
+ * bit 0 = a segment reaches past capacity (its links there are missing), bit 1 = a user id outside [0, n_users) (no row is
+ * read; its segment is empty), bit 2 = the offsets are not the prefix sums of the counts.  One launch each, capturable. */
+int igmc_candidates_count(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok /* may be NULL */,
+                          int exclude_seen, int64_t* d_counts, int32_t* d_err, void* stream);
+int igmc_candidates_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok /* may be NULL */,
+                         int exclude_seen, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v, int64_t capacity,
+                         int32_t* d_err, void* stream);
+/* igmc_select_segments: the `num` first of every segment [d_seg_off[s], d_seg_off[s + 1]) of d_keys, s < ns (no reference
+ * counterpart; by hand `np.lexsort` per user on the host), 1 <= num <= 64, d_seg_off[ns] < 2^31.
+ * THE ORDER: key DESCENDING, then index ascending; every NaN behind every number (NaNs among themselves by index);
+ * -0.0 == 0.0.  Per segment that is np.lexsort((idx, np.where(np.isnan(k), np.inf, -k))).  It is NOT the reverse of
+ * igmc_select_extremes' order: among equal keys the LOWER index comes first here (of two items predicted alike the lower id
+ * ranks first), where the "highest" list of igmc_select_extremes takes the higher index first.
+ *   d_idx_out[s * num + r] = position IN d_keys (not in the segment) of the r-th of segment s     r < count_s = min(len_s, num)
+ *   d_key_out[s * num + r] = d_keys[that position], its own bits (d_key_out may be NULL)
+ * entries r >= count_s hold index -1, key 0; d_count[s] = count_s.
+ * geometry: 0 = chosen from ns (one workgroup per segment from 257 segments on; fewer segments are split so that long ones do
+ * not sit on one workgroup); k in [1, 64] = k workgroups per segment and a merge.  The result is a function of the keys and
+ * the offsets alone, whatever the geometry.  d_scratch: igmc_select_segments_scratch_bytes(ns, num, geometry) bytes (-1 on bad
+ * arguments), 8-byte aligned, owned by the caller; nothing is allocated here, the launches are capturable. */
+int64_t igmc_select_segments_scratch_bytes(int ns, int num, int geometry);
+int igmc_select_segments(const float* d_keys, const int64_t* d_seg_off, int ns, int num, int32_t* d_idx_out, float* d_key_out,
+                         int32_t* d_count, void* d_scratch, int64_t scratch_bytes, int geometry, void* stream);
+
 /* Per-kernel timing of the last call (HIP events on the launch stream); names/ms arrays are
  * filled up to `cap` (ms = total over `calls` launches of that kernel since the last fetch);
  * returns the number of distinct kernels recorded, or <0 on error. */
