@@ -355,11 +355,10 @@ extern "C" int igmc_batch_create(const igmc_graph* g, int max_graphs, int hop, i
   // item-side workgroups of the dense per-layer kernels (denselayer.hip)
   // (IGMC_DL_ALWAYS=1: also for small slots -- lets tests run those kernels on small cases)
   {
-    const char* da = getenv("IGMC_DL_ALWAYS");
     // (more than five relations: the subgraph kernel does not take the arena whatever its slots, the dense-layer kernels do)
     // ... and so for a layer-0 table of more than 32 rows (two hops: the graph's relations x 6 labels)
     const int nlab = 2 * hop + 2;
-    if (d.relm && (cap_u > 128 || cap_v > 128 || g->max_rel + 1 > G2_NR || (g->max_rel + 1) * nlab + nlab + 1 > 32 || (da && atoi(da) == 1))) fail |= M.get(&d.relmT, (size_t)Bc * cap_v * d.relmT_ld);
+    if (d.relm && (cap_u > 128 || cap_v > 128 || g->max_rel + 1 > G2_NR || (g->max_rel + 1) * nlab + nlab + 1 > 32 || igmc_dl_always())) fail |= M.get(&d.relmT, (size_t)Bc * cap_v * d.relmT_ld);
   }
   fail |= M.get(&d.s_gid, Bc * slot) | M.get(&d.s_lab, Bc * slot) | M.get(&d.s_deg, Bc * slot) |
           M.get(&d.t_list, Bc * slot) | M.get(&d.t_dist, Bc * slot);
@@ -874,58 +873,38 @@ extern "C" int64_t igmc_param_offset(const igmc_model* m, int layer, int which, 
   return off;
 }
 
-// the per-layer row-walker kernels read the collated CSR; the matrix-core subgraph kernel does not
-static void csr_for_model(const igmc_model* m, const igmc_batch* b, int dense_capable_call, void* stream) {
-  if (!b->lean) return;
-  G2Layout lay;
-  int cs = 1;
-  const int rows0 = m->d.R * m->d.L + m->d.L + 1;
-  if (dense_capable_call && rows0 <= 32 && igmc_g2_eligible(m->d, b->d, b->last_B, &lay, &cs)) return;
-  // dense per-layer path: it needs the node arrays only, and a lean extraction of such an arena (one with the transposed
-  // block) has left them behind (k_emit_nodes in the extraction branch)
-  if (igmc_dl_eligible(m->d, b->d, b->last_B) && b->d.relm && b->last_B > 0) return;
-  if (dense_capable_call && igmc_dl_wide(m->d, b->d, b->last_B) && b->last_B > 0) return;      // (relation groups: same)
-  ensure_csr(b, stream);
+static StepPlan plan_query(const igmc_model* m, const igmc_batch* b, int B) {      // what a step on (arena, B) would launch
+  StepPlan sp;
+  igmc_step_plan(m->d, b->d, B, IGMC_CALL_STEP, &sp);
+  return sp;
 }
 
-// 1 when the dense per-layer kernels (k_dl_layer) take the conv layers of this arena
+// 1 when the dense-layer kernels (k_dl_*) take the conv layers of this arena
 extern "C" int igmc_model_dense_layers(const igmc_model* m, const igmc_batch* b, int B) {
-  if (!m || !b) return 0;
-  return (igmc_dl_eligible(m->d, b->d, B) || igmc_dl_wide(m->d, b->d, B)) ? 1 : 0;
+  return (m && b) ? plan_query(m, b, B).dense_layers : 0;
 }
 
 extern "C" int igmc_model_dense_path(const igmc_model* m, const igmc_batch* b, int B) {
-  if (!m || !b) return 0;
-  G2Layout lay;
-  int cs = 1;
-  const int rows0 = m->d.R * m->d.L + m->d.L + 1;
-  return (rows0 <= 32 && m->d.D % 16 == 0 && igmc_g2_eligible(m->d, b->d, B, &lay, &cs)) ? 1 : 0;
+  return (m && b) ? plan_query(m, b, B).family == IGMC_FAM_G2 : 0;
 }
 
 extern "C" int igmc_model_step_form(const igmc_model* m, const igmc_batch* b, int B) {
-  if (!m || !b) return 0;
-  if (igmc_model_dense_path(m, b, B)) return 1;
-  if (igmc_dl_wide_gsplit(m->d, b->d, B)) return 3;
-  if (igmc_dl_wide(m->d, b->d, B) || (igmc_dl_eligible(m->d, b->d, B) && igmc_dl_fwd_eligible(m->d, b->d, B))) return 2;
-  return 0;
+  return (m && b) ? plan_query(m, b, B).step_form : 0;
 }
 
 extern "C" int igmc_model_step_geometry(const igmc_model* m, const igmc_batch* b, int B, int32_t* out, int n) {
   if (!m || !b || !out || n < 0) IGMC_FAIL("bad arguments");
   if (B < 1 || B > b->d.graph_cap) IGMC_FAIL("batch size outside the arena's capacity");
-  StepPlan sp;
-  igmc_step_plan(m->d, b->d, B, &sp);
+  const StepPlan sp = plan_query(m, b, B);
   const int g2 = sp.family == IGMC_FAM_G2, dense = sp.family == IGMC_FAM_DLF || sp.family == IGMC_FAM_DL;
-  int nqu = 0, nqv = 0;
-  if (dense) igmc_dl_split(b->d.cap_u, b->d.cap_v, B, &nqu, &nqv);
-  const int32_t v[IGMC_GEOM_N] = {igmc_model_step_form(m, b, B),
+  const int32_t v[IGMC_GEOM_N] = {sp.step_form,
                                   sp.family,
                                   g2 ? sp.cs : 0,
                                   g2 ? sp.grid : 0,
-                                  nqu,
-                                  nqv,
+                                  sp.nqu,
+                                  sp.nqv,
                                   sp.family == IGMC_FAM_ROWS ? 0 : sp.wide ? g2_groups(m->d.R, m->d.L) : 1,
-                                  sp.wide && igmc_dl_wide_gsplit(m->d, b->d, B),
+                                  sp.wide && sp.gsplit,
                                   g2 || sp.dlts,
                                   g2 ? sp.lay.kp : 0,
                                   dense && sp.dlb};
@@ -943,22 +922,55 @@ static int check_fit(igmc_model* m, const igmc_batch* b, std::string* why) {
   return 0;
 }
 
+// What the calls that run the model on a batch share.  check_call: the fit and the caller's buffers; begin_call: the arena's
+// side features, the plan of the call and -- where that plan walks rows -- the collated CSR, which a lean extraction has not
+// emitted; end_call: what igmc_model_backward / igmc_step_finish need to know about the call.
+static int check_call(igmc_model* m, const igmc_batch* b, bool buffers, std::string* why) {
+  if (check_fit(m, b, why)) return 1;
+  if (!buffers) { *why = "null buffer"; return 1; }
+  return 0;
+}
+static StepPlan begin_call(igmc_model* m, const igmc_batch* b, int kind, void* stream) {
+  m->d.side = b->side;
+  StepPlan sp;
+  igmc_step_plan(m->d, b->d, b->last_B, kind, &sp);
+  if (b->lean && sp.needs_csr) ensure_csr(b, stream);
+  return sp;
+}
+static void end_call(igmc_model* m, const igmc_batch* b, int training, int use_edge_flags) {
+  m->last_B = b->last_B;
+  m->last_training = training;
+  m->last_flags = use_edge_flags;
+}
+
+// Adam's bias corrections of step t as the kernels take them: lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t).  With a control
+// block the kernel forms them from the block's own step counter: zeros
+struct AdamScalars {
+  float step_size, inv_sqrt_bc2;
+};
+static AdamScalars adam_scalars(const int64_t* d_ctrl, int64_t t, float lr, float beta1, float beta2) {
+  AdamScalars a = {0.f, 0.f};
+  if (!d_ctrl) {
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)t);
+    const double bc2 = 1.0 - std::pow((double)beta2, (double)t);
+    a.step_size = (float)((double)lr / bc1);
+    a.inv_sqrt_bc2 = (float)(1.0 / std::sqrt(bc2));
+  }
+  return a;
+}
+
 extern "C" int igmc_model_forward(igmc_model* m, const float* d_params, const igmc_batch* b, int training,
                                   int use_edge_flags, const uint8_t* d_lin_mask, uint64_t seed, uint64_t step,
                                   float multiply_by, float* d_out, void* stream) {
   std::string why;
-  if (check_fit(m, b, &why)) IGMC_FAIL(why);
-  if (!d_params || !d_out) IGMC_FAIL("null buffer");
-  m->d.side = b->side;
-  csr_for_model(m, b, !training, stream);
+  if (check_call(m, b, d_params && d_out, &why)) IGMC_FAIL(why);
+  const StepPlan sp = begin_call(m, b, training ? IGMC_CALL_CONV : IGMC_CALL_EVAL, stream);
   ImgScope img(m, d_params);
-  igmc_launch_forward(m->d, m->ax, b->d, d_params, b->last_B, training, use_edge_flags, d_lin_mask, seed, step, multiply_by,
+  igmc_launch_forward(m->d, b->d, sp, d_params, b->last_B, training, use_edge_flags, d_lin_mask, seed, step, multiply_by,
                       d_out, stream);
   img.done_unchanged();
   HIPCHECK(hipGetLastError());
-  m->last_B = b->last_B;
-  m->last_training = training;
-  m->last_flags = use_edge_flags;
+  end_call(m, b, training, use_edge_flags);
   return 0;
 }
 
@@ -968,7 +980,9 @@ extern "C" int igmc_model_backward(igmc_model* m, const float* d_params, const i
   if (check_fit(m, b, &why)) IGMC_FAIL(why);
   if (!m->last_training || m->last_B != b->last_B) IGMC_FAIL("backward needs a preceding training-mode forward on this batch");
   if (!d_params || !d_gout || !d_grad) IGMC_FAIL("null buffer");
-  igmc_launch_backward(m->d, m->ax, b->d, d_params, b->last_B, m->last_flags, d_gout, 0, 0.f, multiply_by, 2.f, 0.f, d_grad,
+  StepPlan sp;      // (the arena's CSR: the training forward's call saw to it)
+  igmc_step_plan(m->d, b->d, b->last_B, IGMC_CALL_CONV, &sp);
+  igmc_launch_backward(m->d, b->d, sp, d_params, b->last_B, m->last_flags, d_gout, 0, 0.f, multiply_by, 2.f, 0.f, d_grad,
                        stream);
   HIPCHECK(hipGetLastError());
   return 0;
@@ -979,18 +993,14 @@ extern "C" int igmc_model_loss_grad(igmc_model* m, const float* d_params, const 
                                     float ARR, float grad_scale, float arr_scale, float* d_out, float* d_grad,
                                     float* d_loss, void* stream) {
   std::string why;
-  if (check_fit(m, b, &why)) IGMC_FAIL(why);
-  if (!d_params || !d_out || !d_grad) IGMC_FAIL("null buffer");
-  m->d.side = b->side;
-  csr_for_model(m, b, 1, stream);
+  if (check_call(m, b, d_params && d_out && d_grad, &why)) IGMC_FAIL(why);
+  const StepPlan sp = begin_call(m, b, IGMC_CALL_STEP, stream);
   ImgScope img(m, d_params);
-  igmc_launch_loss_grad(m->d, m->ax, b->d, (float*)d_params, b->last_B, use_edge_flags, d_lin_mask, seed, step,
+  igmc_launch_loss_grad(m->d, b->d, sp, (float*)d_params, b->last_B, use_edge_flags, d_lin_mask, seed, step,
                         multiply_by, ARR, grad_scale, arr_scale, d_out, d_grad, d_loss, nullptr, stream);
   img.done_unchanged();
   HIPCHECK(hipGetLastError());
-  m->last_B = b->last_B;
-  m->last_training = 1;
-  m->last_flags = use_edge_flags;
+  end_call(m, b, 1, use_edge_flags);
   return 0;
 }
 
@@ -998,10 +1008,9 @@ extern "C" int igmc_adam_step(float* d_params, const float* d_grad, float* d_exp
                               int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay,
                               void* stream) {
   if (!d_params || !d_grad || !d_exp_avg || !d_exp_avg_sq || n <= 0 || step < 1) IGMC_FAIL("bad arguments");
-  const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-  igmc_launch_adam(d_params, d_grad, d_exp_avg, d_exp_avg_sq, n, (float)((double)lr / bc1),
-                   (float)(1.0 / std::sqrt(bc2)), beta1, beta2, eps, weight_decay, nullptr, 0, stream);
+  const AdamScalars as = adam_scalars(nullptr, step, lr, beta1, beta2);
+  igmc_launch_adam(d_params, d_grad, d_exp_avg, d_exp_avg_sq, n, as.step_size, as.inv_sqrt_bc2, beta1, beta2, eps, weight_decay,
+                   nullptr, 0, stream);
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -1179,14 +1188,8 @@ extern "C" int igmc_step_finish(igmc_model* m, const igmc_batch* b, float* d_par
                                 float weight_decay, void* stream) {
   if (!m || !b || !d_params || !d_grad || !d_exp_avg || !d_exp_avg_sq || !d_loss) IGMC_FAIL("bad arguments");
   if (!d_ctrl && step < 1) IGMC_FAIL("step must be >= 1");
-  float step_size = 0.f, inv = 0.f;
-  if (!d_ctrl) {
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-    step_size = (float)((double)lr / bc1);
-    inv = (float)(1.0 / std::sqrt(bc2));
-  }
-  igmc_launch_finish(m->d, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, step_size, inv, beta1, beta2, eps,
+  const AdamScalars as = adam_scalars(d_ctrl, step, lr, beta1, beta2);
+  igmc_launch_finish(m->d, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, as.step_size, as.inv_sqrt_bc2, beta1, beta2, eps,
                      weight_decay, d_ctrl, ARR, d_loss, d_total, m->last_flags, stream);
   m->img_valid = 0;      // (the parameters moved, the weight images did not)
   m->img_hint = 0;
@@ -1200,28 +1203,18 @@ extern "C" int igmc_train_step(igmc_model* m, float* d_params, const igmc_batch*
                                double* d_total, int64_t* d_ctrl, int64_t adam_t, float lr, float beta1, float beta2,
                                float eps, float weight_decay, void* stream) {
   std::string why;
-  if (check_fit(m, b, &why)) IGMC_FAIL(why);
-  if (!d_params || !d_out || !d_grad || !d_exp_avg || !d_exp_avg_sq || !d_loss) IGMC_FAIL("null buffer");
+  if (check_call(m, b, d_params && d_out && d_grad && d_exp_avg && d_exp_avg_sq && d_loss, &why)) IGMC_FAIL(why);
   if (!d_ctrl && adam_t < 1) IGMC_FAIL("adam_t must be >= 1");
-  float step_size = 0.f, inv = 0.f;
-  if (!d_ctrl) {
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)adam_t);
-    const double bc2 = 1.0 - std::pow((double)beta2, (double)adam_t);
-    step_size = (float)((double)lr / bc1);
-    inv = (float)(1.0 / std::sqrt(bc2));
-  }
-  m->d.side = b->side;
-  csr_for_model(m, b, 1, stream);
+  const AdamScalars as = adam_scalars(d_ctrl, adam_t, lr, beta1, beta2);
+  const StepPlan sp = begin_call(m, b, IGMC_CALL_STEP, stream);
   ImgScope img(m, d_params);
   int emitted = 0;
-  igmc_launch_train_step(m->d, m->ax, b->d, d_params, b->last_B, use_edge_flags, d_lin_mask, seed, step, multiply_by, ARR,
-                         d_out, d_grad, d_exp_avg, d_exp_avg_sq, step_size, inv, beta1, beta2, eps, weight_decay, d_ctrl,
-                         m->done_ctr, d_loss, d_total, stream, 0.f, nullptr, &emitted);
+  igmc_launch_train_step(m->d, b->d, sp, d_params, b->last_B, use_edge_flags, d_lin_mask, seed, step, multiply_by, ARR,
+                         d_out, d_grad, d_exp_avg, d_exp_avg_sq, as.step_size, as.inv_sqrt_bc2, beta1, beta2, eps, weight_decay,
+                         d_ctrl, m->done_ctr, d_loss, d_total, stream, 0.f, nullptr, &emitted);
   img.done_updated(emitted);
   HIPCHECK(hipGetLastError());
-  m->last_B = b->last_B;
-  m->last_training = 1;
-  m->last_flags = use_edge_flags;
+  end_call(m, b, 1, use_edge_flags);
   return 0;
 }
 
@@ -1650,7 +1643,7 @@ extern "C" int igmc_allreduce_grads(igmc_comm* c, float* d_flat_grad, int64_t n,
 
 // One optimisation step of a data-parallel job (reference train_eval.py:157-177 per rank, gradients averaged over the
 // ranks): igmc_train_step with the exchange INSIDE the step.  Where the step keeps its gradient sources in reduced form
-// (igmc_step_exchange_inside: the subgraph kernel's tables, the per-layer path's basis-space sums) those are summed over
+// (StepPlan::exchange_inside: the subgraph kernel's tables, the per-layer path's basis-space sums) those are summed over
 // the ranks between their reduction and the gradient / Adam kernel -- the kernels of the single-GPU step, one grouped
 // collective more; elsewhere the flat gradient is formed, all-reduced and handed to the Adam kernel.  comm == NULL: one rank.
 extern "C" int igmc_train_step_dp(igmc_model* m, igmc_comm* comm, float* d_params, const igmc_batch* b, int use_edge_flags,
@@ -1659,44 +1652,34 @@ extern "C" int igmc_train_step_dp(igmc_model* m, igmc_comm* comm, float* d_param
                                   double* d_total, int64_t* d_ctrl, int64_t adam_t, float lr, float beta1, float beta2,
                                   float eps, float weight_decay, void* stream) {
   std::string why;
-  if (check_fit(m, b, &why)) IGMC_FAIL(why);
-  if (!d_params || !d_out || !d_grad || !d_exp_avg || !d_exp_avg_sq || !d_loss) IGMC_FAIL("null buffer");
+  if (check_call(m, b, d_params && d_out && d_grad && d_exp_avg && d_exp_avg_sq && d_loss, &why)) IGMC_FAIL(why);
   if (!d_ctrl && adam_t < 1) IGMC_FAIL("adam_t must be >= 1");
-  float step_size = 0.f, inv = 0.f;
-  if (!d_ctrl) {
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)adam_t);
-    const double bc2 = 1.0 - std::pow((double)beta2, (double)adam_t);
-    step_size = (float)((double)lr / bc1);
-    inv = (float)(1.0 / std::sqrt(bc2));
-  }
+  const AdamScalars as = adam_scalars(d_ctrl, adam_t, lr, beta1, beta2);
   const int world = comm ? comm->world : 1;
   const int B = b->last_B;
   const float gscale = 1.0f / ((float)B * (float)world);
-  m->d.side = b->side;
-  csr_for_model(m, b, 1, stream);
+  const StepPlan sp = begin_call(m, b, IGMC_CALL_STEP, stream);
   ImgScope img(m, d_params);
   int emitted = 0;
-  if (igmc_step_exchange_inside(m->d, b->d, B)) {
+  if (sp.exchange_inside) {
     StepExchange x = {comm_sum2, comm, (comm && comm->peer) ? comm->d_state + 2 : nullptr};
     // (the ARR term depends on the weights only: every rank adds it in full AFTER the exchange)
-    const int rc = igmc_launch_train_step(m->d, m->ax, b->d, d_params, B, use_edge_flags, d_lin_mask, seed, step, multiply_by,
-                                          ARR, d_out, d_grad, d_exp_avg, d_exp_avg_sq, step_size, inv, beta1, beta2, eps,
-                                          weight_decay, d_ctrl, m->done_ctr, d_loss, d_total, stream, gscale,
+    const int rc = igmc_launch_train_step(m->d, b->d, sp, d_params, B, use_edge_flags, d_lin_mask, seed, step, multiply_by,
+                                          ARR, d_out, d_grad, d_exp_avg, d_exp_avg_sq, as.step_size, as.inv_sqrt_bc2, beta1,
+                                          beta2, eps, weight_decay, d_ctrl, m->done_ctr, d_loss, d_total, stream, gscale,
                                           comm ? &x : nullptr, &emitted);
     img.done_updated(emitted);
     if (rc) return 1;
   } else {
-    igmc_launch_loss_grad(m->d, m->ax, b->d, d_params, B, use_edge_flags, d_lin_mask, seed, step, multiply_by, ARR, gscale,
+    igmc_launch_loss_grad(m->d, b->d, sp, d_params, B, use_edge_flags, d_lin_mask, seed, step, multiply_by, ARR, gscale,
                           1.0f / (float)world, d_out, d_grad, nullptr, nullptr, stream);
     if (comm && comm_sum2(comm, d_grad, m->d.n_params, nullptr, 0, stream)) return 1;
-    igmc_launch_finish(m->d, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, step_size, inv, beta1, beta2, eps,
+    igmc_launch_finish(m->d, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, as.step_size, as.inv_sqrt_bc2, beta1, beta2, eps,
                        weight_decay, d_ctrl, ARR, d_loss, d_total, use_edge_flags, stream);
     img.done_updated(0);
   }
   HIPCHECK(hipGetLastError());
-  m->last_B = B;
-  m->last_training = 1;
-  m->last_flags = use_edge_flags;
+  end_call(m, b, 1, use_edge_flags);
   return 0;
 }
 
@@ -1803,7 +1786,9 @@ extern "C" int igmc_sortpool_forward(igmc_sortpool* sp, const float* d_params, c
   igmc_model* m = sp->m;
   ensure_csr(b, stream);
   igmc_launch_sp_pack(m->d, sp->d, d_params, sp->pe, stream);
-  igmc_launch_conv_forward(m->d, b->d, sp->pe, b->last_B, training, use_edge_flags, stream);
+  StepPlan plan;
+  igmc_step_plan(m->d, b->d, b->last_B, IGMC_CALL_CONV, &plan);
+  igmc_launch_conv_forward(m->d, b->d, plan, sp->pe, b->last_B, training, use_edge_flags, stream);
   igmc_launch_sp_forward(m->d, sp->d, b->d, d_params, b->last_B, training, d_lin_mask, seed, step, d_out, stream);
   HIPCHECK(hipGetLastError());
   return 0;
@@ -1823,10 +1808,12 @@ extern "C" int igmc_sortpool_loss_grad(igmc_sortpool* sp, const float* d_params,
   igmc_launch_sp_pack(m->d, sp->d, d_params, sp->pe, stream);
   ModelDev md = m->d;        // (with the dense readout gradient: the conv kernels then know which backward form follows)
   for (int l = 0; l < 3; ++l) md.dcat[l] = sp->d.dcat[l];
-  igmc_launch_conv_forward(md, b->d, sp->pe, B, 1, use_edge_flags, stream);
+  StepPlan plan;
+  igmc_step_plan(md, b->d, B, IGMC_CALL_CONV, &plan);
+  igmc_launch_conv_forward(md, b->d, plan, sp->pe, B, 1, use_edge_flags, stream);
   igmc_launch_sp_forward(m->d, sp->d, b->d, d_params, B, 1, d_lin_mask, seed, step, d_out, stream);
   igmc_launch_sp_backward(m->d, sp->d, b->d, d_params, B, grad_scale > 0.f ? grad_scale : 1.f / (float)B, stream);
-  igmc_launch_conv_backward(md, b->d, sp->pe, B, use_edge_flags, ARR * arr_scale, sp->ge, stream);
+  igmc_launch_conv_backward(md, b->d, plan, sp->pe, B, use_edge_flags, ARR * arr_scale, sp->ge, stream);
   igmc_launch_sp_wgrad(m->d, sp->d, b->d, B, sp->ge, d_grad, stream);
   if (d_loss) igmc_launch_loss(m->d, b->d, ARR, d_loss, stream);
   HIPCHECK(hipGetLastError());
@@ -1840,17 +1827,11 @@ extern "C" int igmc_sortpool_step_finish(igmc_sortpool* sp, const igmc_batch* b,
                                          float weight_decay, void* stream) {
   if (!sp || !b || !d_params || !d_grad || !d_exp_avg || !d_exp_avg_sq || !d_loss) IGMC_FAIL("bad arguments");
   if (!d_ctrl && step < 1) IGMC_FAIL("step must be >= 1");
-  float step_size = 0.f, inv = 0.f;
-  if (!d_ctrl) {
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-    step_size = (float)((double)lr / bc1);
-    inv = (float)(1.0 / std::sqrt(bc2));
-  }
+  const AdamScalars as = adam_scalars(d_ctrl, step, lr, beta1, beta2);
   ModelDev md = sp->m->d;
   md.n_params = sp->d.n_params;          // Adam runs over the sort-pool family's own flat buffer
-  igmc_launch_finish(md, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, step_size, inv, beta1, beta2, eps, weight_decay,
-                     d_ctrl, ARR, d_loss, d_total, sp->m->last_flags, stream);
+  igmc_launch_finish(md, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, as.step_size, as.inv_sqrt_bc2, beta1, beta2, eps,
+                     weight_decay, d_ctrl, ARR, d_loss, d_total, sp->m->last_flags, stream);
   HIPCHECK(hipGetLastError());
   return 0;
 }

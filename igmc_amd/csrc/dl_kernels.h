@@ -1837,54 +1837,13 @@ void igmc_launch_dl_layer0(const ModelDev& m, const BatchDev& b, int B, int trai
   a.cnt0 = training ? m.cnt0 : nullptr;
   const int grid = B * (a.nqu + a.nqv);
   const size_t sm = dl0_lds(a.kp);
-  if (training) {
-    if (use_flags) IGMC_PLAUNCH("k_dl_layer0", (k_dl_layer0<true, true>), grid, DL_THREADS, sm, stream, a);
-    else IGMC_PLAUNCH("k_dl_layer0", (k_dl_layer0<false, true>), grid, DL_THREADS, sm, stream, a);
-  } else {
-    if (use_flags) IGMC_PLAUNCH("k_dl_layer0", (k_dl_layer0<true, false>), grid, DL_THREADS, sm, stream, a);
-    else IGMC_PLAUNCH("k_dl_layer0", (k_dl_layer0<false, false>), grid, DL_THREADS, sm, stream, a);
-  }
+  igmc_dispatch([&](auto uf, auto tr) {
+    IGMC_PLAUNCH("k_dl_layer0", (k_dl_layer0<uf(), tr()>), grid, DL_THREADS, sm, stream, a);
+  }, use_flags != 0, training != 0);
 }
 
 static size_t dl_lds(int kp, bool ts = false) {
   return ((size_t)dl_words_front(ts) + (size_t)dl_words_mid(kp, ts) + DL_NW * 32 + 32) * 4;
-}
-
-// 1 = the dense per-layer kernels take the conv layers of this arena (IGMC_DL=0 switches them off)
-static int dl_base_ok(const ModelDev& m, const BatchDev& b, int B, int wide) {
-  const char* e = getenv("IGMC_DL");
-  if (e && atoi(e) == 0) return 0;
-  if (!b.relm || !b.relmT || !m.g2_w || m.L > 8) return 0;
-  const int rows0 = m.R * m.L + m.L + 1;
-  // wide: the two-group layout -- six to ten relations, or a layer-0 table of 33..48 rows (two hops)
-  if (wide ? (g2_groups(m.R, m.L) == 1 || m.R > G2_NR * G2_NG_MAX || rows0 > 48) : (m.R > G2_NR || rows0 > 32)) return 0;
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
-  const DlSplit sq = dl_split(b.cap_u, b.cap_v, B);
-  return cmax <= 256 && B * (sq.nqu + sq.nqv) <= IGMC_GATHER_BLOCKS;
-}
-int igmc_dl_eligible(const ModelDev& m, const BatchDev& b, int B) {
-  if (!dl_base_ok(m, b, B, 0)) return 0;
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
-  return dl_lds(32 * ((cmax + 31) >> 5) + 8) <= (size_t)160 * 1024;
-}
-
-// 1 = the backward passes of this arena can leave relation-space tables (k_dl_layer<*, true, true>): the tail of the
-// subgraph kernel (k_tail_ts -> k_finalize_ts) then replaces G / Y / the weight-gradient products (IGMC_DL_TS=0: never)
-int igmc_dl_ts_eligible(const ModelDev& m, const BatchDev& b, int B) {
-  const char* e = getenv("IGMC_DL_TS");
-  if (e && atoi(e) == 0) return 0;
-  if (!igmc_dl_eligible(m, b, B) || !m.ts_part || !m.cnt0) return 0;
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
-  const DlSplit sq = dl_split(b.cap_u, b.cap_v, B);
-  const int stride = (B + 7) & ~7;
-  if ((sq.nqu + sq.nqv) * stride > IGMC_TS_BLOCKS || m.R * m.L > 20) return 0;
-  return dl_lds(32 * ((cmax + 31) >> 5) + 8, true) <= (size_t)160 * 1024;
-}
-
-int igmc_dl_grid(const BatchDev& b, int B) {
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
-  const DlSplit sq = dl_split(b.cap_u, b.cap_v, B);
-  return B * (sq.nqu + sq.nqv);
 }
 
 void igmc_launch_g2_compose(const ModelDev& m, const float* P, void* stream) {
@@ -1914,54 +1873,21 @@ void igmc_launch_dl_layer(const ModelDev& m, const BatchDev& b, const float* P, 
   a.bias = P + m.off_bias[l]; a.att = P + m.off_att[l];
   a.L = m.L;
   const int grid = B * (a.nqu + a.nqv);
-  if (bwd && tables) {       // relation-space tables instead of G / d att partials (igmc_dl_ts_eligible)
+  if (bwd && tables) {       // relation-space tables instead of G / d att partials
     a.ts_part = m.ts_part; a.ts_stride = m.ts_stride; a.slot_stride = (B + 7) & ~7;
     a.cnt0 = m.cnt0; a.node_label = b.node_label;
     a.gagg = nullptr; a.Y = nullptr; a.gatt_part = nullptr;
-    const size_t smt = dl_lds(a.kp, true);
-    if (use_flags) IGMC_PLAUNCH("k_dl_layer_bwd", (k_dl_layer<true, true, true>), grid, DL_THREADS, smt, stream, a);
-    else IGMC_PLAUNCH("k_dl_layer_bwd", (k_dl_layer<false, true, true>), grid, DL_THREADS, smt, stream, a);
-    return;
   }
-  const size_t sm = dl_lds(a.kp);
-  if (bwd) {
-    if (use_flags) IGMC_PLAUNCH("k_dl_layer_bwd", (k_dl_layer<true, true, false>), grid, DL_THREADS, sm, stream, a);
-    else IGMC_PLAUNCH("k_dl_layer_bwd", (k_dl_layer<false, true, false>), grid, DL_THREADS, sm, stream, a);
-  } else {
-    if (use_flags) IGMC_PLAUNCH("k_dl_layer_fwd", (k_dl_layer<true, false, false>), grid, DL_THREADS, sm, stream, a);
-    else IGMC_PLAUNCH("k_dl_layer_fwd", (k_dl_layer<false, false, false>), grid, DL_THREADS, sm, stream, a);
-  }
+  const size_t sm = dl_lds(a.kp, bwd && tables);
+  igmc_dispatch([&](auto uf) {
+    if (bwd && tables) IGMC_PLAUNCH("k_dl_layer_bwd", (k_dl_layer<uf(), true, true>), grid, DL_THREADS, sm, stream, a);
+    else if (bwd) IGMC_PLAUNCH("k_dl_layer_bwd", (k_dl_layer<uf(), true, false>), grid, DL_THREADS, sm, stream, a);
+    else IGMC_PLAUNCH("k_dl_layer_fwd", (k_dl_layer<uf(), false, false>), grid, DL_THREADS, sm, stream, a);
+  }, use_flags != 0);
 }
 
-// 1 = the forward of this arena's dense layers runs as ONE launch (k_dl_fwd): exchange regions for 256 nodes a side, every
-// workgroup of the launch resident at once (IGMC_DL_FUSED=0: the per-layer launches)
-int igmc_dl_fwd_eligible(const ModelDev& m, const BatchDev& b, int B) {
-  if (!igmc_g2_xcd_ok()) return 0;      // (the members' exchange goes through the L2 of one XCD)
-  const char* e = getenv("IGMC_DL_FUSED");
-  if (e && atoi(e) == 0) return 0;
-  if (!igmc_dl_eligible(m, b, B) || !m.g2_ex || m.ex_nodes < DLX_K || b.graph_cap > m.g2_graphs) return 0;
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
-  const DlSplit sq = dl_split(b.cap_u, b.cap_v, B);
-  if (B * (sq.nqu + sq.nqv) > 224) return 0;                  // (one workgroup per CU, all of them resident: the members wait for each other)
-  return (size_t)dlf_words(32 * ((cmax + 31) >> 5) + 8) * 4 <= (size_t)160 * 1024;
-}
-
-// 1 = the group-split forms of k_dl_fwd / k_dl_bwd take this arena: two relation groups, no workgroup with more than DL_NW / 2
-// bundles (dl_split / dl_rows over the slot capacities), both images beside the planes in LDS.  IGMC_DL_GSPLIT=0: the
-// group-after-group form (test hook).
-static int dl_gsplit(const ModelDev& m, const BatchDev& b, int B) {
-  if (g2_groups(m.R, m.L) != 2 || g2_rel_groups(m.R) != 2) return 0;
-  const char* e = getenv("IGMC_DL_GSPLIT");
-  if (e && atoi(e) == 0) return 0;
-  const DlSplit sq = dl_split(b.cap_u, b.cap_v, B);
-  const int nbu = (b.cap_u + 15) >> 4, nbv = (b.cap_v + 15) >> 4;
-  if ((nbu + sq.nqu - 1) / sq.nqu > DL_GB || (nbv + sq.nqv - 1) / sq.nqv > DL_GB) return 0;
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v, kp = 32 * ((cmax + 31) >> 5) + 8;
-  return (size_t)dlf_words_gs(kp) * 4 <= 160 * 1024 && (size_t)dlb_words_gs(kp) * 4 <= 160 * 1024;
-}
-
-void igmc_launch_dl_fwd(const ModelDev& m, const BatchDev& b, const float* P, int B, int training, int use_flags,
-                        float* zero_out, int self_seq, void* stream) {
+void igmc_launch_dl_fwd(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
+                        int use_flags, float* zero_out, void* stream) {
   DlfArgs a;
   memset(&a, 0, sizeof(a));
   const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
@@ -1979,87 +1905,27 @@ void igmc_launch_dl_fwd(const ModelDev& m, const BatchDev& b, const float* P, in
   a.g2_w = m.g2_w; a.P = P;
   a.ex = m.g2_ex; a.ex_stride = m.g2_ex_stride;
   a.gs_bar = m.gs_bar; a.gs_err = m.gs_err;
-  a.self_seq = self_seq;
+  a.self_seq = sp.self_seq;
   a.timing = getenv("IGMC_DL_TIMING") ? atoi(getenv("IGMC_DL_TIMING")) : 0;
   a.B = B;
   const int grid = 8 * ((B + 7) / 8) * (a.nqu + a.nqv);      // (XCD-aligned blocks of 8 * members workgroups: DLX_DECODE)
   const int ng = g2_groups(m.R, m.L);
-  const int gs = dl_gsplit(m, b, B);
+  const int gs = sp.gsplit;
   const size_t sm = (size_t)(gs ? dlf_words_gs(a.kp) : dlf_words(a.kp, ng)) * 4;
 #ifdef IGMC_HIPEMU
   hipemu::rt().co_cs = a.nqu + a.nqv;                   // the members of a subgraph run together:
   hipemu::rt().co_stride = 8;                           // workgroups 8 nmem j + x + 8 rem
   hipemu::rt().co_block = 8 * (a.nqu + a.nqv);
 #endif
-  if (ng == 1) {
-    if (training) {
-      if (use_flags) IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<true, true, 1>), grid, DL_THREADS, sm, stream, a);
-      else IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<false, true, 1>), grid, DL_THREADS, sm, stream, a);
-    } else {
-      if (use_flags) IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<true, false, 1>), grid, DL_THREADS, sm, stream, a);
-      else IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<false, false, 1>), grid, DL_THREADS, sm, stream, a);
-    }
-  } else if (gs) {
-    if (training) {
-      if (use_flags) IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<true, true, 2, true>), grid, DL_THREADS, sm, stream, a);
-      else IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<false, true, 2, true>), grid, DL_THREADS, sm, stream, a);
-    } else {
-      if (use_flags) IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<true, false, 2, true>), grid, DL_THREADS, sm, stream, a);
-      else IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<false, false, 2, true>), grid, DL_THREADS, sm, stream, a);
-    }
-  } else {
-    if (training) {
-      if (use_flags) IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<true, true, 2>), grid, DL_THREADS, sm, stream, a);
-      else IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<false, true, 2>), grid, DL_THREADS, sm, stream, a);
-    } else {
-      if (use_flags) IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<true, false, 2>), grid, DL_THREADS, sm, stream, a);
-      else IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<false, false, 2>), grid, DL_THREADS, sm, stream, a);
-    }
-  }
+  igmc_dispatch([&](auto uf, auto tr) {
+    if (ng == 1) IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<uf(), tr(), 1>), grid, DL_THREADS, sm, stream, a);
+    else if (gs) IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<uf(), tr(), 2, true>), grid, DL_THREADS, sm, stream, a);
+    else IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<uf(), tr(), 2>), grid, DL_THREADS, sm, stream, a);
+  }, use_flags != 0, training != 0);
 }
 
-// (k_dl_bwd: same conditions as k_dl_fwd -- whose launch precedes it and maintains the exchange regions -- plus the tables')
-// 1 = more than G2_NR relations (<= G2_NR * G2_NG_MAX, layer-0 table <= 48 rows) on the one-launch dense kernels, which take the
-// relations in groups: k_dl_fwd / k_head_sub / k_dl_bwd<*, NG> with the relation-space tables behind them -- all of it or
-// nothing (the per-layer kernels k_dl_layer0 / k_dl_layer stop at G2_NR relations)
-// 1 = ... and in the group-split form (dl_gsplit): both relation groups at once on the halves of a workgroup
-int igmc_dl_wide_gsplit(const ModelDev& m, const BatchDev& b, int B) { return igmc_dl_wide(m, b, B) && dl_gsplit(m, b, B); }
-void igmc_dl_split(int cap_u, int cap_v, int B, int* nqu, int* nqv) {
-  const DlSplit sq = dl_split(cap_u, cap_v, B);
-  *nqu = sq.nqu;
-  *nqv = sq.nqv;
-}
-
-int igmc_dl_wide(const ModelDev& m, const BatchDev& b, int B) {
-  if (!igmc_g2_xcd_ok()) return 0;      // (the members' exchange goes through the L2 of one XCD)
-  if (!dl_base_ok(m, b, B, 1)) return 0;
-  const char* e = getenv("IGMC_DL_FUSED");
-  if (e && atoi(e) != 2) return 0;
-  const char* et = getenv("IGMC_DL_TS");
-  if (et && atoi(et) == 0) return 0;
-  // (the same predicate as the launch sequence's `fts_pre`, model.hip: with the tables' tail switched off -- IGMC_FIN_MODE=0 --
-  //  or its stash missing the step does NOT go wide, and the arena must then carry the CSR the row walkers read)
-  const char* ef = getenv("IGMC_FIN_MODE");
-  if ((ef && atoi(ef) == 0) || !m.fin_stash || !m.datt_part) return 0;
-  if (!m.g2_ex || m.ex_nodes < DLX_K || b.graph_cap > m.g2_graphs || !m.ts_part || !m.cnt0) return 0;
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
-  const DlSplit sq = dl_split(b.cap_u, b.cap_v, B);
-  const int stride = (B + 7) & ~7, kp = 32 * ((cmax + 31) >> 5) + 8;
-  if (B * (sq.nqu + sq.nqv) > 224 || (sq.nqu + sq.nqv) * stride > IGMC_TS_BLOCKS) return 0;
-  const int ng = g2_groups(m.R, m.L);
-  return (size_t)dlf_words(kp, ng) * 4 <= (size_t)160 * 1024 && (size_t)dlb_words(kp, ng) * 4 <= (size_t)160 * 1024;
-}
-
-int igmc_dl_bwd_eligible(const ModelDev& m, const BatchDev& b, int B) {
-  if (!igmc_g2_xcd_ok()) return 0;      // (the members' exchange goes through the L2 of one XCD)
-  if (!igmc_dl_fwd_eligible(m, b, B) || !igmc_dl_ts_eligible(m, b, B)) return 0;
-  const char* e = getenv("IGMC_DL_FUSED");
-  if (e && atoi(e) == 1) return 0;                 // (1: the forward only)
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
-  return (size_t)dlb_words(32 * ((cmax + 31) >> 5) + 8) * 4 <= (size_t)160 * 1024;
-}
-
-void igmc_launch_dl_bwd(const ModelDev& m, const BatchDev& b, int B, int use_flags, void* stream, const DlHead* head, int dense3) {
+void igmc_launch_dl_bwd(const ModelDev& m, const BatchDev& b, const StepPlan& sp, int B, int use_flags, void* stream,
+                        const DlHead* head, int dense3) {
   DlbArgs a;
   memset(&a, 0, sizeof(a));
   const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
@@ -2084,28 +1950,20 @@ void igmc_launch_dl_bwd(const ModelDev& m, const BatchDev& b, int B, int use_fla
   }
   a.B = B;
   const int grid = 8 * ((B + 7) / 8) * (a.nqu + a.nqv);      // (XCD-aligned blocks of 8 * members workgroups: DLX_DECODE)
-  const int gs = !dense3 && dl_gsplit(m, b, B);
+  const int gs = !dense3 && sp.gsplit;
   const size_t sm = (size_t)(gs ? dlb_words_gs(a.kp) : dlb_words(a.kp, g2_groups(m.R, m.L))) * 4;
 #ifdef IGMC_HIPEMU
   hipemu::rt().co_cs = a.nqu + a.nqv;
   hipemu::rt().co_stride = 8;
   hipemu::rt().co_block = 8 * (a.nqu + a.nqv);
 #endif
-  if (g2_groups(m.R, m.L) == 1) {
-    if (dense3) {
-      if (use_flags) IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<true, 1, true>), grid, DL_THREADS, sm, stream, a);
-      else IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<false, 1, true>), grid, DL_THREADS, sm, stream, a);
-    } else {
-      if (use_flags) IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<true, 1, false>), grid, DL_THREADS, sm, stream, a);
-      else IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<false, 1, false>), grid, DL_THREADS, sm, stream, a);
-    }
-  } else if (gs) {
-    if (use_flags) IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<true, 2, false, true>), grid, DL_THREADS, sm, stream, a);
-    else IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<false, 2, false, true>), grid, DL_THREADS, sm, stream, a);
-  } else {        // (relation groups: centre-node readout only -- igmc_conv_bwd_tables asks for the one-group layout)
-    if (use_flags) IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<true, 2, false>), grid, DL_THREADS, sm, stream, a);
-    else IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<false, 2, false>), grid, DL_THREADS, sm, stream, a);
-  }
+  const int ng = g2_groups(m.R, m.L);
+  igmc_dispatch([&](auto uf) {      // (relation groups: centre-node readout only -- a dense3 plan asks for the one-group layout)
+    if (ng == 1 && dense3) IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<uf(), 1, true>), grid, DL_THREADS, sm, stream, a);
+    else if (ng == 1) IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<uf(), 1, false>), grid, DL_THREADS, sm, stream, a);
+    else if (gs) IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<uf(), 2, false, true>), grid, DL_THREADS, sm, stream, a);
+    else IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<uf(), 2, false>), grid, DL_THREADS, sm, stream, a);
+  }, use_flags != 0);
 }
 
 int igmc_dl_prepare() {

@@ -90,43 +90,8 @@ __global__ __launch_bounds__(G2C_THREADS) void k_g2_compose(ModelDev m, const fl
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-// workgroups per subgraph: 4 (2) when 4 (2) x the padded batch still fits one workgroup per CU with a margin
-int igmc_gs_cluster(int B) {
-#ifdef IGMC_HIPEMU
-  // the emulator runs workgroups one after the other unless a test asks for clusters (their members then run
-  // together: hipemu::Runtime::co_cs)
-  const char* ee = getenv("IGMC_GS_CLUSTER");
-  const int want_e = ee ? atoi(ee) : 1;
-  const int stride_e = (B + 7) & ~7;
-  if (want_e >= 4 && 4 * stride_e <= 224) return 4;
-  if (want_e >= 2 && 2 * stride_e <= 224) return 2;
-  return 1;
-#else
-  static int cus = -1;
-  if (cus < 0) {
-    hipDeviceProp_t prop;
-    int dev = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 0;
-  }
-  int want = (cus >= 240) ? 4 : 1;        // the clustered launch needs (almost) every CU of an MI355X to itself
-  const char* e = getenv("IGMC_GS_CLUSTER");
-  if (e) want = atoi(e);
-  const int stride = (B + 7) & ~7;
-  if (want >= 4 && 4 * stride <= 224) return 4;
-  if (want >= 2 && 2 * stride <= 224) return 2;
-  return 1;
-#endif
-}
-
-int igmc_gs_grid(int B) {
-  int cap = IGMC_WG_BLOCKS;
-  const char* e = getenv("IGMC_GS_GRID");      // test hook: fewer workgroups than graphs (accumulating partials)
-  if (e && atoi(e) > 0 && atoi(e) < cap) cap = atoi(e);
-  return B < cap ? B : cap;
-}
-
 // LDS plan + eligibility for a batch arena / cluster size
-int igmc_g2_layout(const ModelDev& m, const BatchDev& b, int cs, G2Layout* lay) {
+static int igmc_g2_layout(const ModelDev& m, const BatchDev& b, int cs, G2Layout* lay) {
   const int RL = m.R * m.L;
   if (m.S != 0 || m.D != 256 || m.R > G2_NR || m.L > 8 || RL + m.L + 1 > 32 || !m.ts_part || !m.g2_px || !m.g2_fx || !m.g2_w || !b.relm) return 0;
   const int half = 2 * cs;
@@ -199,23 +164,14 @@ int igmc_g2_xcd_ok() {
 #endif
 }
 
-// 1 = the matrix-core subgraph kernel takes this batch configuration (IGMC_GRAPH_STEP=0 forces the per-layer kernels)
-int igmc_g2_eligible(const ModelDev& m, const BatchDev& b, int B, G2Layout* lay, int* cs_out) {
-  const char* en = getenv("IGMC_GRAPH_STEP");      // read on every call: tests switch it per case
-  if (en && atoi(en) == 0) return 0;
-  if (!igmc_g2_xcd_ok()) return 0;
-  const int cs = igmc_gs_cluster(B);
-  if (!igmc_g2_layout(m, b, cs, lay)) return 0;
-  *cs_out = cs;
-  return 1;
-}
-
 // returns 1 when the launch leaves the advance of the launch sequence number to the caller's next kernel (k_tail_ts)
 int g_igmc_compose_count = 0;      // launches of k_g2_compose so far (capi.hip: did a call refresh the weight images)
 
-int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const float* P, int B, int training, int use_flags,
-                            const G2Layout& lay, int cs, const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult,
-                            float grad_scale, float* out, void* stream) {
+int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
+                            int use_flags, const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float grad_scale,
+                            float* out, void* stream) {
+  const G2Layout& lay = sp.lay;
+  const int cs = sp.cs;
   G2Args a;
   memset(&a, 0, sizeof(a));
   a.n_users = b.n_users; a.n_items = b.n_items; a.B = B; a.s_lab = b.s_lab; a.relm = b.relm; a.y = b.y;
@@ -243,7 +199,7 @@ int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const float* P
   a.self_seq = (!training || a.ts) ? 1 : 0;
   a.cs = cs;
   a.stride = (cs > 1) ? ((B + 7) & ~7) : 1;
-  const int grid = (cs > 1) ? cs * 8 * ((B + 7) / 8) : igmc_gs_grid(B);      // (clusters in XCD-aligned blocks of 8 cs workgroups)
+  const int grid = sp.grid;      // (clusters in XCD-aligned blocks of 8 cs workgroups)
   const size_t sm = (size_t)lay.words * 4;
   if (!m.img_current) {
     IGMC_PLAUNCH("k_g2_compose", k_g2_compose, 2 * 3 * g2_groups(m.R, m.L) * (G2_NR + 1) + g2_t0_rows(m.R, m.L) / 32, G2C_THREADS, 0, stream, m, P, m.g2_w);
@@ -257,21 +213,10 @@ int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const float* P
   }
 #endif
   if (getenv("IGMC_GS_TRACE")) fprintf(stderr, "[igmc] k_graph_step B=%d train=%d flags=%d v2 kp=%d lds=%zu cluster=%d grid=%d\n", B, training, use_flags, lay.kp, sm, cs, grid);
-  if (cs > 1) {        // one subgraph per workgroup: the straight-line variants
-    if (training) {
-      if (use_flags) IGMC_PLAUNCH("k_graph_step", (k_graph_step2<true, true, true>), grid, G2_THREADS, sm, stream, a);
-      else IGMC_PLAUNCH("k_graph_step", (k_graph_step2<false, true, true>), grid, G2_THREADS, sm, stream, a);
-    } else {
-      if (use_flags) IGMC_PLAUNCH("k_graph_fwd", (k_graph_step2<true, false, true>), grid, G2_THREADS, sm, stream, a);
-      else IGMC_PLAUNCH("k_graph_fwd", (k_graph_step2<false, false, true>), grid, G2_THREADS, sm, stream, a);
-    }
-  } else if (training) {
-    if (use_flags) IGMC_PLAUNCH("k_graph_step", (k_graph_step2<true, true, false>), grid, G2_THREADS, sm, stream, a);
-    else IGMC_PLAUNCH("k_graph_step", (k_graph_step2<false, true, false>), grid, G2_THREADS, sm, stream, a);
-  } else {
-    if (use_flags) IGMC_PLAUNCH("k_graph_fwd", (k_graph_step2<true, false, false>), grid, G2_THREADS, sm, stream, a);
-    else IGMC_PLAUNCH("k_graph_fwd", (k_graph_step2<false, false, false>), grid, G2_THREADS, sm, stream, a);
-  }
+  // (cs > 1: one subgraph per workgroup -- the straight-line variants)
+  igmc_dispatch([&](auto uf, auto tr, auto cl) {
+    IGMC_PLAUNCH(tr() ? "k_graph_step" : "k_graph_fwd", (k_graph_step2<uf(), tr(), cl()>), grid, G2_THREADS, sm, stream, a);
+  }, use_flags != 0, training != 0, cs > 1);
   return a.self_seq ? 0 : 1;
 }
 

@@ -30,9 +30,10 @@
 // on the two target rows only and is rebuilt locally from the head's d feat: 5 exchanges per launch (h_0, h_1, h_2, dPre_2,
 // dPre_1) + the 256-float centre-node readout (8-byte {f32, tag} words, polled).
 //
-// This translation unit in four files (round 6): graphstep2.hip (this one: the shared gather / transform steps),
-// g2_subgraph.h (k_graph_step2), g2_compose.h (k_g2_compose, layout, eligibility and launch of the subgraph kernel),
-// dl_kernels.h (the dense-layer kernels k_dl_* for slots of up to 256 nodes a side and up to ten relations).
+// This translation unit in five files: graphstep2.hip (this one: the shared gather / transform steps),
+// g2_subgraph.h (k_graph_step2), g2_compose.h (k_g2_compose, layout and launch of the subgraph kernel),
+// dl_kernels.h (the dense-layer kernels k_dl_* for slots of up to 256 nodes a side and up to ten relations),
+// step_plan.h (hooks, eligibility and the StepPlan every launch sequence reads).
 //
 // Eligibility (else the per-layer kernels run): dense block present, R <= 5, layer-0 table <= 32 rows,
 // no side features, both sides <= 16 * (2 * cluster size) <= 128 rows.
@@ -228,3 +229,4 @@ __device__ __forceinline__ void g2_transform(const f32x4 (&acc)[G2_NR][2], const
 #include "g2_subgraph.h"
 #include "g2_compose.h"
 #include "dl_kernels.h"
+#include "step_plan.h"

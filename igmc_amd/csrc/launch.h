@@ -2,6 +2,7 @@
 #pragma once
 #include "model.h"
 #include <string.h>
+#include <type_traits>
 
 // extract.hip
 size_t igmc_extract_smem_bytes(const GraphDev& g);
@@ -30,21 +31,21 @@ void igmc_launch_fill_u8(uint8_t* p, int64_t n, uint8_t v, void* stream);
 int igmc_extract_prepare(size_t smem);
 
 // model.hip
-// auxiliary streams / events of a model: independent kernels of the step run as parallel branches (also when
-// the step is being captured into a hipGraph: event waits become graph edges)
+// auxiliary streams / events of a model (created with it; no launch sequence uses them at present: see the note at k_wgrad)
 struct ModelAux {
-  void* s1;      // Y products (needed only by the backward gathers)
-  void* s2;      // weight-gradient products + lin1 weight gradient
+  void* s1;
+  void* s2;
   void* ev[8];
 };
-void igmc_launch_forward(const ModelDev& m, const ModelAux& ax, const BatchDev& b, const float* P, int B, int training,
+struct StepPlan;      // what a call launches: below (step_plan.h builds it, the launch sequences read it)
+void igmc_launch_forward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
                          int use_flags, const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult,
                          float* out, void* stream);
-void igmc_launch_conv_forward(const ModelDev& m, const BatchDev& b, const float* P, int B, int training, int use_flags,
-                              void* stream);
-void igmc_launch_conv_backward(const ModelDev& m, const BatchDev& b, const float* P, int B, int use_flags, float arr_coef,
-                               float* grad, void* stream);
-void igmc_launch_backward(const ModelDev& m, const ModelAux& ax, const BatchDev& b, const float* P, int B, int use_flags,
+void igmc_launch_conv_forward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
+                              int use_flags, void* stream);
+void igmc_launch_conv_backward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int use_flags,
+                               float arr_coef, float* grad, void* stream);
+void igmc_launch_backward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int use_flags,
                           const float* gout, int from_err, float grad_scale, float mult, float drop_scale,
                           float arr_coef, float* grad, void* stream);
 struct AdamTail;
@@ -58,16 +59,14 @@ struct StepExchange {
   const int* failed;      // device word the exchange raises when its sums are NOT in place (a peer never delivered): the
                           // gradient / Adam kernel behind it then leaves parameters, moments and step counters alone; or null
 };
-// 1 = a step on this arena keeps its gradient sources in exchangeable form (igmc_launch_loss_grad honours `xch`)
-int igmc_step_exchange_inside(const ModelDev& m, const BatchDev& b, int B);
 // returns 0, or the exchange's error code
-int igmc_launch_loss_grad(const ModelDev& m, const ModelAux& ax, const BatchDev& b, float* P, int B, int use_flags,
+int igmc_launch_loss_grad(const ModelDev& m, const BatchDev& b, const StepPlan& sp, float* P, int B, int use_flags,
                           const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float ARR,
                           float grad_scale, float arr_scale, float* out, float* grad, float* loss, const AdamTail* adam,
                           void* stream, const StepExchange* xch = nullptr, int* img_emitted = nullptr);
-// (grad_scale 0: 1 / B; xch: see StepExchange -- only where igmc_step_exchange_inside() says so; *img_emitted = 1 when the
-//  step's last kernel also left the weight images of the updated parameters in m.g2_w)
-int igmc_launch_train_step(const ModelDev& m, const ModelAux& ax, const BatchDev& b, float* P, int B, int use_flags,
+// (sp: a plan of kind IGMC_CALL_STEP; grad_scale 0: 1 / B; xch: see StepExchange -- only where sp.exchange_inside says so;
+//  *img_emitted = 1 when the step's last kernel also left the weight images of the updated parameters in m.g2_w)
+int igmc_launch_train_step(const ModelDev& m, const BatchDev& b, const StepPlan& sp, float* P, int B, int use_flags,
                            const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float ARR, float* out,
                            float* grad, float* m1, float* m2, float step_size, float inv_sqrt_bc2, float beta1,
                            float beta2, float eps, float wd, int64_t* ctrl, int* done, float* loss, double* total,
@@ -110,37 +109,46 @@ struct G2Layout {      // LDS plan of graphstep2.hip, offsets in 4-byte words
 };
 void igmc_launch_side_gather(const float* src, int S, const int32_t* link_idx, int first, int B, const int64_t* ctrl,
                              float* dst, void* stream);
-int igmc_gs_grid(int B);
-int igmc_gs_cluster(int B);
 int igmc_gs_prepare();
-int igmc_g2_eligible(const ModelDev& m, const BatchDev& b, int B, G2Layout* lay, int* cs_out);
-// dense per-layer kernels (graphstep2.hip): slots of 129..256 nodes a side with a dense block + its transposed copy
-int igmc_dl_eligible(const ModelDev& m, const BatchDev& b, int B);
-int igmc_dl_grid(const BatchDev& b, int B);
-void igmc_launch_g2_compose(const ModelDev& m, const float* P, void* stream);
-void igmc_launch_dl_layer0(const ModelDev& m, const BatchDev& b, int B, int training, int use_flags, void* stream);
-int igmc_dl_ts_eligible(const ModelDev& m, const BatchDev& b, int B);
-int igmc_dl_fwd_eligible(const ModelDev& m, const BatchDev& b, int B);
-int igmc_dl_bwd_eligible(const ModelDev& m, const BatchDev& b, int B);
-int igmc_dl_wide(const ModelDev& m, const BatchDev& b, int B);
-int igmc_dl_wide_gsplit(const ModelDev& m, const BatchDev& b, int B);
-void igmc_dl_split(int cap_u, int cap_v, int B, int* nqu, int* nqv);      // workgroups of a subgraph's two sides (dl_split)
+int igmc_g2_prepare();
 
-// What a training step on (arena, B) launches: the one decision igmc_launch_loss_grad takes its branches from, and what
-// igmc_model_step_geometry reports (model.hip)
+// What a call on (model, arena, B) launches (step_plan.h): THE decision.  Every launch sequence of model.hip takes its
+// branches from a plan and every query of the C ABI reports one; the eligibility predicates and the environment hooks
+// behind it are private to step_plan.h.
+#define IGMC_CALL_EVAL 0     // evaluation forward: the subgraph kernel whatever the head's width, no backward
+#define IGMC_CALL_CONV 1     // training forward, then backward, as calls of their own: the generic sequence and the sort-pool family
+#define IGMC_CALL_STEP 2     // the fused step (loss + gradients [+ Adam]): needs fast_head, else the generic sequence
 #define IGMC_FAM_ROWS 0      // the CSR row walkers (k_l0_fwd / k_rgcn_layer4)
 #define IGMC_FAM_G2 1        // the subgraph kernel (k_graph_step)
 #define IGMC_FAM_DLF 2       // the one-launch dense layers (k_dl_fwd)
 #define IGMC_FAM_DL 3        // the per-layer dense layers (k_dl_layer0 / k_dl_layer)
+#define IGMC_TAIL_HANDOFF 0  // gradient / Adam tail: k_finalize (in-kernel hand-offs)
+#define IGMC_TAIL_TS 1       // ... k_tail_ts -> k_finalize_ts on relation-space tables
+#define IGMC_TAIL_BS 2       // ... k_finalize_ts on the reduced basis-space sums
 struct StepPlan {
+  int kind;                  // IGMC_CALL_*
   int fast_head;             // 0: the generic sequence (igmc_launch_forward + igmc_launch_backward)
-  int family;                // IGMC_FAM_*
+  int family;                // IGMC_FAM_* of the forward
   int cs, grid;              // subgraph kernel: workgroups per subgraph, grid
   G2Layout lay;              // ... its LDS plan
   int wide, dl, dlts, dlf, dlb;      // dense layers: relation groups, per-layer / one-launch eligible, relation-space tables,
                                      // one-launch forward, one-launch backward
+  int nqu, nqv, dl_grid;     // ... workgroups of a subgraph's two sides (0 where no dense-layer kernel runs), B * (nqu + nqv)
+  int gsplit;                // ... k_dl_fwd / k_dl_bwd in the group-split form
+  int self_seq;              // ... k_dl_fwd's last workgroup advances the exchange tags itself (else: k_tail_ts behind it)
+  int head_inside;           // ... the loss head runs in k_dl_bwd's set-up (IGMC_DL_HEAD=0: k_head_sub in front of it)
+  int bwd_dense;             // the per-layer backward passes: k_dl_layer (else the row walkers)
+  int need_y;                // the forward leaves the Y products behind (k_dense_y_all)
+  int tail;                  // IGMC_TAIL_*
+  int exchange_inside;       // the step keeps its gradient sources in exchangeable form (StepExchange)
+  int needs_csr;             // some kernel of the call reads the collated CSR (a lean arena must emit it first)
+  int dense_layers;          // the dense-layer kernels take this arena (igmc_model_dense_layers)
+  int step_form;             // igmc_model_step_form
 };
-void igmc_step_plan(const ModelDev& m, const BatchDev& b, int B, StepPlan* p);
+void igmc_step_plan(const ModelDev& m, const BatchDev& b, int B, int kind, StepPlan* p);
+int igmc_dl_always();        // IGMC_DL_ALWAYS=1 (test hook): arenas with small slots get the transposed block as well
+void igmc_launch_g2_compose(const ModelDev& m, const float* P, void* stream);
+void igmc_launch_dl_layer0(const ModelDev& m, const BatchDev& b, int B, int training, int use_flags, void* stream);
 // (head != NULL: the launch runs the subgraphs' loss head itself -- no k_head_sub launch in front of it)
 struct DlHead {
   const float* P;
@@ -150,18 +158,17 @@ struct DlHead {
   float* out;
 };
 // (dense3: the sort-pool family's backward -- dPre_3 of every row from m.dpre[3], the readout gradient of layers 0..2 from m.dcat)
-void igmc_launch_dl_bwd(const ModelDev& m, const BatchDev& b, int B, int use_flags, void* stream, const DlHead* head = nullptr,
-                        int dense3 = 0);
-void igmc_launch_dl_fwd(const ModelDev& m, const BatchDev& b, const float* P, int B, int training, int use_flags,
-                        float* zero_out, int self_seq, void* stream);
+void igmc_launch_dl_bwd(const ModelDev& m, const BatchDev& b, const StepPlan& sp, int B, int use_flags, void* stream,
+                        const DlHead* head = nullptr, int dense3 = 0);
+void igmc_launch_dl_fwd(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
+                        int use_flags, float* zero_out, void* stream);
 void igmc_launch_head_sub(const ModelDev& m, const BatchDev& b, const float* P, int B, const uint8_t* inj_mask, uint64_t seed,
                           uint64_t step, float mult, float grad_scale, float* out, void* stream);
 void igmc_launch_dl_layer(const ModelDev& m, const BatchDev& b, const float* P, int B, int l, int bwd, int use_flags,
                           float* zero_out, void* stream, int tables = 0);
-int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const float* P, int B, int training, int use_flags,
-                             const G2Layout& lay, int cs, const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult,
-                             float grad_scale, float* out, void* stream);
-int igmc_g2_prepare();
+int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
+                            int use_flags, const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float grad_scale,
+                            float* out, void* stream);
 
 // ---- per-kernel timing (HIP events on the launch stream; bench.py's roofline leg) ----
 void igmc_prof_begin(const char* name, void* stream);
@@ -174,3 +181,13 @@ extern int g_igmc_prof_on;
     IGMC_LAUNCH(kern, grid, block, shmem, stream, __VA_ARGS__);            \
     if (g_igmc_prof_on == 1) igmc_prof_end(stream);                        \
   } while (0)
+
+// Runtime flags -> template arguments: igmc_dispatch([&](auto uf, auto tr) { ... k<uf(), tr()> ... }, use_flags, training) calls
+// the generic lambda with one std::bool_constant per flag, so a kernel templated on bools has ONE launch site per variant.
+template <typename F>
+static inline void igmc_dispatch(F&& f) { f(); }
+template <typename F, typename... Rest>
+static inline void igmc_dispatch(F&& f, bool v, Rest... rest) {
+  if (v) igmc_dispatch([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+  else igmc_dispatch([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}

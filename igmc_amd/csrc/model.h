@@ -9,6 +9,10 @@
 #define IGMC_STASH_LAYER 672  // floats per conv layer of the weights-only stash (fin_stash; layout: model.hip)
 #define IGMC_TS_BLOCKS 256   // partial slots of the relation-space tables (one per workgroup of k_graph_step)
 #define IGMC_GATHER_BLOCKS 4096   // max grid of the row-walker kernels (4 rows = 4 waves per block)
+// The basis-space mode of the gradient / Adam tail (k_finalize_ts) is correct up to 128 relations (the stash holds them) but only pays up to 32: its per-relation
+// loops (ARR matrix and value in the stash role, layer 0's d att) are serial in R -- yahoo_music's 71 relations measured
+// k_reduce_partials 15 -> 30 us and the gradient / Adam launch 57 -> 64 us against k_finalize (profiles/r04_experiments).
+#define IGMC_FBS_MAX_R 32
 #define IGMC_L0_BLOCKS 256
 #define IGMC_HG 8            // graphs per workgroup in the head kernels
 

@@ -1871,10 +1871,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_finalize(ModelDev m, const float
 // (k_finalize needs two in-kernel hand-offs for the same work -- layer-wide before Adam, grid-wide before the tick --
 //  each an agent-scope fence pair + an atomic round trip.)
 #define IGMC_FTS_NB 4
-// The basis-space mode of this tail is correct up to 128 relations (the stash holds them) but only pays up to 32: its per-relation
-// loops (ARR matrix and value in the stash role, layer 0's d att) are serial in R -- yahoo_music's 71 relations measured
-// k_reduce_partials 15 -> 30 us and the gradient / Adam launch 57 -> 64 us against k_finalize (profiles/r04_experiments).
-#define IGMC_FBS_MAX_R 32
+// (its basis-space mode takes up to IGMC_FBS_MAX_R relations: model.h)
 // gradient g of parameter i -> flat gradient, Adam moments, parameter; returns the parameter's value after the step.
 // store = false: the value only (a workgroup that needs a neighbour's updated parameter forms it itself; the owner stores)
 __device__ __forceinline__ float fts_emit(float* __restrict__ grad, const AdamTail& at, int64_t i, float g, float pold,
@@ -2310,18 +2307,112 @@ static inline int igmc_l0_grid(const ModelDev& m, int B) {
   return igmc_xcd_grid(m, B, rows, IGMC_GATHER_BLOCKS);
 }
 
-void igmc_launch_forward(const ModelDev& m, const ModelAux& ax, const BatchDev& b, const float* P, int B, int training,
+// ---- the phases of a call, each written once; sp (launch.h: StepPlan) says which kernels take them
+
+// The four conv layers (h_0..h_3 left in HBM): all of them in ONE launch (k_dl_fwd; nothing follows that would advance its
+// exchange tags unless sp.self_seq is 0: k_tail_ts then does), the dense per-layer kernels from the blocks alone -- no edge list
+// is read -- or the row walkers; then the products Y_l = h_{l-1} @ [basis_0 | .. | basis_3] a separate backward's att gradient reads
+static void launch_conv_fwd(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
+                            int use_flags, void* stream) {
+  if (sp.dl) igmc_launch_g2_compose(m, P, stream);        // the step's weight images + layer-0 table
+  if (sp.dlf) {
+    igmc_launch_dl_fwd(m, b, sp, P, B, training, use_flags, training ? m.dpre[3] : nullptr, stream);
+  } else if (sp.dl) {
+    igmc_launch_dl_layer0(m, b, B, training, use_flags, stream);
+  } else {
+    const size_t l0s = (size_t)(m.R * m.L * 32 + m.L * 32 + 32) * sizeof(float) + (size_t)4 * m.R * m.L * sizeof(int);
+    igmc_dispatch([&](auto uf, auto tr) {
+      IGMC_PLAUNCH("k_l0_fwd", (k_l0_fwd<uf(), tr()>), igmc_l0_grid(m, B), IGMC_BLOCK, l0s, stream, b, m, P, m.h[0]);
+    }, use_flags != 0, training != 0);
+  }
+  const int gt = igmc_xcd_grid(m, B, 16, 2048);                        // fused layer: 16 rows per workgroup
+  const size_t fsm4 = (size_t)(16 * IGMC_TP + 1024 + m.R * 4) * sizeof(float);
+  for (int l = 1; l < 4 && !sp.dlf; ++l) {
+    // the top layer's launch also clears dPre_3 (only its target rows are written by the head backward)
+    float* zo = (training && l == 3) ? m.dpre[3] : nullptr;
+    if (sp.dl) igmc_launch_dl_layer(m, b, P, B, l, 0, use_flags, zo, stream);
+    else igmc_dispatch([&](auto uf) {
+      IGMC_PLAUNCH("k_rgcn_layer_fwd", (k_rgcn_layer4<uf(), false>), gt, IGMC_BLOCK, fsm4, stream, b, m, P, l, zo);
+    }, use_flags != 0);
+  }
+  if (training && sp.need_y)
+    IGMC_PLAUNCH("k_dense_y_all", k_dense_y_all, dim3(igmc_rows_grid(m.node_cap, 64, 512), 3), IGMC_BLOCK,
+                 (size_t)32 * (128 + 4) * sizeof(float), stream, b, m, P);
+}
+
+// The three backward layer passes, one launch each: transposed gather of dPre_l (+ d att partials, or relation-space tables),
+// then [G | dPre_l] @ [basis^T ; root^T] + backward epilogue
+static void launch_layers_bwd(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int use_flags,
+                              int tables, void* stream) {
+  const int gt = igmc_xcd_grid(m, B, 16, 2048);
+  const size_t bsm4 = (size_t)(16 * IGMC_TP + 1024 + m.R * 4 + 16 * m.R * 4) * sizeof(float);
+  for (int l = 3; l >= 1; --l) {
+    if (sp.bwd_dense) igmc_launch_dl_layer(m, b, P, B, l, 1, use_flags, nullptr, stream, tables);
+    else igmc_dispatch([&](auto uf) {
+      IGMC_PLAUNCH("k_rgcn_layer_bwd", (k_rgcn_layer4<uf(), true>), gt, IGMC_BLOCK, bsm4, stream, b, m, P, l, (float*)nullptr);
+    }, use_flags != 0);
+  }
+}
+
+// The layer-0 table gradient where it does not ride in the MFMA weight-gradient kernel, then the reduction of every partial
+// (nstash = 4: its extra workgroups prepare the stash of k_finalize_ts in basis-space mode)
+static void launch_reduce(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, const int64_t* ctrl,
+                          int nstash, void* stream) {
+  const int rows0 = m.R * m.L + m.L + 1, l0_mfma = rows0 <= 32;
+  const float* d0 = m.dpre[0];
+  if (l0_mfma) {
+  } else if (rows0 <= 64) IGMC_PLAUNCH("k_l0_bwd", (k_l0_bwd<8>), IGMC_L0_BLOCKS, IGMC_BLOCK, 0, stream, b, m, d0, m.l0_part);
+  else IGMC_PLAUNCH("k_l0_bwd", (k_l0_bwd<40>), IGMC_L0_BLOCKS, IGMC_BLOCK, 0, stream, b, m, d0, m.l0_part);
+  const int nblk = ((l0_mfma ? 4 : 3) * igmc_wg_stride() + 63) / 64 + (l0_mfma ? 0 : (rows0 * 32 + 63) / 64) + (3 * m.R * 4 + 3) / 4;
+  IGMC_PLAUNCH("k_reduce_partials", k_reduce_partials, nblk + nstash, IGMC_BLOCK, 0, stream, m,
+               sp.bwd_dense ? sp.dl_grid : igmc_xcd_grid(m, B, 16, 2048), l0_mfma, IGMC_WG_BLOCKS, P, ctrl, nstash);
+}
+
+// Sum of the workgroups' relation-space tables (+ nlin workgroups that form d lin1 / d lin2, + the stash of k_finalize_ts)
+static void launch_tail_ts(const ModelDev& m, const BatchDev& b, const float* P, int B, float grad_scale, float mult, float* grad,
+                           int nlin, int nparts, int stride, int nstash, const int64_t* ctrl, int bump_seq, void* stream) {
+  IGMC_PLAUNCH("k_tail_ts", k_tail_ts, nlin + (4 * m.ts_stride + 63) / 64 + nstash, IGMC_BLOCK, 0, stream, b, m, P, grad_scale,
+               mult, 2.f, grad, nlin, nparts, stride, B, nstash, ctrl, bump_seq);
+}
+
+// The reduced gradient sources of a data-parallel step, summed over the ranks: tables + d att partials (one allocation), or the
+// basis-space sums (+ layer-0 table, d att); and the lin gradients (the tail of the flat parameter vector)
+static int launch_exchange(const ModelDev& m, int tail, const StepExchange* xch, float* grad, void* stream) {
+  if (!xch || tail == IGMC_TAIL_HANDOFF) return 0;
+  const int rows0 = m.R * m.L + m.L + 1;
+  const int64_t n = tail == IGMC_TAIL_TS ? (int64_t)4 * m.ts_stride + (int64_t)4 * m.ts_stride / 32 * 4
+                                         : (int64_t)3 * igmc_wg_stride() + 3 * m.R * 4 + rows0 * 32;
+  return xch->sum(xch->user, tail == IGMC_TAIL_TS ? m.ts_raw : m.graw, n, grad + m.off_l1w, m.n_params - m.off_l1w, stream);
+}
+
+// Gradient (+ ARR) of the conv parameters from the reduced sources; at.enabled: Adam on every parameter rides in it (and the
+// weight images of the updated parameters, img) -- else the loss is a launch of its own where one is asked for.
+// (ts_mode: k_finalize reads relation-space tables -- the subgraph kernel's, IGMC_FIN_MODE=0)
+static void launch_finalize(const ModelDev& m, const BatchDev& b, const float* P, float* grad, float arr_coef, int tail,
+                            int ts_mode, const AdamTail& at, int img, float ARR, float* loss, int* img_emitted, void* stream) {
+  const int bs = tail == IGMC_TAIL_BS;
+  if (tail == IGMC_TAIL_HANDOFF) {
+    if (at.enabled) IGMC_PLAUNCH("k_finalize_adam", k_finalize, 4 * IGMC_FIN_NB + 32, IGMC_BLOCK, 0, stream, m, P, grad, arr_coef, at, ts_mode);
+    else IGMC_PLAUNCH("k_finalize", k_finalize, 4 * IGMC_FIN_NB, IGMC_BLOCK, 0, stream, m, P, grad, arr_coef, at, ts_mode);
+  } else if (at.enabled) {
+    IGMC_PLAUNCH("k_finalize_adam", k_finalize_ts, 4 * IGMC_FTS_NB + 32 + 1, IGMC_BLOCK, 0, stream, m, P, grad, arr_coef, at, 32, bs, img);
+    if (img_emitted) *img_emitted = img;
+  } else {
+    IGMC_PLAUNCH("k_finalize", k_finalize_ts, 4 * IGMC_FTS_NB, IGMC_BLOCK, 0, stream, m, P, grad, arr_coef, at, 0, bs, 0);
+  }
+  if (!at.enabled && loss) igmc_launch_loss(m, b, ARR, loss, stream);
+}
+
+// ---- the public sequences
+
+void igmc_launch_forward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
                          int use_flags, const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult,
                          float* out, void* stream) {
-  {
-    G2Layout lay2;
-    int cs2 = 1;
-    if (!training && m.R * m.L + m.L + 1 <= 32 && igmc_g2_eligible(m, b, B, &lay2, &cs2)) {
-      igmc_launch_graph_step2(m, b, P, B, 0, use_flags, lay2, cs2, nullptr, seed, step, mult, 0.f, out, stream);
-      return;
-    }
+  if (sp.family == IGMC_FAM_G2) {      // (evaluation only: IGMC_CALL_EVAL)
+    igmc_launch_graph_step2(m, b, sp, P, B, 0, use_flags, nullptr, seed, step, mult, 0.f, out, stream);
+    return;
   }
-  igmc_launch_conv_forward(m, b, P, B, training, use_flags, stream);
+  launch_conv_fwd(m, b, sp, P, B, training, use_flags, stream);
   const int hgrid = (B + IGMC_HG - 1) / IGMC_HG;
   const size_t fs = (size_t)IGMC_HG * m.D * sizeof(float);
   if (m.D % 16 == 0)
@@ -2333,188 +2424,64 @@ void igmc_launch_forward(const ModelDev& m, const ModelAux& ax, const BatchDev& 
   else
     IGMC_PLAUNCH("k_head_fwd", (k_head_fwd<false>), hgrid, 512, 0, stream, b, m, P, training, inj_mask, seed, step,
                  mult, out);
-  (void)ax;
 }
 
-static inline int igmc_fin_mode() {
-  const char* fe = getenv("IGMC_FIN_MODE");        // 0: the hand-off version of the gradient / Adam tail (k_finalize); read
-  return fe ? atoi(fe) : 1;                        // on every call: tests switch it per case
+// The four conv layers alone, whatever the readout that follows (centre-node readout of IGMC: igmc_launch_forward; sort-pool
+// readout of DGCNN_RS: sortpool.hip)
+void igmc_launch_conv_forward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
+                              int use_flags, void* stream) {
+  launch_conv_fwd(m, b, sp, P, B, training, use_flags, stream);
 }
 
-// 1 = the conv backward of a dense readout gradient (sort-pool family) takes the one-launch form with relation-space tables
-// (igmc_launch_conv_backward); the forward then need not leave the Y products behind
-static int igmc_conv_bwd_tables(const ModelDev& m, const BatchDev& b, int B) {
-  const int fts = igmc_fin_mode() && m.fin_stash && m.datt_part && m.R <= 8;
-  return fts && m.R * m.L + m.L + 1 <= 32 && m.dcat[0] && igmc_dl_eligible(m, b, B) && igmc_dl_fwd_eligible(m, b, B) &&
-         igmc_dl_bwd_eligible(m, b, B);
-}
-
-void igmc_step_plan(const ModelDev& m, const BatchDev& b, int B, StepPlan* p) {
-  memset(p, 0, sizeof(*p));
-  const int ny = (m.D / 16 + 3) / 4;
-  const int l0_mfma = m.R * m.L + m.L + 1 <= 32;
-  p->fast_head = (m.D % 16 == 0) && 8 * ny <= IGMC_WG_BLOCKS;
-  if (!p->fast_head) {      // generic sequence: igmc_launch_conv_forward / igmc_launch_conv_backward
-    p->wide = igmc_dl_wide(m, b, B);
-    p->dl = p->wide || igmc_dl_eligible(m, b, B);
-    p->dlf = p->wide || (p->dl && igmc_dl_fwd_eligible(m, b, B));
-    p->dlts = p->dlb = igmc_conv_bwd_tables(m, b, B);
-  } else if (l0_mfma && igmc_g2_eligible(m, b, B, &p->lay, &p->cs)) {
-    p->family = IGMC_FAM_G2;      // (p->cs: igmc_gs_cluster)
-    p->grid = (p->cs > 1) ? p->cs * ((B + 7) & ~7) : igmc_gs_grid(B);
-    return;
-  } else {
-    const int fts_pre = igmc_fin_mode() && m.fin_stash && m.datt_part && m.R <= G2_NR * G2_NG_MAX;
-    p->wide = fts_pre && igmc_dl_wide(m, b, B);
-    p->dl = p->wide || igmc_dl_eligible(m, b, B);
-    p->dlts = p->wide || (p->dl && l0_mfma && fts_pre && m.R <= 8 && igmc_dl_ts_eligible(m, b, B));
-    p->dlf = p->wide || (p->dl && igmc_dl_fwd_eligible(m, b, B));
-    p->dlb = p->dlts && (p->wide || (p->dlf && igmc_dl_bwd_eligible(m, b, B)));
-  }
-  p->family = p->dlf ? IGMC_FAM_DLF : p->dl ? IGMC_FAM_DL : IGMC_FAM_ROWS;
-}
-
-// The four conv layers alone (h_0..h_3 left in HBM): the per-layer kernels, whatever the readout that follows
-// (centre-node readout of IGMC: igmc_launch_forward; sort-pool readout of DGCNN_RS: sortpool.hip)
-void igmc_launch_conv_forward(const ModelDev& m, const BatchDev& b, const float* P, int B, int training, int use_flags,
-                              void* stream) {
-  const size_t l0s = (size_t)(m.R * m.L * 32 + m.L * 32 + 32) * sizeof(float) + (size_t)4 * m.R * m.L * sizeof(int);
-  const int g16 = igmc_xcd_grid(m, B, 4, IGMC_GATHER_BLOCKS);   // one wave per row, 4 rows per block
-  const int g64 = igmc_rows_grid(m.node_cap, 64, 512);
-  // slots of 129..256 nodes a side with a dense block: every conv layer on the matrix cores (graphstep2.hip, k_dl_layer0 /
-  // k_dl_layer) from the blocks alone -- no edge list is read
-  // (more than five relations: the one-launch forward takes them in groups, igmc_dl_wide)
-  const int wide = igmc_dl_wide(m, b, B);
-  const int dl = wide || igmc_dl_eligible(m, b, B);
-  const int dlf = wide || (dl && igmc_dl_fwd_eligible(m, b, B));
-  if (dlf) {                                              // all four layers in ONE launch (k_dl_fwd); nothing follows that
-    igmc_launch_g2_compose(m, P, stream);                 // would advance its exchange tags: its last workgroup does
-    igmc_launch_dl_fwd(m, b, P, B, training, use_flags, training ? m.dpre[3] : nullptr, 1, stream);
-  } else if (dl) {
-    igmc_launch_g2_compose(m, P, stream);                 // the step's weight images + layer-0 table
-    igmc_launch_dl_layer0(m, b, B, training, use_flags, stream);
-  } else if (training) {
-    if (use_flags) IGMC_PLAUNCH("k_l0_fwd", (k_l0_fwd<true, true>), igmc_l0_grid(m, B), IGMC_BLOCK, l0s, stream, b, m, P, m.h[0]);
-    else IGMC_PLAUNCH("k_l0_fwd", (k_l0_fwd<false, true>), igmc_l0_grid(m, B), IGMC_BLOCK, l0s, stream, b, m, P, m.h[0]);
-  } else {
-    if (use_flags) IGMC_PLAUNCH("k_l0_fwd", (k_l0_fwd<true, false>), igmc_l0_grid(m, B), IGMC_BLOCK, l0s, stream, b, m, P, m.h[0]);
-    else IGMC_PLAUNCH("k_l0_fwd", (k_l0_fwd<false, false>), igmc_l0_grid(m, B), IGMC_BLOCK, l0s, stream, b, m, P, m.h[0]);
-  }
-  const size_t ysz = (size_t)32 * (128 + 4) * sizeof(float);
-  const int gt = igmc_xcd_grid(m, B, 16, 2048);                        // fused layer: 16 rows per workgroup
-  const size_t fsm4 = (size_t)(16 * IGMC_TP + 1024 + m.R * 4) * sizeof(float);
-  for (int l = 1; l < 4 && !dlf; ++l) {
-    // the top layer's launch also clears dPre_3 (only its target rows are written by the head backward)
-    float* zo = (training && l == 3) ? m.dpre[3] : nullptr;
-    if (dl) {
-      igmc_launch_dl_layer(m, b, P, B, l, 0, use_flags, zo, stream);
-    } else {
-      if (use_flags) IGMC_PLAUNCH("k_rgcn_layer_fwd", (k_rgcn_layer4<true, false>), gt, IGMC_BLOCK, fsm4, stream, b, m, P, l, zo);
-      else IGMC_PLAUNCH("k_rgcn_layer_fwd", (k_rgcn_layer4<false, false>), gt, IGMC_BLOCK, fsm4, stream, b, m, P, l, zo);
-    }
-  }
-  // training: the products Y_l = h_{l-1} @ [basis_0 | .. | basis_3] the backward's att gradient reads
-  if (training && !igmc_conv_bwd_tables(m, b, B)) IGMC_PLAUNCH("k_dense_y_all", k_dense_y_all, dim3(g64, 3), IGMC_BLOCK, ysz, stream, b, m, P);
-}
-
-void igmc_launch_backward(const ModelDev& m, const ModelAux& ax, const BatchDev& b, const float* P, int B, int use_flags,
+void igmc_launch_backward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int use_flags,
                           const float* gout, int from_err, float grad_scale, float mult, float drop_scale,
                           float arr_coef, float* grad, void* stream) {
-  const int g16 = igmc_xcd_grid(m, B, 4, IGMC_GATHER_BLOCKS);
-  const int g64 = igmc_rows_grid(m.node_cap, 64, 512);
   const int hgrid = (B + IGMC_HG - 1) / IGMC_HG;
-  const int na = m.R * 4;
-  const int rows0 = m.R * m.L + m.L + 1;
-  const int l0_mfma = rows0 <= 32;       // layer-0 table gradient rides in the MFMA weight-gradient kernel
-  void* s2 = stream;      // single stream: see the note at k_wgrad
-  (void)ax;
-  (void)g16; (void)g64; (void)na; (void)l0_mfma;
   if (m.D % 16 == 0)
     IGMC_PLAUNCH("k_head_bwd_a", k_head_bwd_a_mfma, dim3((B + 15) / 16, (m.D / 16 + 7) / 8), 512, 0, stream, b, m, P,
                  gout, from_err, grad_scale, mult, drop_scale, m.dpre[3]);
   else
     IGMC_PLAUNCH("k_head_bwd_a", k_head_bwd_a, hgrid, 1024, 0, stream, b, m, P, gout, from_err, grad_scale, mult,
                  drop_scale, m.dpre[3]);
-  if (m.D % 16 == 0)
-    IGMC_PLAUNCH("k_head_bwd_w", k_head_bwd_w_mfma, dim3(8, (m.D / 16 + 3) / 4), IGMC_BLOCK, 0, s2, b, m, P, gout,
+  if (m.D % 16 == 0)      // (same stream: see the note at k_wgrad)
+    IGMC_PLAUNCH("k_head_bwd_w", k_head_bwd_w_mfma, dim3(8, (m.D / 16 + 3) / 4), IGMC_BLOCK, 0, stream, b, m, P, gout,
                  from_err, grad_scale, mult, drop_scale, grad);
   else
-    IGMC_PLAUNCH("k_head_bwd_w", k_head_bwd_w, dim3(17, (m.D + 255) / 256), IGMC_BLOCK, 0, s2, b, m, P, gout, from_err,
+    IGMC_PLAUNCH("k_head_bwd_w", k_head_bwd_w, dim3(17, (m.D + 255) / 256), IGMC_BLOCK, 0, stream, b, m, P, gout, from_err,
                  grad_scale, mult, drop_scale, grad);
-  igmc_launch_conv_backward(m, b, P, B, use_flags, arr_coef, grad, stream);
+  igmc_launch_conv_backward(m, b, sp, P, B, use_flags, arr_coef, grad, stream);
 }
 
 // Backward of the four conv layers from dPre_3 (in m.dpre[3]) and the readout's gradient w.r.t. h_0..h_2 (gfeat on the
 // target rows, or the dense m.dcat[l]): dPre_2..0, weight-gradient partials, their reduction, gradient (+ ARR) of the conv
-// parameters into `grad` (k_finalize without Adam).
-void igmc_launch_conv_backward(const ModelDev& m, const BatchDev& b, const float* P, int B, int use_flags, float arr_coef,
-                               float* grad, void* stream) {
-  const int g16 = igmc_xcd_grid(m, B, 4, IGMC_GATHER_BLOCKS);
-  const int g64 = igmc_rows_grid(m.node_cap, 64, 512);
-  const int na = m.R * 4;
-  const int rows0 = m.R * m.L + m.L + 1;
-  const int l0_mfma = rows0 <= 32;
-  const int gt = igmc_xcd_grid(m, B, 16, 2048);
-  const size_t bsm4 = (size_t)(16 * IGMC_TP + 1024 + m.R * 4 + 16 * m.R * 4) * sizeof(float);
-  const int dl = igmc_dl_eligible(m, b, B);     // (the images of this step were composed by the forward)
-  // Dense readout gradient (sort-pool family) on the one-launch backward of the dense layers: dPre_3 of every row from
-  // m.dpre[3], the readout gradient of layers 0..2 added per row from m.dcat, relation-space tables -> k_tail_ts (no lin1 / lin2
-  // role) -> k_finalize_ts: three launches instead of the three layer passes, the Y products' consumers (k_wgrad), the
-  // partials' reduction and k_finalize.  (IGMC_DL_TS=0 / IGMC_DL_FUSED=0|1: the per-layer form below.)
-  {
-    if (igmc_conv_bwd_tables(m, b, B)) {
-      igmc_launch_dl_bwd(m, b, B, use_flags, stream, nullptr, 1);
-      const int gstride = (B + 7) & ~7, gg = igmc_dl_grid(b, B) / B * gstride;
-      IGMC_PLAUNCH("k_tail_ts", k_tail_ts, (4 * m.ts_stride + 63) / 64 + 4, IGMC_BLOCK, 0, stream, b, m, P, 0.f, 1.f, 2.f, grad,
-                   0, gg, gstride, B, 4, (const int64_t*)nullptr, 1);
-      AdamTail none;
-      memset(&none, 0, sizeof(none));
-      IGMC_PLAUNCH("k_finalize", k_finalize_ts, 4 * IGMC_FTS_NB, IGMC_BLOCK, 0, stream, m, P, grad, arr_coef, none, 0, 0, 0);
-      return;
-    }
+// parameters into `grad` (no Adam).
+// sp.dlb -- a dense readout gradient (sort-pool family) on the one-launch backward of the dense layers: dPre_3 of every row from
+// m.dpre[3], the readout gradient of layers 0..2 added per row from m.dcat, relation-space tables -> k_tail_ts (no lin1 / lin2
+// role) -> k_finalize_ts: three launches instead of the three layer passes, the Y products' consumers (k_wgrad), the
+// partials' reduction and k_finalize.  (IGMC_DL_TS=0 / IGMC_DL_FUSED=0|1: the per-layer form.)
+void igmc_launch_conv_backward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int use_flags,
+                               float arr_coef, float* grad, void* stream) {
+  AdamTail none;
+  memset(&none, 0, sizeof(none));
+  if (sp.dlb) {
+    const int gstride = (B + 7) & ~7;
+    igmc_launch_dl_bwd(m, b, sp, B, use_flags, stream, nullptr, 1);
+    launch_tail_ts(m, b, P, B, 0.f, 1.f, grad, 0, (sp.nqu + sp.nqv) * gstride, gstride, 4, nullptr, 1, stream);
+  } else {
+    const int l0_mfma = m.R * m.L + m.L + 1 <= 32;       // layer-0 table gradient rides in the MFMA weight-gradient kernel
+    launch_layers_bwd(m, b, sp, P, B, use_flags, 0, stream);
+    IGMC_PLAUNCH("k_wgrad", k_wgrad, dim3(IGMC_WG_BLOCKS, l0_mfma ? 4 : 3), IGMC_BLOCK, 0, stream, b, m, 0);
+    launch_reduce(m, b, sp, nullptr, B, nullptr, 0, stream);
   }
-  for (int l = 3; l >= 1; --l) {
-    // transposed gather of dPre_l (+ d att partials), then [G | dPre_l] @ [basis^T ; root^T] + backward epilogue
-    if (dl) {
-      igmc_launch_dl_layer(m, b, P, B, l, 1, use_flags, nullptr, stream);
-    } else {
-      if (use_flags) IGMC_PLAUNCH("k_rgcn_layer_bwd", (k_rgcn_layer4<true, true>), gt, IGMC_BLOCK, bsm4, stream, b, m, P, l, (float*)nullptr);
-      else IGMC_PLAUNCH("k_rgcn_layer_bwd", (k_rgcn_layer4<false, true>), gt, IGMC_BLOCK, bsm4, stream, b, m, P, l, (float*)nullptr);
-    }
-  }
-  const float* d0 = m.dpre[0];
-  IGMC_PLAUNCH("k_wgrad", k_wgrad, dim3(IGMC_WG_BLOCKS, l0_mfma ? 4 : 3), IGMC_BLOCK, 0, stream, b, m, 0);
-  if (l0_mfma) {
-  } else if (rows0 <= 64) IGMC_PLAUNCH("k_l0_bwd", (k_l0_bwd<8>), IGMC_L0_BLOCKS, IGMC_BLOCK, 0, stream, b, m, d0, m.l0_part);
-  else IGMC_PLAUNCH("k_l0_bwd", (k_l0_bwd<40>), IGMC_L0_BLOCKS, IGMC_BLOCK, 0, stream, b, m, d0, m.l0_part);
-  {
-    const int wgs2 = igmc_wg_stride(), n0 = rows0 * 32;
-    const int nblk = ((l0_mfma ? 4 : 3) * wgs2 + 63) / 64 + (l0_mfma ? 0 : (n0 + 63) / 64) + (3 * na + 3) / 4;
-    IGMC_PLAUNCH("k_reduce_partials", k_reduce_partials, nblk, IGMC_BLOCK, 0, stream, m,
-                 dl ? igmc_dl_grid(b, B) : gt, l0_mfma,
-                 IGMC_WG_BLOCKS, (const float*)nullptr, (const int64_t*)nullptr, 0);
-  }
-  {
-    AdamTail none;
-    memset(&none, 0, sizeof(none));
-    IGMC_PLAUNCH("k_finalize", k_finalize, 4 * IGMC_FIN_NB, IGMC_BLOCK, 0, stream, m, P, grad, arr_coef, none, 0);
-  }
+  launch_finalize(m, b, P, grad, arr_coef, sp.tail, 0, none, 0, 0.f, nullptr, nullptr, stream);
 }
 
-// Fused-step sequence (loss + gradients [+ Adam]) with the multi-role launches:
-//   l0_fwd, 3 x layer_fwd, {head fwd+bwd | Y}, 3 x layer_bwd, {weight grads | lin grads}, reduce, finalize[+Adam]
-
-int igmc_step_exchange_inside(const ModelDev& m, const BatchDev& b, int B) {
-  const int ny = (m.D / 16 + 3) / 4;
-  if (!((m.D % 16 == 0) && 8 * ny <= IGMC_WG_BLOCKS)) return 0;          // generic sequence: flat gradient only
-  G2Layout lay2;
-  int cs2 = 1;
-  if (m.R * m.L + m.L + 1 <= 32 && igmc_g2_eligible(m, b, B, &lay2, &cs2))
-    return igmc_fin_mode() && m.fin_stash && m.datt_part && m.R <= 8;
-  return igmc_fin_mode() && m.fin_stash && m.R <= IGMC_FBS_MAX_R;
-}
-
-int igmc_launch_loss_grad(const ModelDev& m_in, const ModelAux& ax, const BatchDev& b, float* P, int B, int use_flags,
+// Fused-step sequence (loss + gradients [+ Adam]) with the multi-role launches -- per family: forward, head, backward, tail,
+// exchange, finalize
+//   subgraph kernel:   k_graph_step (all of it down to per-workgroup tables), k_tail_ts, finalize
+//   dense + tables:    k_dl_fwd | layers, {head in k_dl_bwd | k_head_sub + k_dl_bwd | k_head_sub + 3 x layer_bwd}, k_tail_ts, finalize
+//   per layer:         l0_fwd, 3 x layer_fwd, {head fwd+bwd | Y}, 3 x layer_bwd, {weight grads | lin grads}, reduce, finalize
+int igmc_launch_loss_grad(const ModelDev& m_in, const BatchDev& b, const StepPlan& sp, float* P, int B, int use_flags,
                           const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float ARR,
                           float grad_scale, float arr_scale, float* out, float* grad, float* loss, const AdamTail* adam,
                           void* stream, const StepExchange* xch, int* img_emitted) {
@@ -2525,21 +2492,22 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const ModelAux& ax, const BatchD
   const int rows0 = m.R * m.L + m.L + 1;
   // the gradient / Adam kernel also leaves the weight images of the updated parameters
   const int img = adam && m.g2_w && m.R <= G2_NR * G2_NG_MAX && rows0 <= (g2_t0_rows(m.R, m.L) == 32 ? 32 : 48);
-  const int l0_mfma = rows0 <= 32;
-  const int gy = igmc_rows_grid(m.node_cap, 128, 512);
-  const int hb = (B + 15) / 16;
   const int ny = (m.D / 16 + 3) / 4;
-  StepPlan sp;      // (the branches below: igmc_step_plan)
-  igmc_step_plan(m, b, B, &sp);
-  const int64_t n_lin = m.n_params - m.off_l1w;      // lin1 / lin2 are the tail of the flat parameter vector
+  const float* Pc = P;
   AdamTail at;
   memset(&at, 0, sizeof(at));
-  if (adam) at = *adam;
+  if (adam) {
+    at = *adam;
+    at.enabled = sp.fast_head;      // (the generic sequence: Adam is a launch of its own)
+    at.b = b;
+    at.ARR = ARR;
+  }
   at.use_flags = use_flags;
   at.skip = xch ? xch->failed : nullptr;
+  const int64_t* ctrl = adam ? at.ctrl : nullptr;
   if (!sp.fast_head) {      // generic sequence
-    igmc_launch_forward(m, ax, b, P, B, 1, use_flags, inj_mask, seed, step, mult, out, stream);
-    igmc_launch_backward(m, ax, b, P, B, use_flags, nullptr, 1, grad_scale, mult, 2.f, ARR * arr_scale, grad, stream);
+    igmc_launch_forward(m, b, sp, Pc, B, 1, use_flags, inj_mask, seed, step, mult, out, stream);
+    igmc_launch_backward(m, b, sp, Pc, B, use_flags, nullptr, 1, grad_scale, mult, 2.f, ARR * arr_scale, grad, stream);
     if (adam) {
       igmc_launch_finish(m, b, at.p, grad, at.m1, at.m2, at.step_size, at.inv_sqrt_bc2, at.beta1, at.beta2, at.eps, at.wd,
                          at.ctrl, ARR, at.loss, at.total, use_flags, stream);
@@ -2548,167 +2516,42 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const ModelAux& ax, const BatchD
     }
     return 0;
   }
+  const int tables = sp.tail == IGMC_TAIL_TS;
   if (sp.family == IGMC_FAM_G2) {
-    // one workgroup (cluster) per subgraph: forward, residual and backward down to the per-workgroup gradient partials
-    const int cs = sp.cs;
-    const int gstride = (cs > 1) ? ((B + 7) & ~7) : IGMC_TS_BLOCKS;
-    const int gg = sp.grid;
-    int bump_seq = 0;       // 1: k_tail_ts advances the launch sequence number of the subgraph kernel's exchange tags
-    bump_seq = igmc_launch_graph_step2(m, b, P, B, 1, use_flags, sp.lay, cs, inj_mask, seed, step, mult, grad_scale, out, stream);
-    // IGMC_FIN_MODE=0: the hand-off version of the gradient / Adam tail (k_finalize) instead of k_finalize_ts
-    const int fts = igmc_fin_mode() && m.fin_stash && m.datt_part && m.R <= 8;
-    IGMC_PLAUNCH("k_tail_ts", k_tail_ts, 8 * ny + (4 * m.ts_stride + 63) / 64 + (fts ? 4 : 0), IGMC_BLOCK, 0, stream, b, m,
-                 (const float*)P, grad_scale, mult, 2.f, grad, 8 * ny, gg, gstride, B, fts ? 4 : 0,
-                 (const int64_t*)(adam ? at.ctrl : nullptr), bump_seq);
-    if (xch && fts) {      // tables + d att partials (one allocation) and the lin gradients, summed over the ranks
-      const int rc = xch->sum(xch->user, m.ts_raw, (int64_t)4 * m.ts_stride + (int64_t)4 * m.ts_stride / 32 * 4,
-                              grad + m.off_l1w, n_lin, stream);
-      if (rc) return rc;
-    }
-    if (adam) {
-      at.enabled = 1;
-      at.b = b;
-      at.ARR = ARR;
-      if (fts) {
-        IGMC_PLAUNCH("k_finalize_adam", k_finalize_ts, 4 * IGMC_FTS_NB + 32 + 1, IGMC_BLOCK, 0, stream, m, (const float*)P, grad, ARR * arr_scale, at, 32, 0, img);
-        if (img_emitted) *img_emitted = img;
-      } else IGMC_PLAUNCH("k_finalize_adam", k_finalize, 4 * IGMC_FIN_NB + 32, IGMC_BLOCK, 0, stream, m, (const float*)P, grad, ARR * arr_scale, at, 1);
-    } else {
-      if (fts) IGMC_PLAUNCH("k_finalize", k_finalize_ts, 4 * IGMC_FTS_NB, IGMC_BLOCK, 0, stream, m, (const float*)P, grad, ARR * arr_scale, at, 0, 0, 0);
-      else IGMC_PLAUNCH("k_finalize", k_finalize, 4 * IGMC_FIN_NB, IGMC_BLOCK, 0, stream, m, (const float*)P, grad, ARR * arr_scale, at, 1);
-      if (loss) igmc_launch_loss(m, b, ARR, loss, stream);
-    }
-    return 0;
-  }
-  const size_t l0s = (size_t)(m.R * m.L * 32 + m.L * 32 + 32) * sizeof(float) + (size_t)4 * m.R * m.L * sizeof(int);
-  const int g16 = igmc_xcd_grid(m, B, 4, IGMC_GATHER_BLOCKS);
-  const int gt = igmc_xcd_grid(m, B, 16, 2048);
-  // slots of 129..256 nodes a side with a dense block: every conv layer on the matrix cores (graphstep2.hip, k_dl_layer0 /
-  // k_dl_layer) from the blocks alone -- no edge list is read
-  // ... and all four of them as ONE launch where the members of a subgraph can hand h_l to each other (k_dl_fwd); the launch
-  // sequence number of its exchange tags is advanced by k_tail_ts (tables path) -- else by the launch's last workgroup
-  // more than five relations (igmc_dl_wide): the one-launch forward / backward in relation groups + the tables' tail, or nothing
-  const int dl = sp.dl, dlts = sp.dlts, dlf = sp.dlf;
-  if (dlf) {
-    igmc_launch_g2_compose(m, (const float*)P, stream);
-    igmc_launch_dl_fwd(m, b, (const float*)P, B, 1, use_flags, m.dpre[3], dlts ? 0 : 1, stream);
-  } else if (dl) {
-    igmc_launch_g2_compose(m, (const float*)P, stream);
-    igmc_launch_dl_layer0(m, b, B, 1, use_flags, stream);
-  } else if (use_flags) IGMC_PLAUNCH("k_l0_fwd", (k_l0_fwd<true, true>), igmc_l0_grid(m, B), IGMC_BLOCK, l0s, stream, b, m, (const float*)P, m.h[0]);
-  else IGMC_PLAUNCH("k_l0_fwd", (k_l0_fwd<false, true>), igmc_l0_grid(m, B), IGMC_BLOCK, l0s, stream, b, m, (const float*)P, m.h[0]);
-  const size_t fsm4 = (size_t)(16 * IGMC_TP + 1024 + m.R * 4) * sizeof(float);
-  const size_t bsm4 = (size_t)(16 * IGMC_TP + 1024 + m.R * 4 + 16 * m.R * 4) * sizeof(float);
-  const int gl = dl ? igmc_dl_grid(b, B) : gt;      // grid of the layer kernels
-  for (int l = 1; l < 4 && !dlf; ++l) {
-    float* zo = (l == 3) ? m.dpre[3] : nullptr;
-    if (dl) {
-      igmc_launch_dl_layer(m, b, (const float*)P, B, l, 0, use_flags, zo, stream);
-    } else {
-      if (use_flags) IGMC_PLAUNCH("k_rgcn_layer_fwd", (k_rgcn_layer4<true, false>), gt, IGMC_BLOCK, fsm4, stream, b, m, (const float*)P, l, zo);
-      else IGMC_PLAUNCH("k_rgcn_layer_fwd", (k_rgcn_layer4<false, false>), gt, IGMC_BLOCK, fsm4, stream, b, m, (const float*)P, l, zo);
-    }
-  }
-  const size_t ysz = (size_t)32 * (128 + 4) * sizeof(float);
-  // dense layers whose backward passes leave relation-space tables (igmc_dl_ts_eligible): the tail of the subgraph kernel
-  // -- k_tail_ts sums the workgroups' tables and forms d lin1 / d lin2, k_finalize_ts turns them into gradients (+ Adam) --
-  // replaces the Y products, G, the weight-gradient products and their reduction
-  if (dlts) {
-    if (sp.dlb) {
-      // the three backward layers as ONE launch, the loss head of each subgraph (side features included) in its set-up
-      // (IGMC_DL_HEAD=0: the head as a launch of its own in front of it)
-      const char* eh = getenv("IGMC_DL_HEAD");
-      DlHead hd;
-      hd.P = (const float*)P; hd.inj_mask = inj_mask; hd.seed = seed; hd.step = step; hd.mult = mult; hd.grad_scale = grad_scale;
-      hd.out = out;
-      const bool inside = !(eh && atoi(eh) == 0);
-      if (!inside) igmc_launch_head_sub(m, b, (const float*)P, B, inj_mask, seed, step, mult, grad_scale, out, stream);
-      igmc_launch_dl_bwd(m, b, B, use_flags, stream, inside ? &hd : nullptr);
-    } else {
-      // the head: one workgroup per subgraph, then one launch per backward layer
-      igmc_launch_head_sub(m, b, (const float*)P, B, inj_mask, seed, step, mult, grad_scale, out, stream);
-      for (int l = 3; l >= 1; --l) igmc_launch_dl_layer(m, b, (const float*)P, B, l, 1, use_flags, nullptr, stream, 1);
-    }
-    const int gstride = (B + 7) & ~7, gg = igmc_dl_grid(b, B) / B * gstride;
-    IGMC_PLAUNCH("k_tail_ts", k_tail_ts, 8 * ny + (4 * m.ts_stride + 63) / 64 + 4, IGMC_BLOCK, 0, stream, b, m,
-                 (const float*)P, grad_scale, mult, 2.f, grad, 8 * ny, gg, gstride, B, 4,
-                 (const int64_t*)(adam ? at.ctrl : nullptr), dlf ? 1 : 0);
-    if (xch) {
-      const int rc = xch->sum(xch->user, m.ts_raw, (int64_t)4 * m.ts_stride + (int64_t)4 * m.ts_stride / 32 * 4,
-                              grad + m.off_l1w, n_lin, stream);
-      if (rc) return rc;
-    }
-    if (adam) {
-      at.enabled = 1;
-      at.b = b;
-      at.ARR = ARR;
-      IGMC_PLAUNCH("k_finalize_adam", k_finalize_ts, 4 * IGMC_FTS_NB + 32 + 1, IGMC_BLOCK, 0, stream, m, (const float*)P, grad, ARR * arr_scale, at, 32, 0, img);
-      if (img_emitted) *img_emitted = img;
-    } else {
-      IGMC_PLAUNCH("k_finalize", k_finalize_ts, 4 * IGMC_FTS_NB, IGMC_BLOCK, 0, stream, m, (const float*)P, grad, ARR * arr_scale, at, 0, 0, 0);
-      if (loss) igmc_launch_loss(m, b, ARR, loss, stream);
-    }
-    return 0;
-  }
-  IGMC_PLAUNCH("k_head_train", k_head_train, dim3(hb > gy ? hb : gy, 4), 512, ysz, stream, b, m, (const float*)P, inj_mask,
-               seed, step, mult, grad_scale, out);
-  const int dlb = dl;
-  for (int l = 3; l >= 1; --l) {
-    if (dlb) {
-      igmc_launch_dl_layer(m, b, (const float*)P, B, l, 1, use_flags, nullptr, stream);
-    } else {
-      if (use_flags) IGMC_PLAUNCH("k_rgcn_layer_bwd", (k_rgcn_layer4<true, true>), gt, IGMC_BLOCK, bsm4, stream, b, m, (const float*)P, l, (float*)nullptr);
-      else IGMC_PLAUNCH("k_rgcn_layer_bwd", (k_rgcn_layer4<false, true>), gt, IGMC_BLOCK, bsm4, stream, b, m, (const float*)P, l, (float*)nullptr);
-    }
-  }
-  const int nsl = l0_mfma ? 4 : 3;
-  IGMC_PLAUNCH("k_wgrad_head", k_wgrad_head, dim3(IGMC_WG_BLOCKS, nsl + 1), IGMC_BLOCK, 0, stream, b, m, (const float*)P,
-               (const float*)nullptr, 1, grad_scale, mult, 2.f, grad, nsl);
-  if (!l0_mfma) {
-    const float* d0 = m.dpre[0];
-    if (rows0 <= 64) IGMC_PLAUNCH("k_l0_bwd", (k_l0_bwd<8>), IGMC_L0_BLOCKS, IGMC_BLOCK, 0, stream, b, m, d0, m.l0_part);
-    else IGMC_PLAUNCH("k_l0_bwd", (k_l0_bwd<40>), IGMC_L0_BLOCKS, IGMC_BLOCK, 0, stream, b, m, d0, m.l0_part);
-  }
-  {
-    const int wgs2 = igmc_wg_stride(), n0 = rows0 * 32, na = m.R * 4;
-    const int nblk = (nsl * wgs2 + 63) / 64 + (l0_mfma ? 0 : (n0 + 63) / 64) + (3 * na + 3) / 4;
-    // gradient / Adam tail without hand-offs (k_finalize_ts in basis-space mode) for R <= IGMC_FBS_MAX_R (the
-    // layer-0 table comes from the MFMA weight-gradient kernel or from k_l0_bwd's partials: same place, same layout);
-    // IGMC_FIN_MODE=0: the hand-off version (k_finalize)
-    const int fbs = igmc_fin_mode() && m.fin_stash && m.R <= IGMC_FBS_MAX_R;
-    IGMC_PLAUNCH("k_reduce_partials", k_reduce_partials, nblk + (fbs ? 4 : 0), IGMC_BLOCK, 0, stream, m, gl, l0_mfma,
-                 IGMC_WG_BLOCKS, (const float*)P, (const int64_t*)(adam ? at.ctrl : nullptr), fbs ? 4 : 0);
-    if (xch && fbs) {      // the reduced basis-space sums (+ layer-0 table, d att) and the lin gradients, over the ranks
-      const int rc = xch->sum(xch->user, m.graw, (int64_t)3 * wgs2 + 3 * na + n0, grad + m.off_l1w, n_lin, stream);
-      if (rc) return rc;
-    }
-    if (fbs) {
-      if (adam) {
-        at.enabled = 1;
-        at.b = b;
-        at.ARR = ARR;
-        IGMC_PLAUNCH("k_finalize_adam", k_finalize_ts, 4 * IGMC_FTS_NB + 32 + 1, IGMC_BLOCK, 0, stream, m, (const float*)P, grad, ARR * arr_scale, at, 32, 1, img);
-        if (img_emitted) *img_emitted = img;
-      } else {
-        IGMC_PLAUNCH("k_finalize", k_finalize_ts, 4 * IGMC_FTS_NB, IGMC_BLOCK, 0, stream, m, (const float*)P, grad, ARR * arr_scale, at, 0, 1, 0);
-        if (loss) igmc_launch_loss(m, b, ARR, loss, stream);
-      }
-      return 0;
-    }
-  }
-  if (adam) {
-    at.enabled = 1;
-    at.b = b;
-    at.ARR = ARR;
-    IGMC_PLAUNCH("k_finalize_adam", k_finalize, 4 * IGMC_FIN_NB + 32, IGMC_BLOCK, 0, stream, m, (const float*)P, grad, ARR * arr_scale, at, 0);
+    // one workgroup (cluster) per subgraph: forward, residual and backward down to the per-workgroup gradient partials;
+    // bump_seq = 1: k_tail_ts advances the launch sequence number of the subgraph kernel's exchange tags
+    const int bump_seq = igmc_launch_graph_step2(m, b, sp, Pc, B, 1, use_flags, inj_mask, seed, step, mult, grad_scale, out, stream);
+    launch_tail_ts(m, b, Pc, B, grad_scale, mult, grad, 8 * ny, sp.grid, (sp.cs > 1) ? ((B + 7) & ~7) : IGMC_TS_BLOCKS,
+                   tables ? 4 : 0, ctrl, bump_seq, stream);
   } else {
-    IGMC_PLAUNCH("k_finalize", k_finalize, 4 * IGMC_FIN_NB, IGMC_BLOCK, 0, stream, m, (const float*)P, grad, ARR * arr_scale, at, 0);
-    if (loss) igmc_launch_loss(m, b, ARR, loss, stream);
+    launch_conv_fwd(m, b, sp, Pc, B, 1, use_flags, stream);
+    if (sp.dlts) {
+      // the head: in the set-up of the one-launch backward (side features included), or one workgroup per subgraph in front of
+      // the backward -- one launch, or one per layer
+      const DlHead hd = {Pc, inj_mask, seed, step, mult, grad_scale, out};
+      const int inside = sp.dlb && sp.head_inside;
+      if (!inside) igmc_launch_head_sub(m, b, Pc, B, inj_mask, seed, step, mult, grad_scale, out, stream);
+      if (sp.dlb) igmc_launch_dl_bwd(m, b, sp, B, use_flags, stream, inside ? &hd : nullptr);
+      else launch_layers_bwd(m, b, sp, Pc, B, use_flags, 1, stream);
+      const int gstride = (B + 7) & ~7;
+      launch_tail_ts(m, b, Pc, B, grad_scale, mult, grad, 8 * ny, (sp.nqu + sp.nqv) * gstride, gstride, 4, ctrl, sp.dlf ? 1 : 0, stream);
+    } else {
+      const int gy = igmc_rows_grid(m.node_cap, 128, 512), hb = (B + 15) / 16, nsl = rows0 <= 32 ? 4 : 3;
+      IGMC_PLAUNCH("k_head_train", k_head_train, dim3(hb > gy ? hb : gy, 4), 512, (size_t)32 * (128 + 4) * sizeof(float), stream,
+                   b, m, Pc, inj_mask, seed, step, mult, grad_scale, out);
+      launch_layers_bwd(m, b, sp, Pc, B, use_flags, 0, stream);
+      IGMC_PLAUNCH("k_wgrad_head", k_wgrad_head, dim3(IGMC_WG_BLOCKS, nsl + 1), IGMC_BLOCK, 0, stream, b, m, Pc,
+                   (const float*)nullptr, 1, grad_scale, mult, 2.f, grad, nsl);
+      launch_reduce(m, b, sp, Pc, B, ctrl, sp.tail == IGMC_TAIL_BS ? 4 : 0, stream);
+    }
   }
+  // (the ARR term depends on the weights only: every rank adds it in full AFTER the exchange)
+  if (const int rc = launch_exchange(m, sp.tail, xch, grad, stream)) return rc;
+  launch_finalize(m, b, Pc, grad, ARR * arr_scale, sp.tail, sp.family == IGMC_FAM_G2, at, img, ARR, loss, img_emitted, stream);
   return 0;
 }
 
-int igmc_launch_train_step(const ModelDev& m, const ModelAux& ax, const BatchDev& b, float* P, int B, int use_flags,
+int igmc_launch_train_step(const ModelDev& m, const BatchDev& b, const StepPlan& sp, float* P, int B, int use_flags,
                            const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float ARR, float* out,
                            float* grad, float* m1, float* m2, float step_size, float inv_sqrt_bc2, float beta1,
                            float beta2, float eps, float wd, int64_t* ctrl, int* done, float* loss, double* total,
@@ -2718,7 +2561,7 @@ int igmc_launch_train_step(const ModelDev& m, const ModelAux& ax, const BatchDev
   at.p = P; at.m1 = m1; at.m2 = m2;
   at.step_size = step_size; at.inv_sqrt_bc2 = inv_sqrt_bc2; at.beta1 = beta1; at.beta2 = beta2; at.eps = eps; at.wd = wd;
   at.ctrl = ctrl; at.done = done; at.loss = loss; at.total = total;
-  return igmc_launch_loss_grad(m, ax, b, P, B, use_flags, inj_mask, seed, step, mult, ARR,
+  return igmc_launch_loss_grad(m, b, sp, P, B, use_flags, inj_mask, seed, step, mult, ARR,
                                grad_scale != 0.f ? grad_scale : 1.0f / (float)B, 1.0f, out, grad, nullptr, &at, stream, xch,
                                img_emitted);
 }

@@ -1,7 +1,7 @@
 """The launch geometries of a training step (``igmc_model_step_geometry``) that the batch size, the slot capacities, the
 relation count, the hop count and the side-feature width select -- one row on each side of every threshold of
-``igmc_gs_cluster`` / ``igmc_g2_layout`` (g2_compose.h), ``dl_split`` / ``igmc_dl_*_eligible`` / ``igmc_dl_wide`` /
-``dl_gsplit`` (dl_kernels.h) and the dense block of ``igmc_batch_create`` (capi.hip).
+``gs_cluster`` / ``igmc_g2_layout`` (step_plan.h, g2_compose.h), ``dl_split`` (dl_kernels.h) / ``dl_*_eligible`` /
+``dl_wide`` / ``dl_gsplit`` (step_plan.h) and the dense block of ``igmc_batch_create`` (capi.hip).
 
 tests/test_gpu_geometry.py runs every row against the oracle on an MI355X; tests/test_emu_geometry.py checks the query's
 answer for every row on the CPU (the emulator picks the clusters an MI355X picks when ``IGMC_GS_CLUSTER=4``)."""
