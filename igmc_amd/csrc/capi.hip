@@ -843,6 +843,18 @@ extern "C" int igmc_debug_lin_mask(const igmc_model* m, uint8_t* h_out, int64_t 
   return 0;
 }
 
+// debug aid (tests): host copy of what the head of the last TRAINING step left per subgraph -- which = 0: a1 [128], 1: dz [128],
+// 2: feat [D], 3: gfeat [D]; n floats from the start of the array.  Synchronises the device.
+extern "C" int igmc_debug_head_array(const igmc_model* m, int which, float* h_out, int64_t n) {
+  if (!m || !h_out) IGMC_FAIL("null argument");
+  if (which < 0 || which > 3) IGMC_FAIL("no such array");
+  const float* src = which == 0 ? m->d.a1 : which == 1 ? m->d.dz : which == 2 ? m->d.feat : m->d.gfeat;
+  if (n < 0 || n > (int64_t)m->d.graph_cap * (which < 2 ? 128 : m->d.D)) IGMC_FAIL("size out of range");
+  HIPCHECK(hipDeviceSynchronize());
+  HIPCHECK(hipMemcpy(h_out, src, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 extern "C" void igmc_model_destroy(igmc_model* m) {
   if (!m) return;
   for (int i = 0; i < 8; ++i) hipEventDestroy((hipEvent_t)m->ax.ev[i]);

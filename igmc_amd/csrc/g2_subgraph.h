@@ -70,7 +70,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
   float* sa1 = sgf + 256;                 // [128]
   float* skeep = sa1 + 128;               // [128]
   float* sdz = skeep + 128;               // [128]
-  float* sred = sdz + 128;                // [512]
+  float* sred = sdz + 128;                // [512] head: reduction slots; backward: column sums of dPre_l [2 (parity of l)][4 bundles][32] (d bias_l)
   float* misc = sred + 512;               // [16]
   const int R = a.R, L = a.L, RL = R * L;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
     {
       const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
       // (the plane image is NOT cleared: its first reader is layer 1's gather, behind a fetch that copies the whole image
-      //  from the exchange region -- planes_load -- and dPre_3's set-up clears what it needs itself; there is no block image)
+      //  from the exchange region -- planes_load -- and what dPre_3 needs is cleared behind layer 3's forward; there is no block image)
       for (int i = tid; i < 2 * G2_NB * 16 * G2_XP / 4; i += G2_THREADS) ((float4*)XOA)[i] = z4;
       for (int i = tid; i < G2_NB * 16 * G2_XP / 4; i += G2_THREADS) ((float4*)HIST)[i] = z4;
     }
@@ -406,6 +406,19 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
         for (int rr = 0; rr < 4; ++rr) of[rr] = hf ? po[rr] + o[1][rr] : o[0][rr] + po[rr];      // (K half 0 + K half 1)
         fwd_out(l, of, bias0_, XOn);
       }
+      if (TRAIN && l == 3) {
+        G2_STAMP(39);
+        // dPre_3's regions are cleared HERE, behind the wave's last forward stores and under the members' readout words
+        // on their way: the first k-step of the plane image (nodes 0..31 of every term / feature row: all that layer 3's
+        // backward gather reads; the rest still holds h_2 -- finite values the next exchange overwrites) and the bundle's
+        // XO0 (h_2 of its rows).  Both died at the pair barrier above; the barriers of the head order the clears in front of
+        // the centre-row writes of the set-up.
+        for (int i = tid; i < nsides * G2_NT * 32 * 16; i += G2_THREADS) {
+          const int s2 = i / (G2_NT * 32 * 16), r2 = i - s2 * (G2_NT * 32 * 16);
+          PLN[s2 * lay.pside + (r2 >> 4) * (kp >> 1) + (r2 & 15)] = 0u;
+        }
+        for (int i = lane + 64 * hf; i < 16 * G2_XP; i += 128) XO0[i] = 0.f;      // (the pair shares the bundle's tile)
+      }
       G2_STAMP(36 + (l - 1));
       // (no barrier here: planes / sW2 were dead at the barrier above; the pair's two halves of h_l in XOn and the reuse of
       //  PX are ordered by the next phase's barrier -- behind the next layer's reload, or the readout poll)
@@ -535,13 +548,8 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
       // ---- dPre_3: non-zero on the two centre rows only.  Own rows -> XO0 (h_3 sits in XO1), the opposite side's
       //      planes are rebuilt locally (node 0 of every feature; everything else zero): no exchange
       //      (only the first k-step -- nodes 0..31 of every term / feature row -- is read by layer 3's gather; the rest of
-      //      the planes still holds h_2: finite values that the next exchange overwrites)
-      for (int i = tid; i < nsides * G2_NT * 32 * 16; i += G2_THREADS) {
-        const int s2 = i / (G2_NT * 32 * 16), r2 = i - s2 * (G2_NT * 32 * 16);
-        PLN[s2 * lay.pside + (r2 >> 4) * (kp >> 1) + (r2 & 15)] = 0u;
-      }
-      for (int i = lane; i < 16 * G2_XP; i += 64) XO0[i] = 0.f;
-      __syncthreads();
+      //      the planes still holds h_2: finite values that the next exchange overwrites -- cleared, with XO0, behind layer 3's
+      //      pair barrier in the forward; only the centre-row writes are left here)
       if (tid < 32 * nsides) {
         const int s2 = tid >> 5, f = tid & 31;
         const int sd = (nsides == 2) ? s2 : 1 - side;
@@ -554,9 +562,12 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
         p2[32 * kp >> 1] = mi & 0xFFFFu;
         p2[2 * (32 * kp >> 1)] = lo & 0xFFFFu;
       }
-      if (active && bi == 0 && lane < 32) {
+      if (hf == 0 && lane < 32) {
+        // (d bias_3: the column sums of dPre_3 over a bundle's rows are its centre row, or zero)
         const float hv = sfeat[side * 128 + 96 + lane];
-        XO0[lane] = sgf[side * 128 + 96 + lane] * (1.f - hv * hv);
+        const float d = (active && bi == 0) ? sgf[side * 128 + 96 + lane] * (1.f - hv * hv) : 0.f;
+        if (active && bi == 0) XO0[lane] = d;
+        sred[(1 * G2_NB + bw) * 32 + lane] = d;
       }
       __syncthreads();
       G2_STAMP(18);
@@ -567,20 +578,6 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
         float* XOc = (l & 1) ? XO0 : XO1;            // dPre_l of the bundle's own rows
         float* XOn = (l & 1) ? XO1 : XO0;            // dPre_{l-1}
         float* wpart = a.ts_part + ((size_t)l * IGMC_TS_BLOCKS + tslot) * ts;
-        {   // d bias_l = column sums of dPre_l over this workgroup's rows (fixed order)
-          const int n = tid & 31, part = tid >> 5;
-          float sb = 0.f;
-          for (int row = part; row < G2_NB * 16; row += G2_THREADS / 32)
-            sb += XOA[(((l & 1) ? 0 : G2_NB) + (row >> 4)) * 16 * G2_XP + (row & 15) * G2_XP + n];
-          sred[part * 32 + n] = sb;
-        }
-        __syncthreads();
-        if (tid < 32) {
-          float s = 0.f;
-          for (int p = 0; p < G2_THREADS / 32; ++p) s += sred[p * 32 + tid];
-          if (first_graph) wpart[(R * 32 + 32) * 32 + tid] = s;
-          else wpart[(R * 32 + 32) * 32 + tid] += s;
-        }
         G2_STAMP(19 + 5 * (3 - l));
         float hreg[4];                               // h_{l-1}: rows 4 kq + rr, feature 16 hf + li
 #pragma unroll
@@ -621,6 +618,8 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
           for (int i = lane; i < 16 * G2_TP; i += 64) T[i] = 0.f;
           for (int i = lane; i < 16 * G2_XP; i += 64) HS[i] = 0.f;
         }
+        // (the column sums of dPre_l -- slots [l & 1][bundle][32] of sred, written one phase ago where dPre_l was formed -- are
+        //  complete at the barrier below; the slots of the other parity are written behind it)
         __syncthreads();                             // the pair's partials are exchanged; tiles / h chunks complete
         if (l == 2) G2_STAMP(47);
         if (active) {
@@ -642,6 +641,22 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
           }
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) XOn[(4 * kq + rr) * G2_XP + f] = v[rr];
+          if (l > 1) {
+            // d bias_{l-1}: column sum of the bundle's 16 rows of dPre_{l-1}, from the registers that hold them (fixed order)
+            float cb = (v[0] + v[1]) + (v[2] + v[3]);
+            cb += __shfl_xor(cb, 16);
+            cb += __shfl_xor(cb, 32);
+            if (kq == 0) sred[(((l - 1) & 1) * G2_NB + bw) * 32 + f] = cb;
+          }
+        } else if (l > 1 && lane < 16) {
+          sred[(((l - 1) & 1) * G2_NB + bw) * 32 + 16 * hf + lane] = 0.f;      // idle bundle: exact zeros
+        }
+        if (tid < 32) {
+          // d bias_l = the bundles' column sums of dPre_l in bundle order: under the table product, behind no barrier of its own
+          const float* sb = sred + (l & 1) * G2_NB * 32 + tid;
+          const float sv = (sb[0] + sb[32]) + (sb[64] + sb[96]);
+          if (first_graph) wpart[(R * 32 + 32) * 32 + tid] = sv;
+          else wpart[(R * 32 + 32) * 32 + tid] += sv;
         }
         G2_STAMP(20 + 5 * (3 - l));
         // (no barrier: the table product reads T' / h_{l-1} / dPre_l, complete at the barrier above; the dPre_{l-1} halves
