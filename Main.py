@@ -92,6 +92,12 @@ def build_parser():
                    help='write the N best unseen items of every requested user (ranked on the device) and stop; 0 = off')
     p.add_argument('--recommend-users', default=None, metavar='K|FILE',
                    help='users to recommend for: the first K user ids, or a text file with one id per line (default: all)')
+    p.add_argument('--rank-eval', default=None, metavar='K[,K...]',
+                   help='rank the held-out links (test split under --testing, else validation split) among every user\'s '
+                        'unseen items on the device, write hr / recall / precision / ndcg @K and mrr, and stop; uses '
+                        '--recommend-users to restrict the users')
+    p.add_argument('--rank-min-rating', type=float, default=None, metavar='X',
+                   help='--rank-eval: only held-out links rated >= X are relevant (default: all of them)')
     p.add_argument('--ensemble', action='store_true', default=False)
     p.add_argument('--standard-rating', action='store_true', default=False)
     # sparsity experiment settings
@@ -151,6 +157,42 @@ def write_recommendations(model, train_graphs, args):
                 f.write('%d\t%d\t%d\t%.6f\n' % (u, r + 1, row[r], srow[r]))
     print('Recommended for {} users: {} candidates scored in {} pass(es), {:.0f} candidates/s; wrote {}'.format(
         stats['users'], stats['candidates'], stats['passes'], stats['candidates'] / max(dt, 1e-9), path))
+    return path
+
+
+def rank_eval_ks(spec):
+    """``--rank-eval 5,10``: the cut-offs K, 1 to 8 integers >= 1."""
+    try:
+        ks = [int(x) for x in spec.split(',')]
+    except ValueError:
+        ks = []
+    if not 1 <= len(ks) <= 8 or min(ks) < 1:
+        raise SystemExit('--rank-eval takes 1 to 8 comma-separated cut-offs K >= 1, e.g. 5,10,20')
+    return ks
+
+
+def write_ranking(model, train_graphs, heldout_graphs, args):
+    """``--rank-eval``: ``<res_dir>/ranking_<data_name>.tsv`` with lines ``metric\tvalue`` -- the ranking metrics of the held-out
+    links among every user's unseen items of the training graph (``igmc_amd/rank_eval.py``)."""
+    import time
+    from igmc_amd.rank_eval import HeldOut, metric_names, rank_eval
+    ks = rank_eval_ks(args.rank_eval)
+    users = recommend_users(args.recommend_users, train_graphs.graph.n_users)
+    heldout = HeldOut.from_links(heldout_graphs, min_rating=args.rank_min_rating)
+    stats = {}
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = rank_eval(model, train_graphs, heldout, ks=ks, batch_size=args.batch_size, users=users, stats=stats)      # (synchronises)
+    dt = time.perf_counter() - t0
+    names = metric_names(ks)
+    path = os.path.join(args.res_dir, 'ranking_{}.tsv'.format(args.data_name))
+    with open(path, 'w') as f:
+        for k in names:
+            f.write('%s\t%.6f\n' % (k, res[k]))
+    print('Ranked {} held-out links of {} users ({} not among the candidates; means over {} users) among {} candidates in '
+          '{} pass(es), {:.0f} candidates/s: {}; wrote {}'.format(
+              stats['queries'], stats['users'], stats['not_candidates'], res['users_evaluated'], stats['candidates'],
+              stats['passes'], stats['candidates'] / max(dt, 1e-9), ', '.join('%s %.4f' % (k, res[k]) for k in names), path))
     return path
 
 
@@ -285,12 +327,18 @@ def main(argv=None):
     # only rank 0 writes checkpoints (inside `logger`): nobody may look for them before it is done
     parallel.barrier()
 
-    if args.recommend > 0:
+    if args.recommend > 0 or args.rank_eval:
         # no reference counterpart: the checkpoint's N best unseen items per user over adj_train, with the training set's
-        # extraction settings (and nothing else of what follows).  Rank 0 does the work; the other ranks wait at the barrier.
+        # extraction settings, and / or where the held-out links (test split under --testing, else validation split) stand
+        # among those items (and nothing else of what follows).  Rank 0 does the work; the other ranks wait at the barrier.
+        if args.rank_eval:
+            rank_eval_ks(args.rank_eval)
         model.load_state_dict(torch.load(args.model_pos, map_location='cpu'))
         if rank == 0:
-            write_recommendations(model, train_graphs, args)
+            if args.recommend > 0:
+                write_recommendations(model, train_graphs, args)
+            if args.rank_eval:
+                write_ranking(model, train_graphs, test_graphs, args)
         parallel.barrier()
         return rmse
 

@@ -1123,6 +1123,33 @@ extern "C" int igmc_select_segments(const float* d_keys, const int64_t* d_seg_of
   return 0;
 }
 
+// ------------------------------------------------------------------ places of given ids in their segments + metric sums (ranking.hip)
+extern "C" int igmc_rank_segments(const float* d_keys, const int32_t* d_ids, int64_t n, const int64_t* d_seg_off, int ns,
+                                  const int64_t* d_q_off, const int32_t* d_q_id, int64_t nq, int32_t* d_q_pos,
+                                  int32_t* d_q_rank, int32_t* d_err, int geometry, void* stream) {
+  if (!d_keys || !d_ids || !d_seg_off || !d_q_off || !d_err) IGMC_FAIL("null argument");
+  if (nq > 0 && (!d_q_id || !d_q_pos || !d_q_rank)) IGMC_FAIL("null argument");
+  if (n < 1 || n > (int64_t)INT32_MAX) IGMC_FAIL("n must be in [1, 2^31)");
+  if (nq < 0 || nq > (int64_t)INT32_MAX) IGMC_FAIL("nq must be in [0, 2^31)");
+  if (ns < 1 || geometry < 0 || geometry > IGMC_SEGSEL_MAX_SPLIT) IGMC_FAIL("ns must be at least 1, geometry in [0, 64]");
+  igmc_launch_rank_segments(d_keys, d_ids, n, d_seg_off, ns, d_q_off, d_q_id, nq,
+                            geometry > 0 ? geometry : igmc_segsel_default_split(ns), d_q_pos, d_q_rank, d_err, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int igmc_rank_metrics(const int32_t* d_q_rank, const int64_t* d_q_off, const uint8_t* d_q_rel, int64_t nq, int ns,
+                                 const int32_t* d_ks, int nk, int32_t* d_cnt, double* d_dcg, int32_t* d_err, int grid,
+                                 void* stream) {
+  if (!d_q_off || !d_ks || !d_cnt || !d_dcg || !d_err) IGMC_FAIL("null argument");
+  if (nq > 0 && !d_q_rank) IGMC_FAIL("null argument");
+  if (nq < 0 || nq > (int64_t)INT32_MAX) IGMC_FAIL("nq must be in [0, 2^31)");
+  if (ns < 1 || nk < 1 || nk > IGMC_RANK_MAX_KS || grid < 0 || grid > 65536)
+    IGMC_FAIL("ns must be at least 1, nk in [1, 8], grid in [0, 65536]");
+  igmc_launch_rank_metrics(d_q_rank, d_q_off, d_q_rel, d_ks, nk, ns, nq, grid, d_cnt, d_dcg, d_err, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
 // ------------------------------------------------------------------ device-side step control
 extern "C" int igmc_ctrl_tick(int64_t* d_ctrl, void* stream) {
   if (!d_ctrl) IGMC_FAIL("null ctrl");

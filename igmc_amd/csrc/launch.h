@@ -93,6 +93,14 @@ void igmc_launch_candidates_fill(const GraphDev& g, const int32_t* users, int nq
 int igmc_segsel_default_split(int ns);
 void igmc_launch_select_segments(const float* keys, const int64_t* seg_off, int ns, int num, int k, void* scratch,
                                  int32_t* idx_out, float* key_out, int32_t* count, void* stream);
+// ranking.hip: the position and the 0-based place (the order of igmc_launch_select_segments) of given ids in their segments,
+// and the per-segment sums of the ranking metrics over those places
+#define IGMC_RANK_MAX_KS 8              // cut-offs K of one metrics launch at most
+void igmc_launch_rank_segments(const float* keys, const int32_t* ids, int64_t n, const int64_t* seg_off, int ns,
+                               const int64_t* q_off, const int32_t* q_id, int64_t nq, int k, int32_t* q_pos, int32_t* q_rank,
+                               int32_t* err, void* stream);
+void igmc_launch_rank_metrics(const int32_t* q_rank, const int64_t* q_off, const uint8_t* q_rel, const int32_t* ks, int nk,
+                              int ns, int64_t nq, int grid, int32_t* cnt, double* dcg, int32_t* err, void* stream);
 int igmc_model_prepare(const ModelDev& m);
 void igmc_launch_adam(float* p, const float* g, float* m1, float* m2, int64_t n, float step_size,
                       float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd, int64_t* ctrl, int tick,

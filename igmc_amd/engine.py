@@ -380,6 +380,89 @@ def select_segments(keys, seg_off, num, geometry=0, lib=None, stream=None):
     return idx, key, count
 
 
+RANK_ERRORS = ((1, 'query offsets that are not 0 = q_off[0] <= ... <= q_off[ns] = the number of queries'),
+               (2, 'a segment outside the keys'))
+
+
+def _dev_vector(t, dtype, what):
+    if t.dtype != dtype or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
+        raise ValueError('%s: a contiguous 1-D %s device tensor' % (what, str(dtype).replace('torch.', '')))
+
+
+def rank_segments(keys, ids, seg_off, q_off, q_id, geometry=0, err=None, lib=None, stream=None):
+    """Where the ids ``q_id`` stand in their segments (``igmc_rank_segments``; no reference counterpart).  ``keys`` float32 /
+    ``ids`` int32 ``[n]`` (ids strictly ascending inside every segment), ``seg_off`` / ``q_off`` int64 ``[ns + 1]``: segment
+    ``s`` owns the queries ``q_id[q_off[s]:q_off[s + 1]]`` (int32).  Returns device tensors ``(pos, rank)`` int32 ``[nq]``:
+    the position in ``keys`` of the entry with the query's id and its 0-based place in the order of
+    :func:`select_segments` (key descending, index ascending, NaNs last); -1 / -1 where the segment has no such entry.
+    ``err``: a zeroed int32 device word that collects the error bits (``RANK_ERRORS``) and is left to the caller to read;
+    without it the word is read here (one synchronisation) and a set bit raises.  Nothing else leaves the device."""
+    import torch
+    lib = lib or _lib.load()
+    _dev_vector(keys, torch.float32, 'keys')
+    _dev_vector(ids, torch.int32, 'ids')
+    _dev_vector(seg_off, torch.int64, 'seg_off')
+    _dev_vector(q_off, torch.int64, 'q_off')
+    _dev_vector(q_id, torch.int32, 'q_id')
+    if ids.numel() != keys.numel() or q_off.numel() != seg_off.numel():
+        raise ValueError('one id per key and one query range per segment')
+    ns, n, nq = seg_off.numel() - 1, keys.numel(), q_id.numel()
+    pos = torch.full((nq,), -1, dtype=torch.int32, device=keys.device)
+    rank = torch.full((nq,), -1, dtype=torch.int32, device=keys.device)
+    if n == 0 or nq == 0:          # (every segment is empty, or nobody asks: nothing to launch over)
+        return pos, rank
+    own = err is None
+    if own:
+        err = torch.zeros(1, dtype=torch.int32, device=keys.device)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    lib.call('igmc_rank_segments', _p(keys.data_ptr()), _p(ids.data_ptr()), n, _p(seg_off.data_ptr()), ns,
+             _p(q_off.data_ptr()), _p(q_id.data_ptr()), nq, _p(pos.data_ptr()), _p(rank.data_ptr()), _p(err.data_ptr()),
+             int(geometry), _p(st))
+    if own:
+        _raise_rank_errors(err, 'igmc_rank_segments')
+    return pos, rank
+
+
+def rank_metrics(rank, q_off, ks, relevant=None, grid=0, err=None, lib=None, stream=None):
+    """Per-segment sums of the ranking metrics over the ranks of :func:`rank_segments` (``igmc_rank_metrics``; binary
+    relevance: a query counts when ``relevant`` -- uint8 ``[nq]``, None = all -- is set and its rank is >= 0).  ``ks``: 1 to 8
+    cut-offs K >= 1.  Returns device tensors ``(cnt int32 [ns, 2 + nk], dcg float64 [ns, 2 * nk])``: ``cnt[:, 0]`` = n_rel,
+    ``cnt[:, 1]`` = the smallest rank (-1: none), ``cnt[:, 2 + j]`` = #{rank < ks[j]}; ``dcg[:, j]`` = the sum of
+    1 / log2(rank + 2) over those, ``dcg[:, nk + j]`` = the same sum for the ideal list of min(K, n_rel) places.  Bit-identical
+    for every ``grid``.  ``err``: as in :func:`rank_segments`."""
+    import torch
+    lib = lib or _lib.load()
+    _dev_vector(rank, torch.int32, 'rank')
+    _dev_vector(q_off, torch.int64, 'q_off')
+    if relevant is not None:
+        _dev_vector(relevant, torch.uint8, 'relevant')
+        if relevant.numel() != rank.numel():
+            raise ValueError('one relevance flag per query')
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= 8 or min(ks) < 1 or max(ks) > 2 ** 31 - 1:
+        raise ValueError('ks: 1 to 8 cut-offs K in [1, 2^31)')
+    ns, nk = q_off.numel() - 1, len(ks)
+    d_ks = torch.tensor(ks, dtype=torch.int32, device=rank.device)
+    cnt = torch.zeros(ns, 2 + nk, dtype=torch.int32, device=rank.device)
+    dcg = torch.zeros(ns, 2 * nk, dtype=torch.float64, device=rank.device)
+    own = err is None
+    if own:
+        err = torch.zeros(1, dtype=torch.int32, device=rank.device)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    lib.call('igmc_rank_metrics', _p(rank.data_ptr() if rank.numel() else None), _p(q_off.data_ptr()),
+             _p(None if relevant is None else relevant.data_ptr()), rank.numel(), ns, _p(d_ks.data_ptr()), nk,
+             _p(cnt.data_ptr()), _p(dcg.data_ptr()), _p(err.data_ptr()), int(grid), _p(st))
+    if own:
+        _raise_rank_errors(err, 'igmc_rank_metrics')
+    return cnt, dcg
+
+
+def _raise_rank_errors(err, what):
+    e = int(err.item())
+    if e:
+        raise RuntimeError('%s: %s (err=%d)' % (what, '; '.join(w for b, w in RANK_ERRORS if e & b), e))
+
+
 def profile_enable(lib, on):
     lib.igmc_profile_enable(int(bool(on)))
 

@@ -1,0 +1,180 @@
+"""Held-out ranking evaluation on the device: where do the items a user really rated stand in that user's recommendation
+list -- hit rate, recall, precision, NDCG@K and MRR over a held-out split (no reference counterpart: the reference judges
+rating regression only, by the test RMSE, which says nothing about order).
+
+Held-out links are absent from the training graph, so they are candidates of :mod:`igmc_amd.recommend` already.
+:func:`rank_eval` runs the passes of ``recommend`` (``recommend.candidate_passes``: refill, score -- one ``CandidateLinks``,
+one replayed ``ScoreGraph``) and, instead of taking the ``n`` best of every segment, asks where GIVEN items stand
+(``igmc_amd/csrc/ranking.hip``):
+
+* ``igmc_rank_segments`` finds every held-out item in its user's item-ascending segment by binary search and counts the
+  candidates in front of it in the order of ``igmc_select_segments`` (score descending, item id ascending, NaNs last): its
+  0-based rank, an integer that does not depend on the launch geometry;
+* ``igmc_rank_metrics`` reduces the ranks to per-user sums (relevant links, first rank, hits@K, DCG@K, ideal DCG@K), float64
+  in a fixed order.
+
+Nothing per candidate crosses to the host: one total per pass (the refill's), the per-user query offsets of the held-out set
+once, and the handful of means at the end.
+
+THE METRICS (binary relevance; means in float64 over the users that have at least one relevant held-out link WITH A RANK):
+``hr@K`` = mean(hits_K > 0), ``recall@K`` = mean(hits_K / n_rel), ``precision@K`` = mean(hits_K / K), ``ndcg@K`` =
+mean(dcg_K / idcg_K), ``mrr`` = mean(1 / (first_rank + 1)), with hits_K = #{rank < K}.  ``recall@K`` IS NORMALISED BY n_rel,
+NOT BY min(K, n_rel): a user with more relevant links than K cannot reach 1 (``ndcg@K``'s ideal list does stop at
+min(K, n_rel)).  A held-out link that is NO CANDIDATE (the user also has it in the rating graph and ``exclude_seen`` is set,
+or ``item_mask`` leaves the item out) has no rank: it is counted in ``stats['not_candidates']`` and LEFT OUT of every metric,
+n_rel included -- never silently counted as a miss.  A link given twice counts twice.
+
+SAMPLER POSITIONS.  As in :mod:`igmc_amd.recommend`: the extraction's sampler is keyed by (seed, epoch, link position), and a
+candidate's position is its index in ITS PASS's list.  Where a per-hop cap binds (a neighbourhood larger than
+``max_nodes_per_hop`` is sampled), a candidate's score -- and so a held-out link's RANK -- depends on where it sits in its
+pass, hence on ``users_per_pass`` and on the users evaluated with it; every result is still a deterministic function of
+(seed, users, ``users_per_pass``).  Where no cap binds the ranks do not depend on how the users are divided into passes.
+"""
+import numpy as np
+import torch
+
+from . import engine
+from .recommend import _dev_int32, candidate_passes
+
+
+class HeldOut(object):
+    """Held-out links grouped by user, on the device: ``users`` (int32 ``[nu]``, distinct, ascending), ``offsets`` (int64
+    ``[nu + 1]``: user ``users[i]`` owns the links ``offsets[i]:offsets[i + 1]``), ``items`` (int32 ``[n]``, ascending
+    within a user), ``relevant`` (uint8 ``[n]``, or None = every link is relevant) and ``order`` (int64 ``[n]``: the
+    index in the input of the link at each place)."""
+
+    def __init__(self, users, offsets, items, relevant, order):
+        self.users, self.offsets, self.items, self.relevant, self.order = users, offsets, items, relevant, order
+
+    def __len__(self):
+        return self.items.numel()
+
+    @classmethod
+    def from_links(cls, dataset_or_graph, u=None, v=None, ratings=None, min_rating=None):
+        """Links ``(u[i], v[i])`` (ids, host or device) sorted by (user, item) on the device.  ``relevant = ratings >=
+        min_rating``; with ``min_rating=None`` every link is relevant.  The first argument names the rating graph the ids
+        belong to (a dataset or its ``engine.Graph``); a dataset given WITHOUT ``u`` / ``v`` is the held-out set itself:
+        its ``link_u``, ``link_v`` and -- as ratings -- ``link_y``."""
+        src = dataset_or_graph
+        graph = getattr(src, 'graph', src)
+        if u is None and v is None:
+            if not hasattr(src, 'link_u'):
+                raise ValueError('no links: give u and v, or a dataset')
+            u, v = src.link_u[:len(src)], src.link_v[:len(src)]
+            if ratings is None:
+                ratings = src.link_y[:len(src)]
+        elif u is None or v is None:
+            raise ValueError('u and v come together')
+        dev = src.link_y.device if hasattr(src, 'link_y') else torch.device('cuda', graph.device)
+        u, v = _dev_int32(u, dev, 'u').long(), _dev_int32(v, dev, 'v').long()
+        if u.numel() != v.numel():
+            raise ValueError('u and v differ in length')
+        if u.numel() < 1:
+            raise ValueError('no held-out links')
+        if bool(((u < 0) | (u >= graph.n_users) | (v < 0) | (v >= graph.n_items)).any().item()):
+            raise ValueError('a link outside the rating graph (%d users x %d items)' % (graph.n_users, graph.n_items))
+        relevant = None
+        if min_rating is not None:
+            if ratings is None:
+                raise ValueError('min_rating needs the ratings of the links')
+            r = torch.as_tensor(np.asarray(ratings) if not torch.is_tensor(ratings) else ratings).to(dev)
+            if r.dim() != 1 or r.numel() != u.numel():
+                raise ValueError('one rating per link')
+            relevant = r >= min_rating
+        order = torch.argsort(u * graph.n_items + v, stable=True)
+        u, v = u[order], v[order]
+        users, counts = torch.unique_consecutive(u, return_counts=True)
+        offsets = torch.zeros(users.numel() + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, out=offsets[1:])
+        return cls(users.to(torch.int32), offsets, v.to(torch.int32).contiguous(),
+                   None if relevant is None else relevant[order].to(torch.uint8).contiguous(), order)
+
+
+def _select(heldout, users):
+    """The held-out users to evaluate -- all of them, or those that are also in ``users`` -- as ``(users int32 [m], q_off
+    int64 [m + 1], items, relevant, index)``: their links side by side, ``index`` = each link's place in ``heldout`` (None:
+    all of them, as they are)."""
+    if users is None:
+        return heldout.users, heldout.offsets, heldout.items, heldout.relevant, None
+    dev = heldout.items.device
+    sel = torch.isin(heldout.users, _dev_int32(users, dev, 'users')).nonzero().view(-1)
+    lens = heldout.offsets[sel + 1] - heldout.offsets[sel]
+    q_off = torch.zeros(sel.numel() + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(lens, 0, out=q_off[1:])
+    index = torch.repeat_interleave(heldout.offsets[sel] - q_off[:-1], lens) + \
+        torch.arange(int(lens.sum().item()), dtype=torch.int64, device=dev)
+    return (heldout.users[sel], q_off, heldout.items[index].contiguous(),
+            None if heldout.relevant is None else heldout.relevant[index].contiguous(), index)
+
+
+def metric_names(ks):
+    return ['%s@%d' % (m, k) for k in ks for m in ('hr', 'recall', 'precision', 'ndcg')] + ['mrr']
+
+
+def reduce_metrics(cnt, dcg, ks):
+    """The means of the module docstring from the per-user sums of ``igmc_rank_metrics``: a float64 device vector in the
+    order of :func:`metric_names`, with the number of users it was taken over behind it.  NaN where no user counts."""
+    nk = len(ks)
+    keep = cnt[:, 0] > 0
+    n = keep.sum().to(torch.float64)
+    n_rel = cnt[keep, 0].to(torch.float64)
+    hits = cnt[keep, 2:].to(torch.float64)
+    out = []
+    for j, k in enumerate(ks):
+        out += [(hits[:, j] > 0).to(torch.float64).sum() / n, (hits[:, j] / n_rel).sum() / n, (hits[:, j] / float(k)).sum() / n,
+                (dcg[keep, j] / dcg[keep, nk + j]).sum() / n]
+    out.append((1.0 / (cnt[keep, 1].to(torch.float64) + 1.0)).sum() / n)
+    return torch.stack(out + [n])
+
+
+def rank_eval(model, dataset, heldout, ks=(5, 10, 20), batch_size=50, exclude_seen=True, item_mask=None, users=None,
+              users_per_pass=None, stats=None):
+    """Ranking metrics of ``heldout`` (a :class:`HeldOut`, or a dataset: :meth:`HeldOut.from_links`) over the rating graph
+    and with the extraction settings of ``dataset`` (normally the training set), for the held-out users -- or those of
+    them that are in ``users`` --: for every pass of ``recommend`` (same candidates, same scores, same ``users_per_pass``)
+    the rank of every held-out link among its user's candidates, then the per-user sums and their means.
+
+    Returns a dict of Python floats ``hr@K``, ``recall@K``, ``precision@K``, ``ndcg@K`` for every K of ``ks`` (1 to 8
+    cut-offs) and ``mrr`` (see the module docstring; NaN when no user counts), ``users_evaluated`` (int: the users the means
+    were taken over) and ``per_user``: device tensors ``users`` (int32 ``[m]``), ``offsets`` (int64 ``[m + 1]``: the user's
+    links), ``items`` / ``relevant`` of the links, ``cnt`` (int32 ``[m, 2 + nk]``) / ``dcg`` (float64 ``[m, 2 * nk]``) as
+    ``engine.rank_metrics`` returns them, and per link ``rank`` and ``pos``, its position in ITS PASS's candidate list
+    (both -1 for a link that is no candidate), ``index`` (its place in ``heldout``; None = the same place).
+
+    ``stats`` receives ``users``, ``candidates``, ``passes``, ``queries`` and ``not_candidates``.  Side-feature datasets
+    raise ``NotImplementedError`` (``CandidateLinks``).  Works for ``DGCNN_RS`` too."""
+    if not isinstance(heldout, HeldOut):
+        heldout = HeldOut.from_links(heldout)
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= 8 or min(ks) < 1:
+        raise ValueError('ks: 1 to 8 cut-offs K >= 1')
+    sel_users, q_off, items, relevant, index = _select(heldout, users)
+    if sel_users.numel() < 1:
+        raise ValueError('none of the users has a held-out link')
+    dev = items.device
+    bounds = q_off.tolist()                 # (per user, once: the passes' slices of the query list)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    pos, rank, total, passes = [], [], 0, 0
+    for q0, cands, R in candidate_passes(model, dataset, sel_users, batch_size, exclude_seen, item_mask, users_per_pass):
+        m = cands.users.numel()
+        a, b = bounds[q0], bounds[q0 + m]
+        p, r = engine.rank_segments(R, cands.link_v[:len(cands)], cands.offsets, (q_off[q0:q0 + m + 1] - a).contiguous(),
+                                    items[a:b], err=err, lib=cands.lib)
+        pos.append(p)
+        rank.append(r)
+        total += len(cands)
+        passes += 1
+    pos, rank = torch.cat(pos), torch.cat(rank)
+    cnt, dcg = engine.rank_metrics(rank, q_off, ks, relevant, err=err, lib=dataset.graph.lib)
+    means = reduce_metrics(cnt, dcg, ks)
+    host = torch.cat([means, (pos < 0).sum().to(torch.float64).view(1), err.to(torch.float64)]).tolist()
+    if int(host[-1]):
+        engine._raise_rank_errors(err, 'rank_eval')
+    if stats is not None:
+        stats.update(users=sel_users.numel(), candidates=total, passes=passes, queries=items.numel(),
+                     not_candidates=int(host[-2]))
+    out = dict(zip(metric_names(ks), host[:-3]))
+    out['users_evaluated'] = int(host[-3])
+    out['per_user'] = dict(users=sel_users, offsets=q_off, items=items, relevant=relevant, cnt=cnt, dcg=dcg, rank=rank,
+                           pos=pos, index=index)
+    return out

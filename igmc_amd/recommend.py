@@ -260,20 +260,12 @@ def pass_plan(graph, n_users_requested, item_mask=None, users_per_pass=None):
     return upp, upp * worst
 
 
-def recommend(model, dataset, users=None, n=10, batch_size=50, exclude_seen=True, item_mask=None, users_per_pass=None,
-              stats=None):
-    """Ranked top-``n`` items for ``users`` (default: every user of the rating graph) over the rating graph and with the
-    extraction settings of ``dataset`` (normally the training set): ``(items int32 [nq, n], scores float32 [nq, n], counts
-    int32 [nq])``, device tensors, rows in the order of ``users``, -1 / 0 behind a user's count.
-
-    ``exclude_seen``: items the user has an entry for in the rating graph are no candidates.  ``item_mask``: bool / uint8
-    ``[n_items]``, candidates are drawn from its items only.  The work is done in passes of ``users_per_pass`` users
-    (:func:`pass_plan`); all passes refill ONE :class:`CandidateLinks` -- kept as ``dataset._recommend_links`` and reused by
-    later calls that fit it -- and therefore replay one captured ``ScoreGraph``.  Nothing per candidate crosses to the host:
-    one total per pass does.  Works for ``DGCNN_RS`` too (``score_links``' eager path).
-
-    Where a per-hop cap binds, scores depend on ``users_per_pass`` (see the module docstring: SAMPLER POSITIONS).
-    ``stats``: a dict that receives ``users``, ``candidates`` and ``passes``."""
+def candidate_passes(model, dataset, users=None, batch_size=50, exclude_seen=True, item_mask=None, users_per_pass=None):
+    """The pass loop of :func:`recommend` and of ``rank_eval.rank_eval``: ``users`` (default: every user of the rating graph)
+    in passes of ``users_per_pass`` (:func:`pass_plan`); a generator of ``(q0, cands, scores)`` -- the index of the pass's
+    first user in ``users``, the ONE :class:`CandidateLinks` every pass refills (kept as ``dataset._recommend_links`` and
+    reused by later calls that fit it, so every pass replays one captured ``ScoreGraph``) and the pass's scores
+    (:func:`score_candidates`).  ``cands`` is refilled by the next pass: take what you need from it before asking for it."""
     from . import train_eval
     if model.flat_parameters().device.type != train_eval.device.type:
         model.to(train_eval.device)
@@ -288,11 +280,29 @@ def recommend(model, dataset, users=None, n=10, batch_size=50, exclude_seen=True
     cands = getattr(dataset, '_recommend_links', None)
     if cands is None or cands.capacity < capacity or cands.source is not dataset:
         cands = dataset._recommend_links = CandidateLinks(dataset, capacity)
-    items, scores, counts, total = [], [], [], 0
     for q0 in range(0, nq, upp):
         cands.refill(users[q0:q0 + upp], exclude_seen, mask)
+        yield q0, cands, score_candidates(model, cands, batch_size)
+
+
+def recommend(model, dataset, users=None, n=10, batch_size=50, exclude_seen=True, item_mask=None, users_per_pass=None,
+              stats=None):
+    """Ranked top-``n`` items for ``users`` (default: every user of the rating graph) over the rating graph and with the
+    extraction settings of ``dataset`` (normally the training set): ``(items int32 [nq, n], scores float32 [nq, n], counts
+    int32 [nq])``, device tensors, rows in the order of ``users``, -1 / 0 behind a user's count.
+
+    ``exclude_seen``: items the user has an entry for in the rating graph are no candidates.  ``item_mask``: bool / uint8
+    ``[n_items]``, candidates are drawn from its items only.  The work is done in passes of ``users_per_pass`` users
+    (:func:`pass_plan`); all passes refill ONE :class:`CandidateLinks` -- kept as ``dataset._recommend_links`` and reused by
+    later calls that fit it -- and therefore replay one captured ``ScoreGraph`` (:func:`candidate_passes`).  Nothing per
+    candidate crosses to the host: one total per pass does.  Works for ``DGCNN_RS`` too (``score_links``' eager path).
+
+    Where a per-hop cap binds, scores depend on ``users_per_pass`` (see the module docstring: SAMPLER POSITIONS).
+    ``stats``: a dict that receives ``users``, ``candidates`` and ``passes``."""
+    items, scores, counts, total, nq = [], [], [], 0, 0
+    for _, cands, R in candidate_passes(model, dataset, users, batch_size, exclude_seen, item_mask, users_per_pass):
         total += len(cands)
-        R = score_candidates(model, cands, batch_size)
+        nq += cands.users.numel()
         i, s, c = top_n(cands, R, n)
         items.append(i)
         scores.append(s)

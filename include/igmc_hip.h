@@ -408,6 +408,50 @@ int64_t igmc_select_segments_scratch_bytes(int ns, int num, int geometry);
 int igmc_select_segments(const float* d_keys, const int64_t* d_seg_off, int ns, int num, int32_t* d_idx_out, float* d_key_out,
                          int32_t* d_count, void* d_scratch, int64_t scratch_bytes, int geometry, void* stream);
 
+/* ---- Where given ids stand in their segments, and the ranking metrics' per-segment sums (no reference counterpart: the
+ * reference judges rating regression only, by the test RMSE; by hand this is every candidate score pulled to the host and one
+ * `np.lexsort` per user).
+ *
+ * igmc_rank_segments: for the segments [d_seg_off[s], d_seg_off[s + 1]) of d_keys (float[n]) and d_ids (int32[n], STRICTLY
+ * ASCENDING inside every segment: the link_v of a candidate list), s < ns, 1 <= n < 2^31, and queries grouped by segment --
+ * segment s owns the queries [d_q_off[s], d_q_off[s + 1]) of d_q_id (int32[nq], in any order, duplicates allowed; d_q_off
+ * int64[ns + 1], d_q_off[0] = 0, d_q_off[ns] = nq, 0 <= nq < 2^31) --, per query q of segment s:
+ *   d_q_pos[q]  = the position IN d_keys (not in the segment) of the segment's entry with d_ids[position] == d_q_id[q];
+ *                 -1 when the segment has none (with candidate lists: an item the user has rated, or one masked out)
+ *   d_q_rank[q] = the number of entries of the segment that come BEFORE that entry in THE ORDER of igmc_select_segments (key
+ *                 descending, then position ascending; every NaN behind every number, NaNs among themselves by position;
+ *                 -0.0 == 0.0), i.e. its 0-based place in np.lexsort((idx, np.where(np.isnan(k), np.inf, -k))) -- querying
+ *                 the id at d_idx_out[s * num + r] of igmc_select_segments returns r; a NaN-keyed entry has a place like any
+ *                 other; -1 where d_q_pos[q] is -1
+ * geometry: 0 = chosen from ns as igmc_select_segments chooses, k in [1, 64] = k workgroups per segment, each counting one
+ * contiguous slice.  The counts are integers summed by vector atomic adds on d_q_rank: the result is a function of the inputs
+ * alone, whatever the geometry; no scratch.  d_err[0] (int32, ZEROED BY THE CALLER, read after the launches):
+ *   bit 0 = d_q_off is not 0 = q_off[0] <= q_off[1] <= ... <= q_off[ns] = nq: the queries cannot be told apart and EVERY query
+ *           gets -1 / -1;
+ *   bit 1 = a segment is not inside [0, n) (d_seg_off decreasing or out of range): it is taken as empty, its queries get
+ *           -1 / -1.
+ * Nothing is read outside the n entries of d_keys / d_ids or the nq queries and nothing is written outside the nq entries of
+ * d_q_pos / d_q_rank, whatever the offsets hold.  Nothing is allocated here, the three launches are capturable. */
+int igmc_rank_segments(const float* d_keys, const int32_t* d_ids, int64_t n, const int64_t* d_seg_off, int ns,
+                       const int64_t* d_q_off, const int32_t* d_q_id, int64_t nq, int32_t* d_q_pos, int32_t* d_q_rank,
+                       int32_t* d_err, int geometry, void* stream);
+/* igmc_rank_metrics: the per-segment (per-user) sums of the held-out ranking metrics with BINARY relevance, over the ranks
+ * igmc_rank_segments left.  A query COUNTS when d_q_rel[q] != 0 (uint8[nq]; NULL = every query is relevant) and
+ * d_q_rank[q] >= 0; a query without a place is left out, never counted as a miss.  d_ks: int32[nk] cut-offs K on the device,
+ * 1 <= nk <= 8, each K >= 1 (a K below 1 counts nothing).  For segment s < ns:
+ *   d_cnt[s * (2 + nk) + 0]     = n_rel, the queries that count
+ *   d_cnt[s * (2 + nk) + 1]     = first_rank, the smallest rank among them (-1 when n_rel = 0)
+ *   d_cnt[s * (2 + nk) + 2 + j] = hits_K = #{rank < K}                                        K = d_ks[j]
+ *   d_dcg[s * 2 * nk + j]       = dcg_K  = sum over {rank < K} of 1 / log2(rank + 2)          (float64)
+ *   d_dcg[s * 2 * nk + nk + j]  = idcg_K = sum over i < min(K, n_rel) of 1 / log2(i + 2)
+ * One wave per segment; the float64 sums are taken in a fixed order (lane l: the segment's queries l, l + 64, ..., then a
+ * fixed butterfly), so the output is bit-identical from launch to launch and for every grid (workgroups of the launch: 0 =
+ * chosen from ns, at most 65536).  A segment whose query range is not inside [0, nq] has no query and raises bit 0 of
+ * d_err[0] (int32, zeroed by the caller).  One launch, capturable. */
+int igmc_rank_metrics(const int32_t* d_q_rank, const int64_t* d_q_off, const uint8_t* d_q_rel /* may be NULL */, int64_t nq,
+                      int ns, const int32_t* d_ks, int nk, int32_t* d_cnt, double* d_dcg, int32_t* d_err, int grid,
+                      void* stream);
+
 /* Per-kernel timing of the last call (HIP events on the launch stream); names/ms arrays are
  * filled up to `cap` (ms = total over `calls` launches of that kernel since the last fetch);
  * returns the number of distinct kernels recorded, or <0 on error. */
