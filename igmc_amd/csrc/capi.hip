@@ -745,11 +745,13 @@ extern "C" int igmc_model_create(int device, int num_relations, int num_bases, i
   d.ts_stride = (d.R * 32 + 33) * 32;
   d.fin_stash = nullptr;
   d.datt_part = nullptr;
+  d.fold_w = nullptr;
   if (d.R <= G2_NR * G2_NG_MAX)
   {   // (sums + d att partials in ONE allocation: a data-parallel step exchanges them as one span)
     fail |= M.get(&d.ts_part, (size_t)4 * IGMC_TS_BLOCKS * d.ts_stride) |
             M.get(&d.ts_raw, (size_t)4 * d.ts_stride + (size_t)4 * d.ts_stride / 32 * 4);
     if (!fail) d.datt_part = d.ts_raw + (size_t)4 * d.ts_stride;
+    fail |= M.get(&d.fold_w, (size_t)4 * 32 * IGMC_FOLD_NA);      // hand-off words of the one-launch tail
   }
   if (d.R <= 128) fail |= M.get(&d.fin_stash, (size_t)4 * IGMC_STASH_LAYER + 16);     // weights-only stash of k_finalize_ts (both modes)
   d.g2_ex = nullptr;
@@ -819,6 +821,7 @@ extern "C" int igmc_model_create(int device, int num_relations, int num_bases, i
     const unsigned long long ts0[4] = {~0ull, 0ull, 0ull, 0ull};
     HIPCHECK(hipMemcpy(m->d.gs_ts, ts0, sizeof(ts0), hipMemcpyHostToDevice));
   }
+  if (m->d.fold_w) HIPCHECK(hipMemset(m->d.fold_w, 0, (size_t)4 * 32 * IGMC_FOLD_NA * sizeof(unsigned long long)));      // tag 0: never issued
   if (m->d.g2_ex) {
     HIPCHECK(hipMemset(m->d.g2_ex, 0, 5 * m->d.g2_ex_stride * sizeof(unsigned long long)));
     HIPCHECK(hipMemset(m->d.g2_fx, 0, (size_t)max_graphs * 256 * sizeof(unsigned long long)));
@@ -852,6 +855,21 @@ extern "C" int igmc_debug_head_array(const igmc_model* m, int which, float* h_ou
   if (n < 0 || n > (int64_t)m->d.graph_cap * (which < 2 ? 128 : m->d.D)) IGMC_FAIL("size out of range");
   HIPCHECK(hipDeviceSynchronize());
   HIPCHECK(hipMemcpy(h_out, src, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// debug aid (tests): host copy of the staged weight images + layer-0 table (g2_image.h) as the last step or compose left them;
+// h_out == NULL: *n_words alone.  Synchronises the device.
+extern "C" int igmc_debug_weight_images(const igmc_model* m, float* h_out, int64_t* n_words) {
+  if (!m || !n_words) IGMC_FAIL("null argument");
+  const int64_t n = m->d.g2_w ? (int64_t)g2_w_words(m->d.R, m->d.L) : 0;
+  if (h_out) {
+    if (*n_words < 0 || *n_words > n) IGMC_FAIL("size out of range");
+    HIPCHECK(hipDeviceSynchronize());
+    if (*n_words) HIPCHECK(hipMemcpy(h_out, m->d.g2_w, (size_t)*n_words * sizeof(float), hipMemcpyDeviceToHost));
+  } else {
+    *n_words = n;
+  }
   return 0;
 }
 
@@ -1190,6 +1208,8 @@ extern "C" int igmc_model_set_ctrl(igmc_model* m, const int64_t* d_ctrl) {
 extern "C" int igmc_model_reset_exchange(igmc_model* m, void* stream) {
   if (!m) IGMC_FAIL("null model");
   hipStream_t st = (hipStream_t)stream;
+  // (the tail's hand-off words carry the launch sequence number, which restarts with the flags)
+  if (m->d.fold_w) HIPCHECK(hipMemsetAsync(m->d.fold_w, 0, (size_t)4 * 32 * IGMC_FOLD_NA * sizeof(unsigned long long), st));
   if (m->d.g2_ex) {
     HIPCHECK(hipMemsetAsync(m->d.g2_ex, 0, 5 * m->d.g2_ex_stride * sizeof(unsigned long long), st));
     HIPCHECK(hipMemsetAsync(m->d.g2_fx, 0, (size_t)m->d.g2_graphs * 256 * sizeof(unsigned long long), st));
@@ -1207,8 +1227,9 @@ extern "C" int igmc_model_check(igmc_model* m, void* stream) {
       HIPCHECK(hipMemset(m->d.gs_bar, 0, (2 * (size_t)m->d.graph_cap + 1) * sizeof(int)));
       (void)igmc_model_reset_exchange(m, stream);        // (sequence number and flags restart together; partial rows gone)
       HIPCHECK(hipStreamSynchronize((hipStream_t)stream));
-      IGMC_FAIL("a workgroup-cluster exchange of k_graph_step2 timed out (GPU shared with another job?): results of the "
-                "affected steps are invalid; set IGMC_GS_CLUSTER=1 or IGMC_GRAPH_STEP=0");
+      IGMC_FAIL("a workgroup-cluster exchange of k_graph_step2 or a hand-off of the one-launch tail k_tail_fin timed out (GPU "
+                "shared with another job?): results of the affected steps are invalid; set IGMC_GS_CLUSTER=1 or "
+                "IGMC_GRAPH_STEP=0 (the tail alone: IGMC_TAIL_FOLD=0)");
     }
   }
   return 0;

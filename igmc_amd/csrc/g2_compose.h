@@ -123,7 +123,7 @@ static int igmc_g2_layout(const ModelDev& m, const BatchDev& b, int cs, G2Layout
   lay->att = o; o += 64;
   lay->head = o; o += 256 + 256 + 3 * 128 + 512 + 16;
   lay->words = o;
-  return (size_t)o * 4 <= 160 * 1024;
+  return (size_t)o * 4 + 768 <= 160 * 1024;      // (+ the static LDS of the appended stash role: fin_stash_body, 736 bytes)
 }
 
 // The plane exchange of k_graph_step2 goes through the L2 of ONE XCD: workgroups b and b + 8 of a launch must sit on the
@@ -169,7 +169,7 @@ int g_igmc_compose_count = 0;      // launches of k_g2_compose so far (capi.hip:
 
 int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
                             int use_flags, const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float grad_scale,
-                            float* out, void* stream) {
+                            float* out, void* stream, int nstash, const int64_t* stash_ctrl) {
   const G2Layout& lay = sp.lay;
   const int cs = sp.cs;
   G2Args a;
@@ -199,7 +199,17 @@ int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan
   a.self_seq = (!training || a.ts) ? 1 : 0;
   a.cs = cs;
   a.stride = (cs > 1) ? ((B + 7) & ~7) : 1;
-  const int grid = sp.grid;      // (clusters in XCD-aligned blocks of 8 cs workgroups)
+  if (training && nstash) {      // the one-launch tail follows: its stash role rides behind the cluster workgroups
+    a.nstash = nstash;
+    a.stash_ctrl = stash_ctrl;
+    a.fs.R = m.R; a.fs.L = m.L;
+    for (int l = 0; l < 4; ++l) {
+      a.fs.off_basis[l] = m.off_basis[l];
+      a.fs.off_att[l] = m.off_att[l];
+    }
+    a.fs.fin_stash = m.fin_stash; a.fs.adam_m1 = m.adam_m1; a.fs.adam_m2 = m.adam_m2; a.fs.arr_part = m.arr_part;
+  }
+  const int grid = sp.grid + a.nstash;      // (clusters in XCD-aligned blocks of 8 cs workgroups [+ the stash role])
   const size_t sm = (size_t)lay.words * 4;
   if (!m.img_current) {
     IGMC_PLAUNCH("k_g2_compose", k_g2_compose, 2 * 3 * g2_groups(m.R, m.L) * (G2_NR + 1) + g2_t0_rows(m.R, m.L) / 32, G2C_THREADS, 0, stream, m, P, m.g2_w);
@@ -231,8 +241,13 @@ int igmc_g2_prepare() {
                         (const void*)k_graph_step2<true, false, true>,  (const void*)k_graph_step2<false, false, true>,
                         (const void*)k_graph_step2<true, true, false>,  (const void*)k_graph_step2<false, true, false>,
                         (const void*)k_graph_step2<true, false, false>, (const void*)k_graph_step2<false, false, false>};
-  for (const void* fn : fns)
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) return 1;
+  for (const void* fn : fns) {
+    // (the limit is on static + dynamic LDS: the training forms carry the stash role's static arrays, which
+    //  igmc_g2_layout leaves room for)
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, fn) != hipSuccess || (int)fa.sharedSizeBytes > 768) return 1;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, mx - (int)fa.sharedSizeBytes) != hipSuccess) return 1;
+  }
 #endif
   return 0;
 }

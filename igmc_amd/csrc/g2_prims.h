@@ -114,19 +114,7 @@ __device__ __forceinline__ void g2_glds16(const float4* src_wave, float4* lds_wa
 #endif
 }
 
-// ---- the readout words of the subgraph kernel: 8-byte {f32, tag}, polled ------------------------------------------------
-// (an ORDINARY 8-byte store: its readers -- g2_poll_f32, sc1 loads -- sit on the writer's XCD and find it in the shared L2
-//  ~250 ns after issue; written through to memory with sc1 it took ~570 ns, profiles/r05_experiments/xcd_oneway.txt)
-__device__ __forceinline__ void g2_pub_f32(unsigned long long* p, float v, uint32_t tag) {
-#ifndef IGMC_HIPEMU
-  __hip_atomic_store(p, ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_WAVEFRONT);
-#else
-  uint32_t bits;
-  memcpy(&bits, &v, 4);
-  *p = ((unsigned long long)tag << 32) | (unsigned long long)bits;
-#endif
-}
+#include "g2_words.h"      // the 8-byte {f32, tag} words: g2_pub_f32 / g2_poll_f32
 
 // ---- plane exchange of the subgraph kernel (k_graph_step2) ------------------------------------------------------------
 // The members of a cluster sit on ONE XCD (graphstep2.hip: workgroup -> (subgraph, member)), so the rows they exchange can
@@ -192,27 +180,6 @@ __device__ __forceinline__ void g2_planes_load_exact(uint32_t* pl, const unsigne
 __device__ __forceinline__ void g2_planes_load(uint32_t* pl, const unsigned char* px, int kp, int wave, int lane, int nwaves) {
   const int pieces = (192 * kp + 1023) >> 10;
   for (int c = wave; c < pieces; c += nwaves) g2_glds16<16>((const float4*)px + c * 64, (float4*)pl + c * 64, lane);
-}
-
-// one 8-byte {f32, tag} word, polled
-__device__ __forceinline__ float g2_poll_f32(const unsigned long long* p, uint32_t tag, int* err) {
-  for (long it = 0;; ++it) {
-#ifndef IGMC_HIPEMU
-    const unsigned long long w = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    const unsigned long long w = *p;
-#endif
-    if ((uint32_t)(w >> 32) == tag) return __uint_as_float((uint32_t)w);
-    if (it > (1L << 22)) {
-      *err = 1;
-      return 0.f;
-    }
-#ifndef IGMC_HIPEMU
-    __builtin_amdgcn_s_sleep(2);
-#else
-    hipemu::yield();
-#endif
-  }
 }
 
 #ifdef IGMC_HIPEMU

@@ -41,6 +41,11 @@ struct G2Args {
   unsigned long long* ts;
   int timing, cs, stride, self_seq;
   G2Layout lay2;
+  // the stash role of the one-launch tail (k_tail_fin), which updates the parameters in place and so cannot form the
+  // weights-only quantities itself: the LAST nstash (0 or 4) workgroups of the launch, one per conv layer (fin_stash.h)
+  int nstash;
+  const int64_t* stash_ctrl;   // control block the step's Adam scalars come from (or NULL: they are kernel arguments)
+  FinStashModel fs;
 };
 
 // ONCE: a workgroup takes exactly one subgraph (clusters, cs > 1: every product launch) -- the body is then STRAIGHT-LINE code.
@@ -97,6 +102,31 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
   if (a.timing && tid == 0 && blockIdx.x < 1024) {
     g_g2_wg[blockIdx.x][0] = g2_wall_clock();
     g_g2_wg[blockIdx.x][2] = g2_xcc_id();
+  }
+  // The launch sequence number (exchange tags) advances once per launch, after every workgroup has read it: a training
+  // launch leaves that to the next kernel on the stream (one store) unless a.self_seq says otherwise; else the
+  // workgroup that finishes LAST does it (an atomic round trip at the end of every workgroup).
+  auto arrive = [&]() {
+    if (tid == 0 && a.self_seq) {
+      const unsigned long long t1 = a.ts ? g2_wall_clock() : 0ull;
+      if (g2_last_workgroup_advances(a.gs_bar) && a.ts) g2_clock_close(a.ts, t1);
+    }
+  };
+  const int nwork = (int)gridDim.x - (TRAIN ? a.nstash : 0);      // workgroups that take subgraphs
+  if (TRAIN && (int)blockIdx.x >= nwork) {
+    // stash role: the first four waves (the role is written for IGMC_BLOCK threads), no exchange region touched; layer 0's
+    // also leaves the sequence number of this launch, the tag of the tail's hand-off words (no workgroup of THAT launch
+    // writes it, and the tail's last workgroup advances the number itself)
+    // NOTE: fin_stash_body holds a __syncthreads() that only waves 0..3 reach.  That is sound ONLY because waves 4..7 do nothing
+    // but arrive() (no barrier in it) and end -- an ended wave leaves the barrier's count.  Nothing with a barrier, and nothing
+    // that waits for waves 0..3, may be put on the upper waves' path.
+    if (tid < IGMC_BLOCK) {
+      const int l = (int)blockIdx.x - nwork;
+      fin_stash_body(a.fs, P, l, a.stash_ctrl);
+      if (l == 0 && tid == 0) a.fs.fin_stash[IGMC_STASH_SCAL + IGMC_STASH_SEQ] = __uint_as_float(seq);
+    }
+    arrive();
+    return;
   }
 
   // ---- the first subgraph's extents are requested before anything else (two dependent round trips overlap with
@@ -735,7 +765,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
       __syncthreads();
       G2_STAMP(34);
     }
-  } while (!ONCE && (g += (int)gridDim.x) < B);
+  } while (!ONCE && (g += nwork) < B);
 
   if (TRAIN && wave < 4) {
     float* part0 = a.ts_part + (size_t)tslot * ts;             // slice 0 of [4][IGMC_TS_BLOCKS][ts]
@@ -746,13 +776,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
       if (c < RL + L + 1) part0[c * 32 + wn * 16 + li] = acc0[rr];
     }
   }
-  // The launch sequence number (exchange tags) advances once per launch, after every workgroup has read it: a training
-  // launch leaves that to the next kernel on the stream (k_tail_ts, one store) unless a.self_seq says otherwise; else the
-  // workgroup that finishes LAST does it here (an atomic round trip at the end of every workgroup).
-  if (tid == 0 && a.self_seq) {
-    const unsigned long long t1 = a.ts ? g2_wall_clock() : 0ull;
-    if (g2_last_workgroup_advances(a.gs_bar) && a.ts) g2_clock_close(a.ts, t1);
-  }
+  arrive();      // (the launch sequence number: above)
   G2_STAMP(35);
   if (a.timing && tid == 0 && blockIdx.x < 1024) g_g2_wg[blockIdx.x][1] = g2_wall_clock();
 }

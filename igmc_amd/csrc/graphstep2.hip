@@ -40,6 +40,7 @@
 #include "launch.h"
 #include "g2_image.h"
 #include "head_sub.h"
+#include "fin_stash.h"
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>

@@ -131,7 +131,7 @@ int igmc_g2_prepare();
 #define IGMC_FAM_DLF 2       // the one-launch dense layers (k_dl_fwd)
 #define IGMC_FAM_DL 3        // the per-layer dense layers (k_dl_layer0 / k_dl_layer)
 #define IGMC_TAIL_HANDOFF 0  // gradient / Adam tail: k_finalize (in-kernel hand-offs)
-#define IGMC_TAIL_TS 1       // ... k_tail_ts -> k_finalize_ts on relation-space tables
+#define IGMC_TAIL_TS 1       // ... k_tail_ts -> k_finalize_ts on relation-space tables (or both in one launch: StepPlan::tail_fold)
 #define IGMC_TAIL_BS 2       // ... k_finalize_ts on the reduced basis-space sums
 struct StepPlan {
   int kind;                  // IGMC_CALL_*
@@ -149,6 +149,8 @@ struct StepPlan {
   int need_y;                // the forward leaves the Y products behind (k_dense_y_all)
   int tail;                  // IGMC_TAIL_*
   int exchange_inside;       // the step keeps its gradient sources in exchangeable form (StepExchange)
+  int tail_fold;             // subgraph kernel, IGMC_TAIL_TS: a single-GPU step with Adam and weight images runs the tail as ONE launch
+                             // (k_tail_fin; its stash role rides in the subgraph kernel's launch) -- IGMC_TAIL_FOLD=0: never
   int needs_csr;             // some kernel of the call reads the collated CSR (a lean arena must emit it first)
   int dense_layers;          // the dense-layer kernels take this arena (igmc_model_dense_layers)
   int step_form;             // igmc_model_step_form
@@ -174,9 +176,10 @@ void igmc_launch_head_sub(const ModelDev& m, const BatchDev& b, const float* P, 
                           uint64_t step, float mult, float grad_scale, float* out, void* stream);
 void igmc_launch_dl_layer(const ModelDev& m, const BatchDev& b, const float* P, int B, int l, int bwd, int use_flags,
                           float* zero_out, void* stream, int tables = 0);
+// (stash_ctrl / nstash = 4: four more workgroups behind sp.grid run the stash role of the one-launch tail that follows)
 int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
                             int use_flags, const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float grad_scale,
-                            float* out, void* stream);
+                            float* out, void* stream, int nstash = 0, const int64_t* stash_ctrl = nullptr);
 
 // ---- per-kernel timing (HIP events on the launch stream; bench.py's roofline leg) ----
 void igmc_prof_begin(const char* name, void* stream);

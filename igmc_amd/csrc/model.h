@@ -7,6 +7,7 @@
 #define IGMC_WG_BLOCKS 64    // grid.x of the weight-gradient kernel (per-block partials, per layer); 128: ml_100k +1.7 %, flixster -2 %; 32: +9 us in the products
 #endif
 #define IGMC_STASH_LAYER 672  // floats per conv layer of the weights-only stash (fin_stash; layout: model.hip)
+#define IGMC_FOLD_NA 32       // d att entries a layer of the one-launch tail (k_tail_fin) hands over: 4 R <= 32
 #define IGMC_TS_BLOCKS 256   // partial slots of the relation-space tables (one per workgroup of k_graph_step)
 #define IGMC_GATHER_BLOCKS 4096   // max grid of the row-walker kernels (4 rows = 4 waves per block)
 // The basis-space mode of the gradient / Adam tail (k_finalize_ts) is correct up to 128 relations (the stash holds them) but only pays up to 32: its per-relation
@@ -43,8 +44,11 @@ struct ModelDev {
   float* ts_raw;      // [4][ts_stride] their sum over the workgroups
   int ts_stride;      // (R*32 + 33) * 32
   float* fin_stash;   // [4][IGMC_STASH_LAYER] per conv layer: Gram of the bases [0..15], ARR matrix M [16..31], att moments [32..160), att copy [160..160+R*4);
-                      // then [16] Adam scalars of the step -- written by k_tail_ts, read by k_finalize_ts (or NULL)
+                      // then [16] scalars of the step: [0..5] Adam's, [8] launch sequence number (bits; k_graph_step2's stash role) --
+                      // written by the stash role, read by k_finalize_ts / k_tail_fin (or NULL)
   float* datt_part;   // [4*ts_stride/32][4] partial <dW_r, basis_b> products of 32 table elements (k_tail_ts)
+  unsigned long long* fold_w;  // [4 layers][32 input rows][IGMC_FOLD_NA] {f32, tag} words: the same partial products as they cross
+                               // the workgroups of the one-launch tail (k_tail_fin); tag 0 is never a launch's (or NULL)
   int* gs_bar;        // k_graph_step clusters: [0] workgroups that finished the launch, [1] launch sequence number
   int* gs_err;        // [1] set when a cluster exchange timed out
   unsigned long long* gs_ts;   // [4] device-side launch clock of k_graph_step (igmc_profile_enable(2)): [0] earliest workgroup

@@ -23,6 +23,8 @@
 //     each (blockIdx.y = layer), and loss / epoch-total / control-block tick ride in the Adam kernel.
 #include "model.h"
 #include "g2_image.h"
+#include "fin_stash.h"      // layout of the weights-only stash (IGMC_STASH_*) and the role that fills it
+#include "g2_words.h"       // {f32, tag} words (the one-launch tail's hand-off)
 #include <stdlib.h>
 
 // ---- XCD affinity -------------------------------------------------------------------------------------
@@ -1264,7 +1266,6 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_wgrad_head(BatchDev b, ModelDev 
 // graw layout: [3][5152] conv1..3 (32x160 + 32) | [3][R*4] d att | [(R*L+L+1)*32] layer-0 table
 // Sections A (weight-gradient partials) and C (layer-0 tables): 64 outputs x 4 partial-slices per block;
 // section B (d att, few outputs x many partials): one wave per output.  Fixed summation order.
-__device__ __forceinline__ void fin_stash_body(const ModelDev& m, const float* __restrict__ P, int l, const int64_t* ctrl);
 
 // nstash = 4: four extra workgroups stash the weights-only quantities of the conv layers for k_finalize_ts (basis-space
 // mode), like the stash role of k_tail_ts.
@@ -1354,6 +1355,25 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_reduce_partials(ModelDev m, int 
   }
 }
 
+// The partial-table slots a launch filled, in the order their sums take them: member c of subgraph g sits in slot g + c * stride
+// (one-workgroup launches: stride = IGMC_TS_BLOCKS, one member); the valid slots in the order (c, g) are numbered q = c * ng + g
+struct TsSlots {
+  int ng, nq, stride;
+};
+__device__ __forceinline__ TsSlots ts_slots(int nparts, int stride, int B) {
+  TsSlots s;
+  s.ng = (nparts < stride) ? nparts : ((B < stride) ? B : stride);
+  s.nq = ((nparts + stride - 1) / stride) * s.ng;
+  s.stride = stride;
+  return s;
+}
+// slot of q (clamped to the last valid one: loads past the end are requested and not added)
+__device__ __forceinline__ int ts_slot(const TsSlots& s, int q) {
+  const int qc = q < s.nq ? q : s.nq - 1;
+  const int c = qc / s.ng, g = qc - c * s.ng;
+  return c * s.stride + g;
+}
+
 // relation-space tables of graphstep.hip: ts_raw[l][i] = sum over the workgroups' partials (fixed order);
 // 64 outputs per block, the 4 waves split the partial slices
 // Pold != NULL: wave 0 also forms, per 32 consecutive outputs (always inside one dW_r block: ts_stride and fin*32 are
@@ -1388,19 +1408,13 @@ __device__ __forceinline__ void reduce_ts_body(const ModelDev& m, int nparts, in
   }
   float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
   if (ok4) {
-    // slot of member c of subgraph g = g + c * stride (one-workgroup launches: stride = IGMC_TS_BLOCKS, cs = 1); the valid
-    // slots in the order (c, g) are numbered q = c * ng + g
     const float* p = m.ts_part + (size_t)l * IGMC_TS_BLOCKS * ts + i0;
-    const int ng = (nparts < stride) ? nparts : ((B < stride) ? B : stride), cs = (nparts + stride - 1) / stride;
-    const int nq = cs * ng;
+    const TsSlots sl = ts_slots(nparts, stride, B);
+    const int nq = sl.nq;
     for (int q0 = pg; q0 < nq; q0 += 16 * 14) {
       float4 v[14];
 #pragma unroll
-      for (int u = 0; u < 14; ++u) {
-        const int q = q0 + 16 * u, qc = q < nq ? q : nq - 1;
-        const int c = qc / ng, g = qc - c * ng;
-        v[u] = *(const float4*)(p + (size_t)(c * stride + g) * ts);
-      }
+      for (int u = 0; u < 14; ++u) v[u] = *(const float4*)(p + (size_t)ts_slot(sl, q0 + 16 * u) * ts);
 #pragma unroll
       for (int u = 0; u < 14; ++u)
         if (q0 + 16 * u < nq) {
@@ -1434,118 +1448,6 @@ __device__ __forceinline__ void reduce_ts_body(const ModelDev& m, int nparts, in
   }
 }
 
-// Weights-only quantities of conv layer l for k_finalize_ts, formed while the tables are being reduced: Gram matrix of
-// the bases, ARR matrix M[b][b'] = sum_r att[r,b] c[r,b'], the ARR value, a copy of att (k_finalize_ts updates att in
-// place while other workgroups still need the old values) and, from the control block, the Adam scalars of the step.
-#define IGMC_STASH_G 0
-#define IGMC_STASH_M 16
-#define IGMC_STASH_ATTM1 32       // Adam moments of att before the step (R <= 16; k_finalize_ts with img: every workgroup of
-#define IGMC_STASH_ATTM2 96       // the layer forms the new att, while the owner updates the moments in place)
-#define IGMC_STASH_ATT 160        // copy of att: R <= 128
-// (IGMC_STASH_LAYER floats per layer: model.h)
-#define IGMC_STASH_SCAL (4 * IGMC_STASH_LAYER)
-__device__ __forceinline__ void fin_stash_body(const ModelDev& m, const float* __restrict__ P, int l,
-                                               const int64_t* ctrl) {
-  __shared__ float sg10[4][10];
-  __shared__ float sG[16];
-  __shared__ float s_att[128];                       // att[r][b] of the layer (R <= 32: else read from HBM where needed)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nE = ((l == 0) ? m.L : 32) * 32, R = m.R, na = R * 4;
-  const float* basis = P + m.off_basis[l];
-  const float* attg = P + m.off_att[l];
-  float* st = m.fin_stash + l * IGMC_STASH_LAYER;
-  // Every load of the role is requested HERE, before the first use: att, the thread's (<= 4) elements of the four bases, att's
-  // Adam moments, the step's scalars.  Left inside the loops below they were a dozen dependent round trips -- the longest
-  // chain of the whole k_tail_ts launch.
-  const bool small = na <= 128;
-  const float attv = (small && tid < na) ? attg[tid] : 0.f;
-  float bq[4][4];
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int e = tid + it * IGMC_BLOCK, ec = e < nE ? e : nE - 1;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) bq[it][q] = (e < nE) ? basis[q * nE + ec] : 0.f;
-  }
-  float m1v = 0.f, m2v = 0.f;
-  const bool mom = m.adam_m1 && na <= 64 && tid >= 128 && tid < 128 + na;
-  if (mom) {
-    m1v = m.adam_m1[m.off_att[l] + tid - 128];
-    m2v = m.adam_m2[m.off_att[l] + tid - 128];
-  }
-  double scal = 0.0;
-  const bool sc = l == 0 && ctrl && tid >= 192 && tid < 198;
-  if (sc) {
-    const double* d = (const double*)ctrl;
-    const int k = tid - 192;
-    const int src = (k == 0) ? IGMC_CTRL_STEP_SIZE : (k == 1) ? IGMC_CTRL_INV_SQRT_BC2 : (k == 2) ? IGMC_CTRL_BETA1
-                  : (k == 3) ? IGMC_CTRL_BETA2 : (k == 4) ? IGMC_CTRL_EPS : IGMC_CTRL_WD;
-    scal = d[src];
-  }
-  if (small && tid < na) s_att[tid] = attv;
-  float gp[10];
-#pragma unroll
-  for (int q = 0; q < 10; ++q) gp[q] = 0.f;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {                     // (element order per thread as before: e = tid, tid + 256, ..)
-    if (tid + it * IGMC_BLOCK < nE) {
-      const float b0 = bq[it][0], b1 = bq[it][1], b2 = bq[it][2], b3 = bq[it][3];
-      gp[0] += b0 * b0; gp[1] += b0 * b1; gp[2] += b0 * b2; gp[3] += b0 * b3;
-      gp[4] += b1 * b1; gp[5] += b1 * b2; gp[6] += b1 * b3;
-      gp[7] += b2 * b2; gp[8] += b2 * b3; gp[9] += b3 * b3;
-    }
-  }
-  for (int e = tid + 4 * IGMC_BLOCK; e < nE; e += IGMC_BLOCK) {      // (nE <= 1024: never)
-    const float b0 = basis[e], b1 = basis[nE + e], b2 = basis[2 * nE + e], b3 = basis[3 * nE + e];
-    gp[0] += b0 * b0; gp[1] += b0 * b1; gp[2] += b0 * b2; gp[3] += b0 * b3;
-    gp[4] += b1 * b1; gp[5] += b1 * b2; gp[6] += b1 * b3;
-    gp[7] += b2 * b2; gp[8] += b2 * b3; gp[9] += b3 * b3;
-  }
-#pragma unroll
-  for (int q = 0; q < 10; ++q) gp[q] = igmc_wave_sum_f(gp[q]);
-  if (lane == 0) {
-#pragma unroll
-    for (int q = 0; q < 10; ++q) sg10[wave][q] = gp[q];
-  }
-  __syncthreads();                                   // s_att, sg10
-  const float* att = small ? (const float*)s_att : attg;
-  if (tid >= 64 && tid < 80) {           // M[b][b'] = sum_r att[r,b] c[r,b'],  c[r] = 2 (d[r-1] - d[r]),  d[r] = att[r+1]-att[r]
-    const int bb = (tid - 64) >> 2, bp = tid & 3;
-    float sacc = 0.f;
-    for (int r = 0; r < R; ++r) {
-      const float dm = (r > 0) ? att[r * 4 + bp] - att[(r - 1) * 4 + bp] : 0.f;
-      const float dn = (r + 1 < R) ? att[(r + 1) * 4 + bp] - att[r * 4 + bp] : 0.f;
-      sacc += att[r * 4 + bb] * 2.f * (dm - dn);
-    }
-    st[IGMC_STASH_M + tid - 64] = sacc;
-  }
-  if (tid >= 128 && na <= IGMC_STASH_LAYER - IGMC_STASH_ATT) {
-    for (int i = tid - 128; i < na; i += IGMC_BLOCK - 128) {
-      st[IGMC_STASH_ATT + i] = att[i];
-      if (m.adam_m1 && na <= 64) {
-        st[IGMC_STASH_ATTM1 + i] = mom && i == tid - 128 ? m1v : m.adam_m1[m.off_att[l] + i];
-        st[IGMC_STASH_ATTM2 + i] = mom && i == tid - 128 ? m2v : m.adam_m2[m.off_att[l] + i];
-      }
-    }
-  }
-  if (sc) m.fin_stash[IGMC_STASH_SCAL + tid - 192] = (float)scal;
-  if (tid == 0) {
-    const int ij[10][2] = {{0, 0}, {0, 1}, {0, 2}, {0, 3}, {1, 1}, {1, 2}, {1, 3}, {2, 2}, {2, 3}, {3, 3}};
-    for (int q = 0; q < 10; ++q) {
-      const float v = (sg10[0][q] + sg10[1][q]) + (sg10[2][q] + sg10[3][q]);
-      sG[ij[q][0] * 4 + ij[q][1]] = v;
-      sG[ij[q][1] * 4 + ij[q][0]] = v;
-    }
-    float reg = 0.f;                       // reg = sum_r d[r]^T Gm d[r]   (reference train_eval.py:167-174)
-    for (int r = 0; r + 1 < R; ++r) {
-      float d[4];
-      for (int q = 0; q < 4; ++q) d[q] = att[(r + 1) * 4 + q] - att[r * 4 + q];
-      for (int p1 = 0; p1 < 4; ++p1)
-        for (int p2 = 0; p2 < 4; ++p2) reg += d[p1] * sG[p1 * 4 + p2] * d[p2];
-    }
-    m.arr_part[l] = reg;
-    for (int q = 0; q < 16; ++q) st[IGMC_STASH_G + q] = sG[q];
-  }
-}
 
 // Both consumers of k_graph_step's outputs in ONE launch (they are independent of each other): the first `nlin`
 // workgroups form d lin1 / d lin2 (batched product over the subgraphs), the others sum the relation-space tables.
@@ -1588,7 +1490,7 @@ __device__ __forceinline__ void ctrl_check_and_advance(int64_t* ctrl, const Batc
   int bad = 0;
   if (got >= 0 && got != want) bad |= 2;
   if (use_flags && got >= 0 && b.stamp[1] >= 0 && (uint64_t)b.stamp[1] != igmc_ctrl_drop_key(ctrl, (int)want)) bad |= 4;
-  if (bad) ctrl[IGMC_CTRL_SYNC_ERR] |= bad;
+  if (bad) atomicOr((unsigned long long*)(ctrl + IGMC_CTRL_SYNC_ERR), (unsigned long long)bad);      // (k_tail_fin: other workgroups of the launch may raise their bit)
   ctrl_advance(ctrl);
 }
 
@@ -1622,6 +1524,35 @@ __device__ __forceinline__ void adam_elem(float* __restrict__ p, const float* __
   p[i] = pi - step_size * a / (sqrtf(v) * inv_sqrt_bc2 + eps);
 }
 
+// ... of an element whose gradient, parameter and moments are in registers already
+__device__ __forceinline__ void adam_store(float* p, float* m1, float* m2, int64_t i, float gi, float pv, float av, float vv,
+                                           float step_size, float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd) {
+  if (wd != 0.f) gi += wd * pv;
+  const float a = beta1 * av + (1.f - beta1) * gi;
+  const float v = beta2 * vv + (1.f - beta2) * gi * gi;
+  m1[i] = a;
+  m2[i] = v;
+  p[i] = pv - step_size * a / (sqrtf(v) * inv_sqrt_bc2 + eps);
+}
+
+// The same step with the two products of each moment rounded SEPARATELY (no fused multiply-add): the form of every walk over
+// the lin parameters -- adam_range and the lin role of k_tail_fin, which visits the same elements in its own order.  Left to
+// the compiler, a * b + c * d becomes two packed multiplies and an add in one caller and an fma in another (it depends on the
+// unroll count): a last-bit difference in the moments between kernels that must leave the same bits.
+__device__ __forceinline__ void adam_store_sep(float* p, float* m1, float* m2, int64_t i, float gi, float pv, float av, float vv,
+                                               float step_size, float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd) {
+  if (wd != 0.f) gi += wd * pv;
+  float a, v;
+  {
+#pragma clang fp contract(off)
+    a = beta1 * av + (1.f - beta1) * gi;
+    v = beta2 * vv + (1.f - beta2) * gi * gi;
+  }
+  m1[i] = a;
+  m2[i] = v;
+  p[i] = pv - step_size * a / (sqrtf(v) * inv_sqrt_bc2 + eps);
+}
+
 // Adam on [lo, hi) by one workgroup: NB elements per thread and round, all 4 NB loads requested before the first use
 // (the element-by-element loop pays one memory round trip per element: the stores of element k keep the compiler from
 // requesting element k + 1 early)
@@ -1643,15 +1574,7 @@ __device__ __forceinline__ void adam_range(float* p, const float* g, float* m1, 
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
       const int64_t i = i0 + (int64_t)k * IGMC_BLOCK;
-      if (i < hi) {
-        float gi = gv[k];
-        if (wd != 0.f) gi += wd * pv[k];
-        const float a = beta1 * av[k] + (1.f - beta1) * gi;
-        const float v = beta2 * vv[k] + (1.f - beta2) * gi * gi;
-        m1[i] = a;
-        m2[i] = v;
-        p[i] = pv[k] - step_size * a / (sqrtf(v) * inv_sqrt_bc2 + eps);
-      }
+      if (i < hi) adam_store_sep(p, m1, m2, i, gv[k], pv[k], av[k], vv[k], step_size, inv_sqrt_bc2, beta1, beta2, eps, wd);
     }
   }
 }
@@ -1891,6 +1814,90 @@ __device__ __forceinline__ float fts_emit(float* __restrict__ grad, const AdamTa
   return pnew;
 }
 
+// ---- the roles of a conv layer's tail, shared by k_finalize_ts and the one-launch tail k_tail_fin: ONE body each, so that the
+//      two kernels form every gradient, moment, parameter and image word with the same operations in the same order
+// d att[r,b] (entry rb) from the sum g of its fin partial products: + ARR term, then the update; returns att[r,b] after the step
+__device__ __forceinline__ float fts_att_entry(float* __restrict__ grad, const AdamTail& at, const float* st, int R, int rb,
+                                               float g, float arr_coef, int64_t i, float pold, float m1o, float m2o, bool store) {
+  const int r = rb >> 2, bb = rb & 3;
+  if (arr_coef != 0.f) {
+    float sacc = 0.f;
+    for (int bp = 0; bp < 4; ++bp) {
+      const float a0 = st[IGMC_STASH_ATT + r * 4 + bp];
+      const float dm = (r > 0) ? a0 - st[IGMC_STASH_ATT + (r - 1) * 4 + bp] : 0.f;
+      const float dn = (r + 1 < R) ? st[IGMC_STASH_ATT + (r + 1) * 4 + bp] - a0 : 0.f;
+      sacc += 2.f * (dm - dn) * st[IGMC_STASH_G + bp * 4 + bb];
+    }
+    g += arr_coef * sacc;
+  }
+  return fts_emit(grad, at, i, g, pold, m1o, m2o, store);
+}
+// column (c, f) of a layer: d basis_b[c][f] += sum_{r < min(R, 8)} att[r,b] dW_r[c][f] from the column's table values
+__device__ __forceinline__ void fts_col_table8(float (&g)[5], const float* st, const float (&tv)[8], int R) {
+#pragma unroll
+  for (int r = 0; r < 8; ++r)
+    if (r < R) {
+#pragma unroll
+      for (int bb = 0; bb < 4; ++bb) g[bb] += st[IGMC_STASH_ATT + r * 4 + bb] * tv[r];
+    }
+}
+// ... + ARR term, then the update of basis_0..3[c][f] and root[c][f]; pn: their values after the step
+__device__ __forceinline__ void fts_col_emit(float* __restrict__ grad, const AdamTail& at, const float* st, float arr_coef,
+                                             const int64_t (&idx)[5], float (&g)[5], const float (&pv)[5], const float (&m1v)[5],
+                                             const float (&m2v)[5], float (&pn)[5]) {
+  if (arr_coef != 0.f) {
+    // (the roundings of  g += arr_coef (M0 p0 + M1 p1 + M2 p2 + M3 p3)  are spelled out: left to the compiler, the sum came out
+    //  as an fma chain in one kernel and as four products and three adds in another -- last bits of every basis gradient.  This
+    //  is the chain k_finalize_ts has always computed: M1 p1 rounded, the other three products fused)
+#pragma unroll
+    for (int bb = 0; bb < 4; ++bb) {
+      float t = fmaf(st[IGMC_STASH_M + bb * 4 + 0], pv[0], st[IGMC_STASH_M + bb * 4 + 1] * pv[1]);
+      t = fmaf(st[IGMC_STASH_M + bb * 4 + 2], pv[2], t);
+      t = fmaf(st[IGMC_STASH_M + bb * 4 + 3], pv[3], t);
+      g[bb] = fmaf(arr_coef, t, g[bb]);
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 5; ++q) pn[q] = fts_emit(grad, at, idx[q], g[q], pv[q], m1v[q], m2v[q]);
+}
+// weight-image words of column (c, f) after the step, relations r0, r0 + rstep, .. (R = the root): layer 0 -> its rows of the
+// layer-0 table [W_0[r * L + c] | root_0[c] | bias_0] (rows past R L + L stay zero: first compose); layers 1..3 -> forward
+// image element (k = c, n = f) and transposed image element (k = f, n = c): relation r -> block r % G2_NR of group r / G2_NR,
+// root -> block G2_NR of group 0 (blocks of relations the model does not have stay zero: first compose)
+__device__ __forceinline__ void fts_image_col(const ModelDev& m, int ng, int l, int R, int fin, int c, int f, const float* s_attn,
+                                              const float (&pn)[5], int r0, int rstep) {
+  if (l == 0) {
+    float* t0w = m.g2_w + g2_t0_off(ng);
+    for (int r = r0; r <= R; r += rstep)
+      t0w[(r * fin + c) * 32 + f] = (r == R) ? pn[4]
+                                  : g2_wsum(s_attn[r * 4], s_attn[r * 4 + 1], s_attn[r * 4 + 2], s_attn[r * 4 + 3], pn[0], pn[1], pn[2], pn[3]);
+  } else {
+#pragma unroll 3
+    for (int r = r0; r <= R; r += rstep) {
+      const float v = (r == R) ? pn[4]
+                    : g2_wsum(s_attn[r * 4], s_attn[r * 4 + 1], s_attn[r * 4 + 2], s_attn[r * 4 + 3], pn[0], pn[1], pn[2], pn[3]);
+      const int grp = (r == R) ? 0 : r / G2_NR, blk = (r == R) ? G2_NR : r % G2_NR;
+      uint16_t* imf = (uint16_t*)(m.g2_w + g2_img_off(ng, l, 0, grp));
+      uint16_t* imt = (uint16_t*)(m.g2_w + g2_img_off(ng, l, 1, grp));
+      uint32_t h, mi, lo;
+      g2_split2(v, 0.f, h, mi, lo);
+      const uint32_t t3[3] = {h, mi, lo};
+#pragma unroll
+      for (int t = 0; t < G2_NT; ++t) {
+        imf[g2_img_index(t, blk, c, f)] = (uint16_t)t3[t];
+        imt[g2_img_index(t, blk, f, c)] = (uint16_t)t3[t];
+      }
+    }
+  }
+}
+// d bias[f] of a layer (bq: gradient, parameter, moments); layer 0 with images: the bias row of the layer-0 table
+__device__ __forceinline__ void fts_bias(const ModelDev& m, float* __restrict__ grad, const AdamTail& at, int ng, int l, int R,
+                                         int fin, int f, const float (&bq)[4], bool emit) {
+  const int64_t i = m.off_bias[l] + f;
+  const float bnew = fts_emit(grad, at, i, bq[0], bq[1], bq[2], bq[3]);
+  if (emit && l == 0) m.g2_w[g2_t0_off(ng) + (R * fin + fin) * 32 + f] = bnew;
+}
+
 // img != 0 (with Adam): the weight images of the UPDATED parameters are written too -- what k_g2_compose would form from
 // them for the next step's subgraph / dense-layer kernels (g2_image.h): a thread holds the new basis_0..3[c][f] and
 // root[c][f] of its column; the layer's new att (20 values) is formed by EVERY workgroup of the layer (the owner stores it),
@@ -2061,10 +2068,8 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_finalize_ts(ModelDev m, const fl
     // (the bias / att roles FIRST: the weight images wait for the layer's new att, formed by wave 1 -- behind its share of the
     //  main pass it kept every other wave of the workgroup waiting at the barrier below for 2.6 k cycles)
     if (roles) {
-      if (bias_role) {                             // d bias
-        const int64_t i = m.off_bias[l] + tid;
-        const float bnew = fts_emit(grad, at, i, bq[0], bq[1], bq[2], bq[3]);
-        if (emit && l == 0) m.g2_w[g2_t0_off(ng) + (R * fin + fin) * 32 + tid] = bnew;       // layer-0 table: bias row
+      if (bias_role) {                             // d bias (layer-0 table: bias row)
+        fts_bias(m, grad, at, ng, l, R, fin, tid, bq, emit);
       } else if (tid >= 64) {                      // d att[r,b] = <dW_r, basis_b> (+ ARR): fin partials, fixed order
        for (int rb = tid - 64; rb < na; rb += IGMC_BLOCK - 64) {      // (one entry a thread up to 48 relations)
         const int r = rb >> 2, bb = rb & 3;
@@ -2090,75 +2095,26 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_finalize_ts(ModelDev m, const fl
             for (int k = 0; k < 32; ++k) g += v[k];
           }
         }
-        if (arr_coef != 0.f) {
-          float sacc = 0.f;
-          for (int bp = 0; bp < 4; ++bp) {
-            const float a0 = st[IGMC_STASH_ATT + r * 4 + bp];
-            const float dm = (r > 0) ? a0 - st[IGMC_STASH_ATT + (r - 1) * 4 + bp] : 0.f;
-            const float dn = (r + 1 < R) ? st[IGMC_STASH_ATT + (r + 1) * 4 + bp] - a0 : 0.f;
-            sacc += 2.f * (dm - dn) * st[IGMC_STASH_G + bp * 4 + bb];
-          }
-          g += arr_coef * sacc;
-        }
-        const float anew = fts_emit(grad, at, i, g, pold, m1o, m2o, part == 0);
+        const float anew = fts_att_entry(grad, at, st, R, rb, g, arr_coef, i, pold, m1o, m2o, part == 0);
         if (emit) s_attn[rb] = anew;
        }
       }
     }
     if (has) {       // one round for fin <= 32
       if (table) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-          if (r < R) {
-#pragma unroll
-            for (int bb = 0; bb < 4; ++bb) g[bb] += st[IGMC_STASH_ATT + r * 4 + bb] * tv[r];
-          }
+        fts_col_table8(g, st, tv, R);
         for (int r = 8; r < R; ++r) {
           const float tvr = t0[(size_t)r * nE + e];
 #pragma unroll
           for (int bb = 0; bb < 4; ++bb) g[bb] += st[IGMC_STASH_ATT + r * 4 + bb] * tvr;
         }
       }
-      if (arr_coef != 0.f) {
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb)
-          g[bb] += arr_coef * (st[IGMC_STASH_M + bb * 4 + 0] * pv[0] + st[IGMC_STASH_M + bb * 4 + 1] * pv[1] +
-                               st[IGMC_STASH_M + bb * 4 + 2] * pv[2] + st[IGMC_STASH_M + bb * 4 + 3] * pv[3]);
-      }
-#pragma unroll
-      for (int q = 0; q < 5; ++q) pn[q] = fts_emit(grad, at, idx[q], g[q], pv[q], m1v[q], m2v[q]);
+      fts_col_emit(grad, at, st, arr_coef, idx, g, pv, m1v, m2v, pn);
       e_img = e;
     }
     if (emit) {
       __syncthreads();
-      if (e_img >= 0) {
-        const int c = e_img >> 5, f = e_img & 31;
-        if (l == 0) {       // layer-0 table [W_0[r * L + c] | root_0[c] | bias_0] (rows past R L + L stay zero: first compose)
-          float* t0w = m.g2_w + g2_t0_off(ng);
-          for (int r = 0; r < R; ++r)
-            t0w[(r * fin + c) * 32 + f] = g2_wsum(s_attn[r * 4], s_attn[r * 4 + 1], s_attn[r * 4 + 2], s_attn[r * 4 + 3],
-                                                  pn[0], pn[1], pn[2], pn[3]);
-          t0w[(R * fin + c) * 32 + f] = pn[4];
-        } else {            // forward image: element (k = c, n = f); transposed image: element (k = f, n = c)
-          // relation r -> block r % G2_NR of group r / G2_NR; root -> block G2_NR of group 0
-#pragma unroll 3
-          for (int r = 0; r <= R; ++r) {           // (blocks of relations the model does not have stay zero: first compose)
-            const float v = (r == R) ? pn[4]
-                          : g2_wsum(s_attn[r * 4], s_attn[r * 4 + 1], s_attn[r * 4 + 2], s_attn[r * 4 + 3], pn[0], pn[1], pn[2], pn[3]);
-            const int grp = (r == R) ? 0 : r / G2_NR, blk = (r == R) ? G2_NR : r % G2_NR;
-            uint16_t* imf = (uint16_t*)(m.g2_w + g2_img_off(ng, l, 0, grp));
-            uint16_t* imt = (uint16_t*)(m.g2_w + g2_img_off(ng, l, 1, grp));
-            uint32_t h, mi, lo;
-            g2_split2(v, 0.f, h, mi, lo);
-            const uint32_t t3[3] = {h, mi, lo};
-#pragma unroll
-            for (int t = 0; t < G2_NT; ++t) {
-              imf[g2_img_index(t, blk, c, f)] = (uint16_t)t3[t];
-              imt[g2_img_index(t, blk, f, c)] = (uint16_t)t3[t];
-            }
-          }
-        }
-      }
+      if (e_img >= 0) fts_image_col(m, ng, l, R, fin, e_img >> 5, e_img & 31, s_attn, pn, 0, 1);
     }
   } else if ((int)blockIdx.x < 4 * IGMC_FTS_NB + nlin) {      // Adam on lin1 / lin2 (their gradients are final already)
     const int64_t n_lin = m.n_params - m.off_l1w;
@@ -2169,6 +2125,334 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_finalize_ts(ModelDev m, const fl
   } else {                                                     // loss, epoch total, control-block tick
     loss_body(at.b, m, at.ARR, at.loss, at.total, smf);
     if (tid == 0 && at.ctrl) ctrl_check_and_advance(at.ctrl, at.b, at.use_flags);
+  }
+}
+
+// ===================================================================== the tail of the subgraph kernel in ONE launch
+// k_tail_ts -> k_finalize_ts without the launch between them.  k_tail_ts does ~1 us of work; what it is there for is the
+// grid-wide fence between "every table is summed" and "every parameter is updated".  Here NO table data crosses a workgroup:
+//   * conv layers -- one workgroup per (layer l, input row c): it sums, from the nq partial tables, exactly the rows it
+//     consumes (dW_r[c] for r < R, d root[c], and for c == 0 the bias row) in reduce_ts_body's order -- per float4 column 16
+//     partial groups that take the slots pg, pg + 16, .. one after the other, then the groups in index order through LDS --
+//     and runs k_finalize_ts's column body on its 32 columns (c, f);
+//   * d att[r,b] = <dW_r, basis_b> needs every input row of the layer: the workgroup forms its row's share (the very values
+//     k_tail_ts leaves in datt_part), publishes the 4 R of them as {f32, tag} words (device scope: the readers sit on any
+//     XCD) and every workgroup of the layer polls the fin x 4 R words, adds them over c in index order and forms the layer's
+//     new att from the stashed moments, as k_finalize_ts does for its weight images; workgroup c == 0 stores att;
+//   * lin1 / lin2 -- the workgroups that form the gradient (head_bwd_w_body) update exactly the elements they formed;
+//   * the last workgroup -- loss, epoch total, control-block tick, launch sequence number.
+// The weights-only stash (fin_stash_body) reads parameters this launch updates in place: it rides in the launch in front
+// (k_graph_step2's appended workgroups) and also leaves the TAG of the words: that launch's sequence number, a word nobody
+// writes here.  Nothing but the words is waited for, the wait is bounded by the wall clock, and a workgroup that gives up
+// updates nothing and reports it (gs_err, sync_err bit 8).  ~133 workgroups of 256 threads: all resident together.
+// Every sum keeps the order the two-launch tail gives it: the step's results are the same bits.
+#define IGMC_TF_SETS 3                    // float4 columns a thread has in flight (x 14 slots each)
+#define IGMC_TF_ROWS 384                  // LDS floats of the reduced rows: up to 6 sets of 16 columns (R <= 8: 80 columns)
+#define IGMC_TF_O_ROWS (IGMC_TF_SETS * 1024)
+#define IGMC_TF_O_ST (IGMC_TF_O_ROWS + IGMC_TF_ROWS)
+#define IGMC_TF_O_DATT (IGMC_TF_O_ST + IGMC_STASH_LAYER)
+#define IGMC_TF_O_ATTN (IGMC_TF_O_DATT + 32 * IGMC_FOLD_NA)
+#define IGMC_TF_O_PN (IGMC_TF_O_ATTN + 64)
+#define IGMC_TF_O_SMF (IGMC_TF_O_PN + 5 * 32)
+#define IGMC_TF_WORDS (IGMC_TF_O_SMF + 16)
+#define IGMC_TF_POLL ((32 * IGMC_FOLD_NA + IGMC_BLOCK - 1) / IGMC_BLOCK)      // words a thread polls
+#define IGMC_TF_TIMEOUT_TICKS 20000000ll  // 200 ms of the 100 MHz wall clock
+#define IGMC_SYNC_ERR_FOLD 8              // sync_err bit: a hand-off of k_tail_fin timed out
+
+// Phase stamps (a variant library built with -DIGMC_FIN_CLOCKS; tools/exp_fin_clocks.py): shader-clock values of the first conv
+// workgroup (layer 1, row 0: slots 0..), the first lin workgroup (16..) and the loss / tick workgroup (32..).  The product
+// build carries none of it.
+#if defined(IGMC_FIN_CLOCKS) && !defined(IGMC_HIPEMU)
+__device__ unsigned long long g_fin_clk[64];
+extern "C" int igmc_debug_fin_clocks(unsigned long long* out) {
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fin_clk), sizeof(g_fin_clk)) != hipSuccess;
+}
+#define TF_STAMP(on, k) do { if ((on) && threadIdx.x == 0) g_fin_clk[k] = __builtin_readcyclecounter(); } while (0)
+#else
+#define TF_STAMP(on, k) do { } while (0)
+#endif
+
+__global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m, const float* P, float grad_scale, float mult,
+                                                           float drop_scale, float* grad, float arr_coef, AdamTail at, int nlin,
+                                                           int nparts, int stride, int B, int bump_seq, int mute_layer) {
+  __builtin_amdgcn_s_setprio(3);      // (step chain: ahead of the extraction chain's waves wherever the two share a SIMD)
+  igmc_kernarg_warm<sizeof(BatchDev) + sizeof(ModelDev) + sizeof(AdamTail) + 64>();
+  IGMC_DYN_SMEM(smem);
+  float* S = (float*)smem;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* stash = m.fin_stash;
+  if (at.ctrl) {      // hipGraph replay: the Adam scalars of the step, stashed in the launch in front
+    at.step_size = stash[IGMC_STASH_SCAL + 0];
+    at.inv_sqrt_bc2 = stash[IGMC_STASH_SCAL + 1];
+    at.beta1 = stash[IGMC_STASH_SCAL + 2];
+    at.beta2 = stash[IGMC_STASH_SCAL + 3];
+    at.eps = stash[IGMC_STASH_SCAL + 4];
+    at.wd = stash[IGMC_STASH_SCAL + 5];
+  }
+  const int R = m.R, L = m.L, na = R * 4;
+  const int nconv = 96 + L;                 // layers 1..3: 32 workgroups each, then layer 0's L
+  const int blk = blockIdx.x;
+  TF_STAMP(blk == 0, 0);
+  TF_STAMP(blk == nconv, 16);
+  TF_STAMP(blk == nconv + nlin, 32);
+  if (blk < nconv) {
+    const int l = blk < 96 ? 1 + (blk >> 5) : 0, c = blk < 96 ? (blk & 31) : blk - 96;
+    const int fin = (l == 0) ? L : 32, nE = fin * 32, ts = m.ts_stride;
+    const uint32_t tag = __float_as_uint(stash[IGMC_STASH_SCAL + IGMC_STASH_SEQ]) * 2u + 1u;      // (never 0)
+    float4* sred4 = (float4*)S;                       // [set][16 partial groups][16 columns]
+    float* rows = S + IGMC_TF_O_ROWS;                 // [R dW_r[c] | d root[c] | d bias (c == 0)][32]
+    float* s_st = S + IGMC_TF_O_ST;                   // the layer's stash
+    float* s_datt = S + IGMC_TF_O_DATT;               // [fin][IGMC_FOLD_NA] the layer's d att partial products
+    float* s_attn = S + IGMC_TF_O_ATTN;               // the layer's att after the step
+    float* s_pn = S + IGMC_TF_O_PN;                   // [5][32] the columns' basis_0..3 / root after the step
+    int* s_flag = (int*)(S + IGMC_TF_O_SMF + 8);      // a poll of the workgroup ran out
+    const int ng = g2_groups(R, L);
+    const int o4 = lane & 15, pg = wave * 4 + (lane >> 4);
+    // ---- every load that does not depend on another workgroup is requested here, in front of the partial tables: the layer's
+    // stash, the column threads' (tid < 32: f = tid) parameters and moments, wave 0's basis values for the d att products
+    // (both 32-lane halves: f = lane & 31), the bias role's (c == 0: tid 32..63)
+    float stq[(IGMC_STASH_LAYER + IGMC_BLOCK - 1) / IGMC_BLOCK];
+#pragma unroll
+    for (int u = 0; u < (IGMC_STASH_LAYER + IGMC_BLOCK - 1) / IGMC_BLOCK; ++u) {
+      const int i = tid + u * IGMC_BLOCK;
+      stq[u] = stash[l * IGMC_STASH_LAYER + (i < IGMC_STASH_LAYER ? i : IGMC_STASH_LAYER - 1)];
+    }
+    const int f = tid & 31, e = c * 32 + f;
+    const bool col = tid < 32, bias_role = c == 0 && tid >= 32 && tid < 64;
+    int64_t idx[5];
+    float pv[5], m1v[5], m2v[5], pvb[4] = {0.f, 0.f, 0.f, 0.f}, bq[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      idx[q] = (q < 4) ? m.off_basis[l] + (int64_t)q * nE + e : m.off_root[l] + e;
+      pv[q] = col ? P[idx[q]] : 0.f;
+      m1v[q] = col ? at.m1[idx[q]] : 0.f;
+      m2v[q] = col ? at.m2[idx[q]] : 0.f;
+    }
+    if (wave == 0) {
+#pragma unroll
+      for (int bb = 0; bb < 4; ++bb) pvb[bb] = P[idx[bb]];
+    }
+    if (bias_role) {
+      const int64_t i = m.off_bias[l] + f;
+      bq[1] = P[i];
+      bq[2] = at.m1[i];
+      bq[3] = at.m2[i];
+    }
+    if (tid == 0) *s_flag = 0;
+    TF_STAMP(blk == 0, 1);      // the independent loads are requested
+    // ---- the rows of this workgroup, summed over the partial tables: column k = (row j = k >> 3, float4 k & 7) in sets of 16
+    // columns, IGMC_TF_SETS sets a round (<= 42 sixteen-byte loads a thread, all requested before the first add).  The rows the
+    // d att products need -- dW_r[c] and d root[c], one round up to five relations -- come first; the bias row (c == 0) is a
+    // round of its own BEHIND the hand-off, under the wait for the other workgroups' words
+    const float* pl = m.ts_part + (size_t)l * IGMC_TS_BLOCKS * ts;
+    const TsSlots sl = ts_slots(nparts, stride, B);
+    const int nq = sl.nq;
+    bool first_round = true;
+    auto sum_columns = [&](int k0, int k1) {      // columns k0 .. k1 - 1 (k1 - k0 <= 16 IGMC_TF_SETS) -> rows
+      const int nsets = (k1 - k0 + 15) >> 4;
+      int i0[IGMC_TF_SETS];
+      float4 s4[IGMC_TF_SETS];
+#pragma unroll
+      for (int s = 0; s < IGMC_TF_SETS; ++s) {
+        const int k = k0 + 16 * s + o4, kc = k < k1 ? k : k1 - 1, j = kc >> 3;
+        const int row = j < R ? j * fin + c : j == R ? R * fin + c : R * fin + fin;
+        i0[s] = row * 32 + 4 * (kc & 7);
+        s4[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      for (int q0 = pg; q0 < nq; q0 += 16 * 14) {
+        float4 v[IGMC_TF_SETS][14];
+        size_t so[14];
+#pragma unroll
+        for (int u = 0; u < 14; ++u) so[u] = (size_t)ts_slot(sl, q0 + 16 * u) * ts;
+#pragma unroll
+        for (int s = 0; s < IGMC_TF_SETS; ++s)
+          if (s < nsets) {      // (uniform over the workgroup)
+#pragma unroll
+            for (int u = 0; u < 14; ++u) v[s][u] = *(const float4*)(pl + so[u] + i0[s]);
+          }
+#pragma unroll
+        for (int s = 0; s < IGMC_TF_SETS; ++s)
+          if (s < nsets) {
+#pragma unroll
+            for (int u = 0; u < 14; ++u)
+              if (q0 + 16 * u < nq) {
+                s4[s].x += v[s][u].x; s4[s].y += v[s][u].y; s4[s].z += v[s][u].z; s4[s].w += v[s][u].w;
+              }
+          }
+      }
+      if (!first_round) __syncthreads();      // (the groups' sums of the round before have been read)
+#pragma unroll
+      for (int s = 0; s < IGMC_TF_SETS; ++s)
+        if (s < nsets) sred4[(s * 16 + pg) * 16 + o4] = s4[s];
+      if (first_round) {
+#pragma unroll
+        for (int u = 0; u < (IGMC_STASH_LAYER + IGMC_BLOCK - 1) / IGMC_BLOCK; ++u) {
+          const int i = tid + u * IGMC_BLOCK;
+          if (i < IGMC_STASH_LAYER) s_st[i] = stq[u];
+        }
+      }
+      first_round = false;
+      __syncthreads();
+      if (wave < nsets) {
+        // wave -> set, lane -> component (lane & 3) of column (lane >> 2): the 16 groups in index order
+        const float* sr = (const float*)sred4;
+        float tot = 0.f;
+#pragma unroll
+        for (int g16 = 0; g16 < 16; ++g16) tot += sr[((wave * 16 + g16) * 16 + (lane >> 2)) * 4 + (lane & 3)];
+        const int k = k0 + 16 * wave + (lane >> 2);
+        if (k < k1) rows[k * 4 + (lane & 3)] = tot;
+      }
+    };
+    const int ncol_a = 8 * (R + 1);
+    for (int k0 = 0; k0 < ncol_a; k0 += 16 * IGMC_TF_SETS) sum_columns(k0, k0 + 16 * IGMC_TF_SETS < ncol_a ? k0 + 16 * IGMC_TF_SETS : ncol_a);
+    __syncthreads();
+    TF_STAMP(blk == 0, 2);      // the rows are reduced (the partial tables' round trip)
+    // ---- this row's share of d att[r,b] = <dW_r, basis_b>: 32 features, the butterfly of reduce_ts_body inside a 32-lane half
+    // (half h takes the relations h, h + 2, ..), published by the half's first lane
+    unsigned long long* words = m.fold_w + (size_t)l * 32 * IGMC_FOLD_NA;
+    if (wave == 0) {
+      const int h = lane >> 5;
+      for (int r2 = 0; r2 < R; r2 += 2) {
+        const int r = r2 + h;
+        const float tot = r < R ? rows[r * 32 + f] : 0.f;
+        float pb[4];
+#pragma unroll
+        for (int bb = 0; bb < 4; ++bb) pb[bb] = tot * pvb[bb];
+#pragma unroll
+        for (int bb = 0; bb < 4; ++bb)
+#pragma unroll
+          for (int d = 16; d >= 1; d >>= 1) pb[bb] += __shfl_xor(pb[bb], d, 64);     // stays inside a 32-lane half
+#ifdef IGMC_HIPEMU
+        if (l == mute_layer) continue;      // (the timeout test: this layer publishes nothing)
+#endif
+        if (f == 0 && r < R) {
+#pragma unroll
+          for (int bb = 0; bb < 4; ++bb) g2_pub_f32_agent(words + c * IGMC_FOLD_NA + r * 4 + bb, pb[bb], tag);
+        }
+      }
+    }
+    TF_STAMP(blk == 0, 3);      // the row's words are published
+    if (c == 0) sum_columns(ncol_a, ncol_a + 8);      // the bias row (read behind the barrier below)
+    TF_STAMP(blk == 0, 4);      // ... and the bias row is summed (c == 0 only)
+    // ---- the layer's fin x 4 R words: <= IGMC_TF_POLL a thread, looked at together until every one carries the launch's tag
+    {
+      const int nw = fin * na;
+      const unsigned long long* wp[IGMC_TF_POLL];
+      int wi[IGMC_TF_POLL];
+#pragma unroll
+      for (int u = 0; u < IGMC_TF_POLL; ++u) {
+        const int w = tid + u * IGMC_BLOCK, wc = w < nw ? w : nw - 1;
+        wi[u] = (wc / na) * IGMC_FOLD_NA + wc % na;
+        wp[u] = words + wi[u];
+      }
+      bool ok = false;
+#ifndef IGMC_HIPEMU
+      const long long t0 = (long long)wall_clock64();
+#endif
+      for (long it = 0;; ++it) {
+        unsigned long long w[IGMC_TF_POLL];
+        bool all = true;
+#pragma unroll
+        for (int u = 0; u < IGMC_TF_POLL; ++u) w[u] = g2_ld_word(wp[u]);
+#pragma unroll
+        for (int u = 0; u < IGMC_TF_POLL; ++u) all = all && (uint32_t)(w[u] >> 32) == tag;
+        if (all) {
+#pragma unroll
+          for (int u = 0; u < IGMC_TF_POLL; ++u) s_datt[wi[u]] = __uint_as_float((uint32_t)w[u]);     // (clamped repeats: the same value again)
+          ok = true;
+          break;
+        }
+#ifndef IGMC_HIPEMU
+        if ((it & 15) == 15 && (long long)wall_clock64() - t0 > IGMC_TF_TIMEOUT_TICKS) break;
+        __builtin_amdgcn_s_sleep(2);
+#else
+        if (it > (1L << 12)) break;
+        hipemu::yield();
+#endif
+      }
+      if (!ok) *s_flag = 1;
+    }
+    __syncthreads();
+    TF_STAMP(blk == 0, 5);      // the layer's words are in
+    if (*s_flag) {      // nothing of this workgroup's is updated
+      if (tid == 0) {
+        *m.gs_err = 1;
+        if (at.ctrl) atomicOr((unsigned long long*)(at.ctrl + IGMC_CTRL_SYNC_ERR), (unsigned long long)IGMC_SYNC_ERR_FOLD);
+      }
+      return;
+    }
+    const float* st = s_st;
+    // ---- the layer's new att (every workgroup forms it for its image words; c == 0 stores it, its moments and d att): the
+    // fin partial products in index order, as k_finalize_ts adds them
+    if (tid >= 64 && tid - 64 < na) {
+      const int rb = tid - 64;
+      float g = 0.f;
+#pragma unroll
+      for (int k = 0; k < 32; ++k) g += (k < fin) ? s_datt[k * IGMC_FOLD_NA + rb] : 0.f;
+      s_attn[rb] = fts_att_entry(grad, at, st, R, rb, g, arr_coef, m.off_att[l] + rb, st[IGMC_STASH_ATT + rb],
+                                 st[IGMC_STASH_ATTM1 + rb], st[IGMC_STASH_ATTM2 + rb], c == 0);
+    }
+    if (bias_role) {
+      bq[0] = rows[(R + 1) * 32 + f];
+      fts_bias(m, grad, at, ng, l, R, fin, f, bq, true);
+    }
+    if (col) {       // the column body of k_finalize_ts on (c, f)
+      float g[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, tv[8], pn[5];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) tv[r] = (r < R) ? rows[r * 32 + f] : 0.f;
+      g[4] = rows[R * 32 + f];
+      fts_col_table8(g, st, tv, R);
+      fts_col_emit(grad, at, st, arr_coef, idx, g, pv, m1v, m2v, pn);
+#pragma unroll
+      for (int q = 0; q < 5; ++q) s_pn[q * 32 + f] = pn[q];
+    }
+    TF_STAMP(blk == 0, 6);      // the main pass is stored
+    __syncthreads();
+    {   // the image words of the 32 columns: thread -> (relation tid >> 5 of eight at a time, column f)
+      float pn[5];
+#pragma unroll
+      for (int q = 0; q < 5; ++q) pn[q] = s_pn[q * 32 + f];
+      fts_image_col(m, ng, l, R, fin, c, f, s_attn, pn, tid >> 5, IGMC_BLOCK / 32);
+    }
+    TF_STAMP(blk == 0, 7);      // the image words are stored
+  } else if (blk < nconv + nlin) {
+    // ---- d lin1 / d lin2 and Adam on exactly the elements this workgroup formed: the 16 x 64 tile of lin1.weight and, for the
+    // first column tile, 16 entries of lin1.bias / lin2.weight (+ lin2.bias)
+    const int bx = (blk - nconv) & 7, by = (blk - nconv) >> 3, D = m.D;
+    head_bwd_w_body(b, m, P, nullptr, 1, grad_scale, mult, drop_scale, grad, bx, by, B);
+    __syncthreads();
+    TF_STAMP(blk == nconv, 17);      // the tile's gradient is formed
+    int64_t ix[5];
+    bool okx[5];
+    float gv[5], pv[5], av[5], vv[5];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int el = tid + k * IGMC_BLOCK, colx = by * 64 + (el & 63);
+      okx[k] = colx < D;
+      ix[k] = m.off_l1w + (int64_t)(bx * 16 + (el >> 6)) * D + (okx[k] ? colx : 0);
+    }
+    okx[4] = by == 0 && (tid < 32 || (tid == 32 && bx == 0));
+    ix[4] = tid < 16 ? m.off_l1b + bx * 16 + tid : tid < 32 ? m.off_l2w + bx * 16 + tid - 16 : m.off_l2b;
+    const float* gsrc = grad;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      const int64_t i = okx[k] ? ix[k] : m.off_l1w;      // clamped, not predicated: the loads go out back to back
+      gv[k] = gsrc[i];
+      pv[k] = at.p[i];
+      av[k] = at.m1[i];
+      vv[k] = at.m2[i];
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+      if (okx[k]) adam_store_sep(at.p, at.m1, at.m2, ix[k], gv[k], pv[k], av[k], vv[k], at.step_size, at.inv_sqrt_bc2, at.beta1,
+                                 at.beta2, at.eps, at.wd);      // (adam_range's bits: k_finalize_ts's lin workgroups)
+    TF_STAMP(blk == nconv, 18);
+  } else {                                                     // loss, epoch total, control-block tick, sequence number
+    if (bump_seq && tid == 0) m.gs_bar[1] += 1;               // (every workgroup of k_graph_step2 is done)
+    loss_body(at.b, m, at.ARR, at.loss, at.total, S + IGMC_TF_O_SMF);
+    TF_STAMP(true, 33);
+    if (tid == 0 && at.ctrl) ctrl_check_and_advance(at.ctrl, at.b, at.use_flags);
+    TF_STAMP(true, 34);
   }
 }
 
@@ -2375,6 +2659,23 @@ static void launch_tail_ts(const ModelDev& m, const BatchDev& b, const float* P,
                mult, 2.f, grad, nlin, nparts, stride, B, nstash, ctrl, bump_seq);
 }
 
+// ... and the whole tail behind the subgraph kernel as ONE launch (sp.tail_fold; the stash role ran in the launch in front)
+static void launch_tail_fin(const ModelDev& m, const BatchDev& b, const float* P, int B, float grad_scale, float mult, float* grad,
+                            float arr_coef, const AdamTail& at, int nlin, int nparts, int stride, int bump_seq, void* stream) {
+  int mute = -1;
+#ifdef IGMC_HIPEMU
+  // (emulator only -- the timeout test: the workgroups of this layer publish nothing, its pollers give up)
+  if (const char* e = getenv("IGMC_EMU_FOLD_MUTE")) mute = atoi(e);
+  // the workgroups of a layer wait for each other's words: they run together (32 consecutive workgroups = layer 1, 2, 3, then
+  // layer 0's in front of the lin workgroups)
+  hipemu::rt().co_cs = 32;
+  hipemu::rt().co_stride = -1;
+  hipemu::rt().co_block = 0;
+#endif
+  IGMC_PLAUNCH("k_tail_fin", k_tail_fin, 96 + m.L + nlin + 1, IGMC_BLOCK, (size_t)IGMC_TF_WORDS * sizeof(float), stream, b, m, P,
+               grad_scale, mult, 2.f, grad, arr_coef, at, nlin, nparts, stride, B, bump_seq, mute);
+}
+
 // The reduced gradient sources of a data-parallel step, summed over the ranks: tables + d att partials (one allocation), or the
 // basis-space sums (+ layer-0 table, d att); and the lin gradients (the tail of the flat parameter vector)
 static int launch_exchange(const ModelDev& m, int tail, const StepExchange* xch, float* grad, void* stream) {
@@ -2520,7 +2821,17 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const BatchDev& b, const StepPla
   if (sp.family == IGMC_FAM_G2) {
     // one workgroup (cluster) per subgraph: forward, residual and backward down to the per-workgroup gradient partials;
     // bump_seq = 1: k_tail_ts advances the launch sequence number of the subgraph kernel's exchange tags
-    const int bump_seq = igmc_launch_graph_step2(m, b, sp, Pc, B, 1, use_flags, inj_mask, seed, step, mult, grad_scale, out, stream);
+    // sp.tail_fold, a step with Adam that leaves the weight images, no exchange: the tail is ONE launch behind the subgraph
+    // kernel, whose launch then carries the stash role (four more workgroups)
+    const int fold = sp.tail_fold && tables && adam && at.enabled && img && !xch;
+    const int stride = (sp.cs > 1) ? ((B + 7) & ~7) : IGMC_TS_BLOCKS;
+    const int bump_seq = igmc_launch_graph_step2(m, b, sp, Pc, B, 1, use_flags, inj_mask, seed, step, mult, grad_scale, out, stream,
+                                                 fold ? 4 : 0, ctrl);
+    if (fold) {
+      launch_tail_fin(m, b, Pc, B, grad_scale, mult, grad, ARR * arr_scale, at, 8 * ny, sp.grid, stride, bump_seq, stream);
+      if (img_emitted) *img_emitted = 1;
+      return 0;
+    }
     launch_tail_ts(m, b, Pc, B, grad_scale, mult, grad, 8 * ny, sp.grid, (sp.cs > 1) ? ((B + 7) & ~7) : IGMC_TS_BLOCKS,
                    tables ? 4 : 0, ctrl, bump_seq, stream);
   } else {

@@ -17,6 +17,7 @@ struct StepHooks {
   int dl_gsplit;       // IGMC_DL_GSPLIT=0: the group-after-group form
   int dl_head;         // IGMC_DL_HEAD=0: the loss head as a launch of its own in front of k_dl_bwd
   int fin_mode;        // IGMC_FIN_MODE=0: the hand-off version of the gradient / Adam tail (k_finalize)
+  int tail_fold;       // IGMC_TAIL_FOLD=0: the two-launch tail behind the subgraph kernel (k_tail_ts -> k_finalize_ts)
 };
 static int step_hook(const char* name, int unset) {
   const char* e = getenv(name);
@@ -33,6 +34,7 @@ static StepHooks step_hooks() {
   hk.dl_gsplit = step_hook("IGMC_DL_GSPLIT", 1);
   hk.dl_head = step_hook("IGMC_DL_HEAD", 1);
   hk.fin_mode = step_hook("IGMC_FIN_MODE", 1);
+  hk.tail_fold = step_hook("IGMC_TAIL_FOLD", 1);
   return hk;
 }
 int igmc_dl_always() { return step_hook("IGMC_DL_ALWAYS", 0) == 1; }
@@ -165,6 +167,11 @@ void igmc_step_plan(const ModelDev& m, const BatchDev& b, int B, int kind, StepP
     p->grid = (p->cs > 1) ? p->cs * ((B + 7) & ~7) : gs_grid(hk, B);
     p->tail = fts ? IGMC_TAIL_TS : IGMC_TAIL_HANDOFF;
     p->exchange_inside = fused && fts;
+    // the tail as ONE launch (k_tail_fin): a workgroup per input row of a layer, which takes no more than 32 of them and hands
+    // over no more than IGMC_FOLD_NA d att entries.  The call decides the rest: Adam with the weight images, no exchange
+    // (the four stash workgroups appended to the subgraph kernel's launch take a CU each -- the launch's dynamic LDS -- and are
+    //  resident with the rest: a clustered grid is <= 224 on >= 240 CUs (gs_cluster), any other <= IGMC_WG_BLOCKS)
+    p->tail_fold = fused && fts && hk.tail_fold != 0 && m.fold_w && m.L <= 32 && 4 * m.R <= IGMC_FOLD_NA;
     p->step_form = 1;
     return;
   }

@@ -828,6 +828,9 @@ class StepGraph(GroupPipeline):
                 what.append('a step trained on an arena whose stamp is not the batch of its cursor')
             if err & 4:
                 what.append('a step trained on edge-dropout draws keyed by another batch')
+            if err & 8:
+                what.append('a hand-off between workgroups of the one-launch tail (k_tail_fin) timed out: a conv layer kept '
+                            'its parameters (GPU shared with another job? IGMC_TAIL_FOLD=0 runs the two-launch tail)')
             raise RuntimeError('device-side step control: %s (sync_err=%d); results of the affected steps are invalid'
                                % ('; '.join(what) or 'error', err))
 

@@ -1,5 +1,11 @@
-"""Experiment (GPU, variant library with stamps in k_finalize_ts: profiles/r06_experiments): cycles between the stamps of a main
-workgroup (layer 1, part 0), a lin workgroup and the loss / tick workgroup of the LAST k_finalize_ts launch of a short run."""
+"""Experiment (GPU, variant library with phase stamps in the one-launch tail k_tail_fin): shader-clock cycles between the stamps
+of the first conv workgroup (layer 1, input row 0), the first lin workgroup and the loss / tick workgroup of the LAST
+k_tail_fin launch of a short replayed run.
+
+The variant is the product's sources compiled with -DIGMC_FIN_CLOCKS into a library of its own:
+    HIPCC_COMPILE_FLAGS_APPEND=-DIGMC_FIN_CLOCKS IGMC_HIP_LIB_OUT=$PWD/igmc_amd/lib/libigmc_hip_finclk.so \\
+        python -m igmc_amd.build --force
+(The stamps of k_finalize_ts that this tool read in round 6 lived in a patch: profiles/r06_experiments.)"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -30,9 +36,11 @@ for rep in range(3):
     lib.cdll.igmc_debug_fin_clocks.argtypes = [C.c_void_p]
     assert lib.cdll.igmc_debug_fin_clocks(out) == 0
     v = list(out)
-    t0 = v[0]
     def row(base, ks, names):
         return '  '.join('%s +%d' % (n, v[base + k] - v[base]) for k, n in zip(ks, names))
-    print('main wg (layer 1, part 0): ' + row(0, [1, 2, 3, 4, 5, 6, 7], ['loads issued', 'stash in LDS', 'barrier', 'main pass stored', 'roles done', 'img barrier', 'images stored']))
-    print('lin wg: start +%d  ' % (v[16] - t0) + row(16, [1, 7], ['begin', 'adam done']))
-    print('tick wg: start +%d  ' % (v[32] - t0) + row(32, [1, 2, 7], ['begin', 'loss done', 'tick done']))
+    print('conv wg (layer 1, row 0): ' + row(0, [1, 2, 3, 4, 5, 6, 7], ['loads issued', 'rows reduced', 'words published', 'bias row',
+                                                                    'words polled', 'main pass stored', 'images stored']))
+    # (each workgroup against its OWN first stamp: the shader clocks of different XCDs do not share an origin)
+    print('lin wg: ' + row(16, [1, 2], ['gradient tile', 'adam done']))
+    print('tick wg: ' + row(32, [1, 2], ['loss done', 'tick done']))
+sg.check()
