@@ -15,7 +15,8 @@
 //                  one workgroup per segment merges.
 //
 // THE ORDER of a segment (igmc_hip.h states it for callers): (key descending, index ascending), every NaN behind every number,
-// -0.0 == 0.0 -- np.lexsort((idx, np.where(np.isnan(k), np.inf, -k))).  A key and its GLOBAL position travel as one 64-bit
+// -0.0 == 0.0 -- np.lexsort((idx, np.where(np.isnan(k), 0, -k), np.isnan(k))); the two-key np.lexsort((idx, np.where(np.isnan(k),
+// np.inf, -k))) is that order only for segments without a -inf key.  A key and its GLOBAL position travel as one 64-bit
 // word (select.h: sel_word_desc), the order is "word ascending", words are distinct: the lists do not depend on k.
 // Plain vector stores only (error words: a vector atomic OR, reached on errors only).
 #include "launch.h"

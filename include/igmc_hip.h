@@ -394,8 +394,10 @@ int igmc_candidates_fill(const igmc_graph* g, const int32_t* d_users, int nq, co
 /* igmc_select_segments: the `num` first of every segment [d_seg_off[s], d_seg_off[s + 1]) of d_keys, s < ns (no reference
  * counterpart; by hand `np.lexsort` per user on the host), 1 <= num <= 64, d_seg_off[ns] < 2^31.
  * THE ORDER: key DESCENDING, then index ascending; every NaN behind every number (NaNs among themselves by index);
- * -0.0 == 0.0.  Per segment that is np.lexsort((idx, np.where(np.isnan(k), np.inf, -k))).  It is NOT the reverse of
- * igmc_select_extremes' order: among equal keys the LOWER index comes first here (of two items predicted alike the lower id
+ * -0.0 == 0.0.  Per segment that is the three-key np.lexsort((idx, np.where(np.isnan(k), 0, -k), np.isnan(k))): the NaNs are
+ * set behind the numbers by a key of their own.  (The two-key np.lexsort((idx, np.where(np.isnan(k), np.inf, -k))) maps -inf
+ * and NaN to the same value and orders the two among themselves by index: it is THE ORDER only for segments without a -inf
+ * key.)  It is NOT the reverse of igmc_select_extremes' order: among equal keys the LOWER index comes first here (of two items predicted alike the lower id
  * ranks first), where the "highest" list of igmc_select_extremes takes the higher index first.
  *   d_idx_out[s * num + r] = position IN d_keys (not in the segment) of the r-th of segment s     r < count_s = min(len_s, num)
  *   d_key_out[s * num + r] = d_keys[that position], its own bits (d_key_out may be NULL)
@@ -420,7 +422,7 @@ int igmc_select_segments(const float* d_keys, const int64_t* d_seg_off, int ns, 
  *                 -1 when the segment has none (with candidate lists: an item the user has rated, or one masked out)
  *   d_q_rank[q] = the number of entries of the segment that come BEFORE that entry in THE ORDER of igmc_select_segments (key
  *                 descending, then position ascending; every NaN behind every number, NaNs among themselves by position;
- *                 -0.0 == 0.0), i.e. its 0-based place in np.lexsort((idx, np.where(np.isnan(k), np.inf, -k))) -- querying
+ *                 -0.0 == 0.0), i.e. its 0-based place in np.lexsort((idx, np.where(np.isnan(k), 0, -k), np.isnan(k))) -- querying
  *                 the id at d_idx_out[s * num + r] of igmc_select_segments returns r; a NaN-keyed entry has a place like any
  *                 other; -1 where d_q_pos[q] is -1
  * geometry: 0 = chosen from ns as igmc_select_segments chooses, k in [1, 64] = k workgroups per segment, each counting one

@@ -6,9 +6,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import selection_checks as SC
 from helpers import emu_lib, load_extract_golden
 from igmc_amd import _lib, engine
 from igmc_amd.stepgraph import _ctrl_words
+from parity_checks import EmuBackend
 
 CASES = load_extract_golden()
 P = engine._p
@@ -107,61 +109,18 @@ def test_a_position_without_a_place_is_reported_and_writes_nothing():
 
 
 # ------------------------------------------------------------------ selection of the extremes
-def select(lib, keys, num, grid=0):
-    keys = np.ascontiguousarray(keys, np.float32)
-    n = len(keys)
-    nbytes = lib.igmc_select_scratch_bytes(n, num, grid)
-    assert nbytes > 0
-    scratch = np.zeros(nbytes // 8, np.uint64)
-    il, ih = np.full(num, -9, np.int32), np.full(num, -9, np.int32)
-    kl, kh = np.full(num, -9.0, np.float32), np.full(num, -9.0, np.float32)
-    cnt = np.zeros(1, np.int32)
-    lib.call('igmc_select_extremes', P(keys), n, num, P(il), P(ih), P(kl), P(kh), P(cnt), P(scratch), nbytes, grid, None)
-    return il, ih, kl, kh, int(cnt[0])
-
-
-def expect(keys, num):
-    order = np.argsort(np.asarray(keys, np.float32), kind='stable')
-    return order[:num], order[-num:][::-1]
-
-
-def key_sets(n, seed):
-    rng = np.random.default_rng(seed)
-    special = rng.normal(0, 1, n).astype(np.float32)
-    for j, v in enumerate((np.inf, -np.inf, np.nan, -0.0, 0.0, np.nan, -np.inf, 0.0, -0.0, np.inf)):
-        special[(j * 7919) % n] = v
-    return {
-        'random': rng.normal(0, 1, n).astype(np.float32),
-        'five_levels': rng.integers(1, 6, n).astype(np.float32),          # heavy ties, as sort_by='true' has
-        'all_equal': np.full(n, 2.5, np.float32),
-        'special': special,
-    }
-
-
+# (cases, reference and checks: tests/selection_checks.py, shared with tests/test_gpu_selection.py)
 @pytest.mark.parametrize('num', [1, 5, 64])
 def test_select_extremes_is_the_stable_argsort(num):
-    lib = emu_lib()
+    be = EmuBackend()
     sizes = sorted(set(s for s in (1, 3, num - 1, num, num + 1, 64, 65, 1000, 5000) if s >= 1))
     for n in sizes:
-        for name, keys in key_sets(n, 100 * num + n).items():
-            lo, hi = expect(keys, num)
-            results = [select(lib, keys, num, grid) for grid in (0, 1, 3, 7)]
-            for il, ih, kl, kh, cnt in results:
-                c = min(n, num)
-                assert cnt == c, (name, n)
-                assert np.array_equal(il[:c], lo) and np.array_equal(ih[:c], hi), (name, n, il[:c], lo, ih[:c], hi)
-                assert kl[:c].tobytes() == keys[lo].tobytes() and kh[:c].tobytes() == keys[hi].tobytes()      # the keys' own bits
-                assert (il[c:] == -1).all() and (ih[c:] == -1).all() and (kl[c:] == 0).all() and (kh[c:] == 0).all()
+        for name, keys in SC.key_sets(n, 100 * num + n).items():
+            SC.check_extremes(be, keys, num, (0, 1, 3, 7), name)
 
 
 def test_select_extremes_nan_and_signed_zero_order():
-    lib = emu_lib()
-    keys = np.array([np.nan, 0.0, -0.0, np.inf, -np.inf, -np.nan, 1.0, -0.0], np.float32)
-    il, ih, _, _, cnt = select(lib, keys, 8)
-    assert cnt == 8
-    assert il.tolist() == [4, 1, 2, 7, 6, 3, 0, 5]          # -inf, the zeros by index, 1, +inf, the NaNs by index
-    assert il.tolist() == np.argsort(keys, kind='stable').tolist()
-    assert ih.tolist() == il.tolist()[::-1]
+    SC.check_extremes_known_answer(EmuBackend())
 
 
 def test_select_extremes_refuses_bad_arguments():

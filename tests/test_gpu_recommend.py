@@ -1,7 +1,7 @@
 """Top-N recommendation on a real MI355X (``igmc_amd/recommend.py``, ``igmc_amd/csrc/candidates.hip``): candidate links
 enumerated on the device score bit for bit like the same links uploaded from the host, the ranked lists are the numpy
-lexsort of those scores, passes replay one captured graph, the lists agree with the CPU oracle, and ``Main.py --recommend``
-end to end."""
+lexsort of those scores (``selection_checks.descending_order``), passes replay one captured graph, the lists agree with the
+CPU oracle, and ``Main.py --recommend`` end to end."""
 import os
 import subprocess
 import sys
@@ -12,6 +12,7 @@ import scipy.sparse as ssp
 
 import parity_checks as PC
 from helpers import ROOT, random_rating_graph
+from selection_checks import descending_order
 
 pytestmark = pytest.mark.gpu
 
@@ -48,13 +49,13 @@ def _complement(adj, users, item_mask=None, exclude_seen=True):
 
 
 def _expect_lists(scores, items, off, n):
-    """Per segment np.lexsort((idx, np.where(np.isnan(k), np.inf, -k))): (items [nq, n], scores [nq, n], counts)."""
+    """Per segment THE ORDER (selection_checks.descending_order): (items [nq, n], scores [nq, n], counts)."""
     nq = len(off) - 1
     I, S, C = np.full((nq, n), -1, np.int32), np.zeros((nq, n), np.float32), np.zeros(nq, np.int32)
     for q in range(nq):
         k = scores[off[q]:off[q + 1]]
         idx = np.arange(off[q], off[q + 1])
-        order = np.lexsort((idx, np.where(np.isnan(k), np.inf, -k)))[:n]
+        order = descending_order(k, idx)[:n]
         c = len(order)
         I[q, :c], S[q, :c], C[q] = items[idx[order]], k[order], c
     return I, S, C
