@@ -751,7 +751,7 @@ extern "C" int igmc_model_create(int device, int num_relations, int num_bases, i
     fail |= M.get(&d.ts_part, (size_t)4 * IGMC_TS_BLOCKS * d.ts_stride) |
             M.get(&d.ts_raw, (size_t)4 * d.ts_stride + (size_t)4 * d.ts_stride / 32 * 4);
     if (!fail) d.datt_part = d.ts_raw + (size_t)4 * d.ts_stride;
-    fail |= M.get(&d.fold_w, (size_t)4 * 32 * IGMC_FOLD_NA);      // hand-off words of the one-launch tail
+    fail |= M.get(&d.fold_w, (size_t)IGMC_FOLD_WORDS);      // hand-off words of the one-launch tail
   }
   if (d.R <= 128) fail |= M.get(&d.fin_stash, (size_t)4 * IGMC_STASH_LAYER + 16);     // weights-only stash of k_finalize_ts (both modes)
   d.g2_ex = nullptr;
@@ -821,7 +821,7 @@ extern "C" int igmc_model_create(int device, int num_relations, int num_bases, i
     const unsigned long long ts0[4] = {~0ull, 0ull, 0ull, 0ull};
     HIPCHECK(hipMemcpy(m->d.gs_ts, ts0, sizeof(ts0), hipMemcpyHostToDevice));
   }
-  if (m->d.fold_w) HIPCHECK(hipMemset(m->d.fold_w, 0, (size_t)4 * 32 * IGMC_FOLD_NA * sizeof(unsigned long long)));      // tag 0: never issued
+  if (m->d.fold_w) HIPCHECK(hipMemset(m->d.fold_w, 0, (size_t)IGMC_FOLD_WORDS * sizeof(unsigned long long)));      // tag 0: never issued
   if (m->d.g2_ex) {
     HIPCHECK(hipMemset(m->d.g2_ex, 0, 5 * m->d.g2_ex_stride * sizeof(unsigned long long)));
     HIPCHECK(hipMemset(m->d.g2_fx, 0, (size_t)max_graphs * 256 * sizeof(unsigned long long)));
@@ -1209,7 +1209,7 @@ extern "C" int igmc_model_reset_exchange(igmc_model* m, void* stream) {
   if (!m) IGMC_FAIL("null model");
   hipStream_t st = (hipStream_t)stream;
   // (the tail's hand-off words carry the launch sequence number, which restarts with the flags)
-  if (m->d.fold_w) HIPCHECK(hipMemsetAsync(m->d.fold_w, 0, (size_t)4 * 32 * IGMC_FOLD_NA * sizeof(unsigned long long), st));
+  if (m->d.fold_w) HIPCHECK(hipMemsetAsync(m->d.fold_w, 0, (size_t)IGMC_FOLD_WORDS * sizeof(unsigned long long), st));
   if (m->d.g2_ex) {
     HIPCHECK(hipMemsetAsync(m->d.g2_ex, 0, 5 * m->d.g2_ex_stride * sizeof(unsigned long long), st));
     HIPCHECK(hipMemsetAsync(m->d.g2_fx, 0, (size_t)m->d.g2_graphs * 256 * sizeof(unsigned long long), st));

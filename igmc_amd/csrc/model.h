@@ -8,6 +8,11 @@
 #endif
 #define IGMC_STASH_LAYER 672  // floats per conv layer of the weights-only stash (fin_stash; layout: model.hip)
 #define IGMC_FOLD_NA 32       // d att entries a layer of the one-launch tail (k_tail_fin) hands over: 4 R <= 32
+#define IGMC_FOLD_PSETS 4     // row producers an input row can have there: the sets 1.. of 16 float4 columns (R <= 8: 72 columns, 5 sets)
+// the hand-off words of the one-launch tail (ModelDev::fold_w), in words: d att partial products, reduced rows, bias rows
+#define IGMC_FOLD_O_ROWS (4 * 32 * IGMC_FOLD_NA)
+#define IGMC_FOLD_O_BIAS (IGMC_FOLD_O_ROWS + 4 * 32 * IGMC_FOLD_PSETS * 64)
+#define IGMC_FOLD_WORDS (IGMC_FOLD_O_BIAS + 4 * 32)
 #define IGMC_TS_BLOCKS 256   // partial slots of the relation-space tables (one per workgroup of k_graph_step)
 #define IGMC_GATHER_BLOCKS 4096   // max grid of the row-walker kernels (4 rows = 4 waves per block)
 // The basis-space mode of the gradient / Adam tail (k_finalize_ts) is correct up to 128 relations (the stash holds them) but only pays up to 32: its per-relation
@@ -48,7 +53,9 @@ struct ModelDev {
                       // written by the stash role, read by k_finalize_ts / k_tail_fin (or NULL)
   float* datt_part;   // [4*ts_stride/32][4] partial <dW_r, basis_b> products of 32 table elements (k_tail_ts)
   unsigned long long* fold_w;  // [4 layers][32 input rows][IGMC_FOLD_NA] {f32, tag} words: the same partial products as they cross
-                               // the workgroups of the one-launch tail (k_tail_fin); tag 0 is never a launch's (or NULL)
+                               // the workgroups of the one-launch tail (k_tail_fin); tag 0 is never a launch's (or NULL).  Behind
+                               // them (IGMC_FOLD_O_ROWS) [4][32][IGMC_FOLD_PSETS][64] words of the rows its producer workgroups
+                               // reduce, and (IGMC_FOLD_O_BIAS) [4][32] of the bias rows: IGMC_FOLD_WORDS in all
   int* gs_bar;        // k_graph_step clusters: [0] workgroups that finished the launch, [1] launch sequence number
   int* gs_err;        // [1] set when a cluster exchange timed out
   unsigned long long* gs_ts;   // [4] device-side launch clock of k_graph_step (igmc_profile_enable(2)): [0] earliest workgroup

@@ -26,6 +26,7 @@
 #include "fin_stash.h"      // layout of the weights-only stash (IGMC_STASH_*) and the role that fills it
 #include "g2_words.h"       // {f32, tag} words (the one-launch tail's hand-off)
 #include <stdlib.h>
+#include <string.h>
 
 // ---- XCD affinity -------------------------------------------------------------------------------------
 // MI355X has 8 XCDs with private, mutually non-coherent 4 MiB L2s, and workgroup b of a launch runs on XCD
@@ -2130,38 +2131,50 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_finalize_ts(ModelDev m, const fl
 
 // ===================================================================== the tail of the subgraph kernel in ONE launch
 // k_tail_ts -> k_finalize_ts without the launch between them.  k_tail_ts does ~1 us of work; what it is there for is the
-// grid-wide fence between "every table is summed" and "every parameter is updated".  Here NO table data crosses a workgroup:
-//   * conv layers -- one workgroup per (layer l, input row c): it sums, from the nq partial tables, exactly the rows it
-//     consumes (dW_r[c] for r < R, d root[c], and for c == 0 the bias row) in reduce_ts_body's order -- per float4 column 16
-//     partial groups that take the slots pg, pg + 16, .. one after the other, then the groups in index order through LDS --
-//     and runs k_finalize_ts's column body on its 32 columns (c, f);
-//   * d att[r,b] = <dW_r, basis_b> needs every input row of the layer: the workgroup forms its row's share (the very values
-//     k_tail_ts leaves in datt_part), publishes the 4 R of them as {f32, tag} words (device scope: the readers sit on any
-//     XCD) and every workgroup of the layer polls the fin x 4 R words, adds them over c in index order and forms the layer's
-//     new att from the stashed moments, as k_finalize_ts does for its weight images; workgroup c == 0 stores att;
+// grid-wide fence between "every table is summed" and "every parameter is updated".  Here the only table data that crosses a
+// workgroup are REDUCED rows, 64 floats a producer, as tagged words:
+//   * conv layers -- the rows (layer l, input row c) consumes (dW_r[c] for r < R, d root[c]) are 8 (R + 1) float4 columns,
+//     taken in sets of 16 (R = 5: dW_0|dW_1, dW_2|dW_3, dW_4|d root).  A workgroup sums ONE set from the nq partial tables
+//     (tf_sum_set: 14 sixteen-byte loads a thread) in reduce_ts_body's order -- per float4 column 16 partial groups that take
+//     the slots pg, pg + 16, .. one after the other, then the groups in index order through LDS.  The "main" workgroup of
+//     (l, c) takes set 0, a "row producer" each of the other sets, and one "bias producer" a layer the bias row.  A producer
+//     publishes its <= 64 sums as {f32, tag} words (device scope: the readers sit on any XCD); the main polls those of its
+//     row (every main of the layer also the bias words, so that a layer whose words never arrive is left untouched as a
+//     whole; c == 0 consumes them) and runs k_finalize_ts's column body on its 32 columns (c, f);
+//   * d att[r,b] = <dW_r, basis_b> needs every input row of the layer: the workgroup that reduced dW_r[c] -- the main for the
+//     relations of set 0, a row producer for the others -- forms the row's share (tf_datt_pub: the very values k_tail_ts
+//     leaves in datt_part) and publishes it the same way; every main of the layer polls the fin x 4 R words, adds them over c
+//     in index order and forms the layer's new att from the stashed moments, as k_finalize_ts does for its weight images;
+//     main c == 0 stores att;
 //   * lin1 / lin2 -- the workgroups that form the gradient (head_bwd_w_body) update exactly the elements they formed;
 //   * the last workgroup -- loss, epoch total, control-block tick, launch sequence number.
+// Grid: [row producers: main-major, set-minor | 4 bias producers | workgroups that return at once, up to a multiple of 32 |
+// mains of layers 1, 2, 3: 32 each | layer 0's L mains | nlin lin workgroups | tick] -- 200 + 4 + 20 + 100 + 32 + 1 = 357
+// workgroups of 256 threads at R = 5, L = 4: all resident together.  No deadlock: a producer waits for nothing; a main waits
+// for producers, which have lower indices and so were dispatched before it, and for the mains of its own layer, 32 consecutive
+// indices (the CPU emulator runs aligned groups of 32 consecutive workgroups together, one group after the other: every
+// producer group is complete before a main runs, and the mains of a layer run together).
 // The weights-only stash (fin_stash_body) reads parameters this launch updates in place: it rides in the launch in front
 // (k_graph_step2's appended workgroups) and also leaves the TAG of the words: that launch's sequence number, a word nobody
-// writes here.  Nothing but the words is waited for, the wait is bounded by the wall clock, and a workgroup that gives up
-// updates nothing and reports it (gs_err, sync_err bit 8).  ~133 workgroups of 256 threads: all resident together.
+// writes here.  Nothing but the words is waited for (no fence, no release / acquire: value and tag are one store), the wait
+// is bounded by the wall clock, and a workgroup that gives up updates nothing and reports it (gs_err, sync_err bit 8).
 // Every sum keeps the order the two-launch tail gives it: the step's results are the same bits.
-#define IGMC_TF_SETS 3                    // float4 columns a thread has in flight (x 14 slots each)
 #define IGMC_TF_ROWS 384                  // LDS floats of the reduced rows: up to 6 sets of 16 columns (R <= 8: 80 columns)
-#define IGMC_TF_O_ROWS (IGMC_TF_SETS * 1024)
+#define IGMC_TF_O_ROWS 1024               // (in front: one set of [16 partial groups][16 float4 columns])
 #define IGMC_TF_O_ST (IGMC_TF_O_ROWS + IGMC_TF_ROWS)
 #define IGMC_TF_O_DATT (IGMC_TF_O_ST + IGMC_STASH_LAYER)
 #define IGMC_TF_O_ATTN (IGMC_TF_O_DATT + 32 * IGMC_FOLD_NA)
 #define IGMC_TF_O_PN (IGMC_TF_O_ATTN + 64)
 #define IGMC_TF_O_SMF (IGMC_TF_O_PN + 5 * 32)
 #define IGMC_TF_WORDS (IGMC_TF_O_SMF + 16)
-#define IGMC_TF_POLL ((32 * IGMC_FOLD_NA + IGMC_BLOCK - 1) / IGMC_BLOCK)      // words a thread polls
+// words a thread of a main polls: its row's (<= IGMC_FOLD_PSETS x 64), the layer's d att (<= 32 x IGMC_FOLD_NA), the bias row's
+#define IGMC_TF_POLL ((IGMC_FOLD_PSETS * 64 + 32 * IGMC_FOLD_NA + 32 + IGMC_BLOCK - 1) / IGMC_BLOCK)
 #define IGMC_TF_TIMEOUT_TICKS 20000000ll  // 200 ms of the 100 MHz wall clock
 #define IGMC_SYNC_ERR_FOLD 8              // sync_err bit: a hand-off of k_tail_fin timed out
 
-// Phase stamps (a variant library built with -DIGMC_FIN_CLOCKS; tools/exp_fin_clocks.py): shader-clock values of the first conv
-// workgroup (layer 1, row 0: slots 0..), the first lin workgroup (16..) and the loss / tick workgroup (32..).  The product
-// build carries none of it.
+// Phase stamps (a variant library built with -DIGMC_FIN_CLOCKS; tools/exp_fin_clocks.py): shader-clock values of the first main
+// workgroup (layer 1, row 0: slots 0..), the first lin workgroup (16..), the loss / tick workgroup (32..), the first row
+// producer (layer 1, row 0, set 1: 40..) and layer 1's bias producer (48..).  The product build carries none of it.
 #if defined(IGMC_FIN_CLOCKS) && !defined(IGMC_HIPEMU)
 __device__ unsigned long long g_fin_clk[64];
 extern "C" int igmc_debug_fin_clocks(unsigned long long* out) {
@@ -2172,15 +2185,122 @@ extern "C" int igmc_debug_fin_clocks(unsigned long long* out) {
 #define TF_STAMP(on, k) do { } while (0)
 #endif
 
+// One set of <= 16 float4 columns of (layer, input row c) summed over the nq partial tables, the ONE body of the mains and the
+// producers of k_tail_fin: column k = (row j = k >> 3, float4 k & 7) for k0 <= k < k1 (j < R: dW_j[c], j == R: d root[c],
+// j == R + 1: the bias row); thread (o4, pg) sums the slots pg, pg + 16, .. of column k0 + o4 in order (14 sixteen-byte loads
+// in flight, all requested before the first add), wave 0 adds the 16 groups in index order through LDS (sred4: 1024 floats).
+// Returns, in wave 0, component (lane & 3) of column k0 + (lane >> 2): element lane of the set's 64 floats.  One barrier;
+// sred4 must not be in use by the workgroup.
+__device__ __forceinline__ float tf_sum_set(const float* __restrict__ pl, const TsSlots& sl, int ts, int R, int fin, int c,
+                                            int k0, int k1, float4* sred4) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int o4 = lane & 15, pg = wave * 4 + (lane >> 4);
+  const int k = k0 + o4, kc = k < k1 ? k : k1 - 1, j = kc >> 3;
+  const int row = j < R ? j * fin + c : j == R ? R * fin + c : R * fin + fin;
+  const int i0 = row * 32 + 4 * (kc & 7);
+  float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int nq = sl.nq;
+  for (int q0 = pg; q0 < nq; q0 += 16 * 14) {
+    float4 v[14];
+#pragma unroll
+    for (int u = 0; u < 14; ++u) v[u] = *(const float4*)(pl + (size_t)ts_slot(sl, q0 + 16 * u) * ts + i0);
+#pragma unroll
+    for (int u = 0; u < 14; ++u)
+      if (q0 + 16 * u < nq) {
+        s4.x += v[u].x; s4.y += v[u].y; s4.z += v[u].z; s4.w += v[u].w;
+      }
+  }
+  sred4[pg * 16 + o4] = s4;
+  __syncthreads();
+  float tot = 0.f;
+  if (wave == 0) {
+    const float* sr = (const float*)sred4;
+#pragma unroll
+    for (int g16 = 0; g16 < 16; ++g16) tot += sr[(g16 * 16 + (lane >> 2)) * 4 + (lane & 3)];
+  }
+  return tot;
+}
+
+// A row's share of d att[r,b] = <dW_r, basis_b> for the two relations r = r2 + h of a set (wave 0 only; half h = lane >> 5,
+// feature f = lane & 31; tot: dW_r[c][f], the lane's own element of the set; pvb: basis_b[c][f]): the butterfly of
+// reduce_ts_body inside a 32-lane half, published by the half's first lane as the launch's words
+__device__ __forceinline__ void tf_datt_pub(float tot, int r, int R, const float (&pvb)[4], unsigned long long* wrow, uint32_t tag,
+                                            bool mute) {
+  const int f = threadIdx.x & 31;
+  if (r >= R) tot = 0.f;
+  float pb[4];
+#pragma unroll
+  for (int bb = 0; bb < 4; ++bb) pb[bb] = tot * pvb[bb];
+#pragma unroll
+  for (int bb = 0; bb < 4; ++bb)
+#pragma unroll
+    for (int d = 16; d >= 1; d >>= 1) pb[bb] += __shfl_xor(pb[bb], d, 64);     // stays inside a 32-lane half
+  if (mute) return;      // (emulator's timeout test)
+  if (f == 0 && r < R) {
+#pragma unroll
+    for (int bb = 0; bb < 4; ++bb) g2_pub_f32_agent(wrow + r * 4 + bb, pb[bb], tag);
+  }
+}
+
 __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m, const float* P, float grad_scale, float mult,
                                                            float drop_scale, float* grad, float arr_coef, AdamTail at, int nlin,
-                                                           int nparts, int stride, int B, int bump_seq, int mute_layer) {
+                                                           int nparts, int stride, int B, int bump_seq, int mute) {
   __builtin_amdgcn_s_setprio(3);      // (step chain: ahead of the extraction chain's waves wherever the two share a SIMD)
   igmc_kernarg_warm<sizeof(BatchDev) + sizeof(ModelDev) + sizeof(AdamTail) + 64>();
   IGMC_DYN_SMEM(smem);
   float* S = (float*)smem;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* stash = m.fin_stash;
+  const int R = m.R, L = m.L, na = R * 4;
+  const int nconv = 96 + L;                 // mains -- layers 1..3: 32 workgroups each, then layer 0's L
+  const int ncol_a = 8 * (R + 1), nsets = (ncol_a + 15) >> 4;
+  const int nprod_r = (nsets - 1) * nconv, nprod = (nprod_r + 4 + 31) & ~31;      // row producers; + bias producers, padded
+  const int blk = blockIdx.x;
+#ifdef IGMC_HIPEMU
+  // (the timeout test: publishers of layer mute & 255 stay silent -- all of them, or (mute >> 8) 1: its row producers, 2: its bias producer)
+  const int mute_layer = mute < 0 ? -1 : (mute & 255), mute_role = mute < 0 ? 0 : (mute >> 8);
+#else
+  const int mute_layer = -1, mute_role = 0;
+#endif
+  TF_STAMP(blk == nprod, 0);
+  TF_STAMP(blk == nprod + nconv, 16);
+  TF_STAMP(blk == nprod + nconv + nlin, 32);
+  TF_STAMP(blk == 0, 40);
+  TF_STAMP(blk == nprod_r + 1, 48);
+  if (blk < nprod) {
+    // ---- producers: one set of one row summed and published; they wait for nothing
+    if (blk >= nprod_r + 4) return;      // (padding: the mains of a layer stay an aligned run of 32 workgroups)
+    const bool brow = blk >= nprod_r;
+    const int mi = brow ? 0 : blk / (nsets - 1), set = brow ? 0 : 1 + blk % (nsets - 1);
+    const int l = brow ? blk - nprod_r : mi < 96 ? 1 + (mi >> 5) : 0, c = brow ? 0 : mi < 96 ? (mi & 31) : mi - 96;
+    const int fin = (l == 0) ? L : 32, nE = fin * 32, ts = m.ts_stride;
+    const uint32_t tag = __float_as_uint(stash[IGMC_STASH_SCAL + IGMC_STASH_SEQ]) * 2u + 1u;      // (never 0)
+    // the basis values of the d att products are requested with the table loads.  The main (l, c) updates these parameters
+    // only behind its poll of the layer's words, this workgroup's among them: the read is ordered before that write by data
+    // dependence
+    float pvb[4] = {0.f, 0.f, 0.f, 0.f};
+    if (wave == 0 && !brow) {
+#pragma unroll
+      for (int bb = 0; bb < 4; ++bb) pvb[bb] = P[m.off_basis[l] + (int64_t)bb * nE + c * 32 + (lane & 31)];
+    }
+    TF_STAMP(blk == 0, 41);
+    TF_STAMP(blk == nprod_r + 1, 49);
+    const TsSlots sl = ts_slots(nparts, stride, B);
+    const int k0 = brow ? ncol_a : 16 * set, k1 = brow ? ncol_a + 8 : (k0 + 16 < ncol_a ? k0 + 16 : ncol_a);
+    const float tot = tf_sum_set(m.ts_part + (size_t)l * IGMC_TS_BLOCKS * ts, sl, ts, R, fin, c, k0, k1, (float4*)S);
+    TF_STAMP(blk == 0, 42);
+    TF_STAMP(blk == nprod_r + 1, 50);
+    if (wave == 0) {
+      const bool silent = l == mute_layer && mute_role != (brow ? 1 : 2);
+      unsigned long long* w = brow ? m.fold_w + IGMC_FOLD_O_BIAS + l * 32
+                                   : m.fold_w + IGMC_FOLD_O_ROWS + (size_t)((l * 32 + c) * IGMC_FOLD_PSETS + set - 1) * 64;
+      if (!silent && k0 + (lane >> 2) < k1) g2_pub_f32_agent(w + lane, tot, tag);
+      if (!brow) tf_datt_pub(tot, 2 * set + (lane >> 5), R, pvb, m.fold_w + (size_t)(l * 32 + c) * IGMC_FOLD_NA, tag, silent);
+    }
+    TF_STAMP(blk == 0, 43);
+    TF_STAMP(blk == nprod_r + 1, 51);
+    return;
+  }
   if (at.ctrl) {      // hipGraph replay: the Adam scalars of the step, stashed in the launch in front
     at.step_size = stash[IGMC_STASH_SCAL + 0];
     at.inv_sqrt_bc2 = stash[IGMC_STASH_SCAL + 1];
@@ -2189,25 +2309,19 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m,
     at.eps = stash[IGMC_STASH_SCAL + 4];
     at.wd = stash[IGMC_STASH_SCAL + 5];
   }
-  const int R = m.R, L = m.L, na = R * 4;
-  const int nconv = 96 + L;                 // layers 1..3: 32 workgroups each, then layer 0's L
-  const int blk = blockIdx.x;
-  TF_STAMP(blk == 0, 0);
-  TF_STAMP(blk == nconv, 16);
-  TF_STAMP(blk == nconv + nlin, 32);
-  if (blk < nconv) {
-    const int l = blk < 96 ? 1 + (blk >> 5) : 0, c = blk < 96 ? (blk & 31) : blk - 96;
+  const int mb = blk - nprod;
+  if (mb < nconv) {
+    const int l = mb < 96 ? 1 + (mb >> 5) : 0, c = mb < 96 ? (mb & 31) : mb - 96;
     const int fin = (l == 0) ? L : 32, nE = fin * 32, ts = m.ts_stride;
     const uint32_t tag = __float_as_uint(stash[IGMC_STASH_SCAL + IGMC_STASH_SEQ]) * 2u + 1u;      // (never 0)
-    float4* sred4 = (float4*)S;                       // [set][16 partial groups][16 columns]
-    float* rows = S + IGMC_TF_O_ROWS;                 // [R dW_r[c] | d root[c] | d bias (c == 0)][32]
+    float4* sred4 = (float4*)S;                       // [16 partial groups][16 columns]
+    float* rows = S + IGMC_TF_O_ROWS;                 // [R dW_r[c] | d root[c] | d bias][32]
     float* s_st = S + IGMC_TF_O_ST;                   // the layer's stash
     float* s_datt = S + IGMC_TF_O_DATT;               // [fin][IGMC_FOLD_NA] the layer's d att partial products
     float* s_attn = S + IGMC_TF_O_ATTN;               // the layer's att after the step
     float* s_pn = S + IGMC_TF_O_PN;                   // [5][32] the columns' basis_0..3 / root after the step
     int* s_flag = (int*)(S + IGMC_TF_O_SMF + 8);      // a poll of the workgroup ran out
     const int ng = g2_groups(R, L);
-    const int o4 = lane & 15, pg = wave * 4 + (lane >> 4);
     // ---- every load that does not depend on another workgroup is requested here, in front of the partial tables: the layer's
     // stash, the column threads' (tid < 32: f = tid) parameters and moments, wave 0's basis values for the d att products
     // (both 32-lane halves: f = lane & 31), the bias role's (c == 0: tid 32..63)
@@ -2239,111 +2353,45 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m,
       bq[3] = at.m2[i];
     }
     if (tid == 0) *s_flag = 0;
-    TF_STAMP(blk == 0, 1);      // the independent loads are requested
-    // ---- the rows of this workgroup, summed over the partial tables: column k = (row j = k >> 3, float4 k & 7) in sets of 16
-    // columns, IGMC_TF_SETS sets a round (<= 42 sixteen-byte loads a thread, all requested before the first add).  The rows the
-    // d att products need -- dW_r[c] and d root[c], one round up to five relations -- come first; the bias row (c == 0) is a
-    // round of its own BEHIND the hand-off, under the wait for the other workgroups' words
-    const float* pl = m.ts_part + (size_t)l * IGMC_TS_BLOCKS * ts;
+    TF_STAMP(mb == 0, 1);      // the independent loads are requested
+    // ---- set 0 of this workgroup's rows (dW_0[c] | dW_1[c], or d root[c] behind the last relation) summed over the partial
+    // tables; the other sets and the bias row arrive as words from their producers
     const TsSlots sl = ts_slots(nparts, stride, B);
-    const int nq = sl.nq;
-    bool first_round = true;
-    auto sum_columns = [&](int k0, int k1) {      // columns k0 .. k1 - 1 (k1 - k0 <= 16 IGMC_TF_SETS) -> rows
-      const int nsets = (k1 - k0 + 15) >> 4;
-      int i0[IGMC_TF_SETS];
-      float4 s4[IGMC_TF_SETS];
 #pragma unroll
-      for (int s = 0; s < IGMC_TF_SETS; ++s) {
-        const int k = k0 + 16 * s + o4, kc = k < k1 ? k : k1 - 1, j = kc >> 3;
-        const int row = j < R ? j * fin + c : j == R ? R * fin + c : R * fin + fin;
-        i0[s] = row * 32 + 4 * (kc & 7);
-        s4[s] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      for (int q0 = pg; q0 < nq; q0 += 16 * 14) {
-        float4 v[IGMC_TF_SETS][14];
-        size_t so[14];
-#pragma unroll
-        for (int u = 0; u < 14; ++u) so[u] = (size_t)ts_slot(sl, q0 + 16 * u) * ts;
-#pragma unroll
-        for (int s = 0; s < IGMC_TF_SETS; ++s)
-          if (s < nsets) {      // (uniform over the workgroup)
-#pragma unroll
-            for (int u = 0; u < 14; ++u) v[s][u] = *(const float4*)(pl + so[u] + i0[s]);
-          }
-#pragma unroll
-        for (int s = 0; s < IGMC_TF_SETS; ++s)
-          if (s < nsets) {
-#pragma unroll
-            for (int u = 0; u < 14; ++u)
-              if (q0 + 16 * u < nq) {
-                s4[s].x += v[s][u].x; s4[s].y += v[s][u].y; s4[s].z += v[s][u].z; s4[s].w += v[s][u].w;
-              }
-          }
-      }
-      if (!first_round) __syncthreads();      // (the groups' sums of the round before have been read)
-#pragma unroll
-      for (int s = 0; s < IGMC_TF_SETS; ++s)
-        if (s < nsets) sred4[(s * 16 + pg) * 16 + o4] = s4[s];
-      if (first_round) {
-#pragma unroll
-        for (int u = 0; u < (IGMC_STASH_LAYER + IGMC_BLOCK - 1) / IGMC_BLOCK; ++u) {
-          const int i = tid + u * IGMC_BLOCK;
-          if (i < IGMC_STASH_LAYER) s_st[i] = stq[u];
-        }
-      }
-      first_round = false;
-      __syncthreads();
-      if (wave < nsets) {
-        // wave -> set, lane -> component (lane & 3) of column (lane >> 2): the 16 groups in index order
-        const float* sr = (const float*)sred4;
-        float tot = 0.f;
-#pragma unroll
-        for (int g16 = 0; g16 < 16; ++g16) tot += sr[((wave * 16 + g16) * 16 + (lane >> 2)) * 4 + (lane & 3)];
-        const int k = k0 + 16 * wave + (lane >> 2);
-        if (k < k1) rows[k * 4 + (lane & 3)] = tot;
-      }
-    };
-    const int ncol_a = 8 * (R + 1);
-    for (int k0 = 0; k0 < ncol_a; k0 += 16 * IGMC_TF_SETS) sum_columns(k0, k0 + 16 * IGMC_TF_SETS < ncol_a ? k0 + 16 * IGMC_TF_SETS : ncol_a);
-    __syncthreads();
-    TF_STAMP(blk == 0, 2);      // the rows are reduced (the partial tables' round trip)
-    // ---- this row's share of d att[r,b] = <dW_r, basis_b>: 32 features, the butterfly of reduce_ts_body inside a 32-lane half
-    // (half h takes the relations h, h + 2, ..), published by the half's first lane
-    unsigned long long* words = m.fold_w + (size_t)l * 32 * IGMC_FOLD_NA;
-    if (wave == 0) {
-      const int h = lane >> 5;
-      for (int r2 = 0; r2 < R; r2 += 2) {
-        const int r = r2 + h;
-        const float tot = r < R ? rows[r * 32 + f] : 0.f;
-        float pb[4];
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) pb[bb] = tot * pvb[bb];
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb)
-#pragma unroll
-          for (int d = 16; d >= 1; d >>= 1) pb[bb] += __shfl_xor(pb[bb], d, 64);     // stays inside a 32-lane half
-#ifdef IGMC_HIPEMU
-        if (l == mute_layer) continue;      // (the timeout test: this layer publishes nothing)
-#endif
-        if (f == 0 && r < R) {
-#pragma unroll
-          for (int bb = 0; bb < 4; ++bb) g2_pub_f32_agent(words + c * IGMC_FOLD_NA + r * 4 + bb, pb[bb], tag);
-        }
-      }
+    for (int u = 0; u < (IGMC_STASH_LAYER + IGMC_BLOCK - 1) / IGMC_BLOCK; ++u) {
+      const int i = tid + u * IGMC_BLOCK;
+      if (i < IGMC_STASH_LAYER) s_st[i] = stq[u];
     }
-    TF_STAMP(blk == 0, 3);      // the row's words are published
-    if (c == 0) sum_columns(ncol_a, ncol_a + 8);      // the bias row (read behind the barrier below)
-    TF_STAMP(blk == 0, 4);      // ... and the bias row is summed (c == 0 only)
-    // ---- the layer's fin x 4 R words: <= IGMC_TF_POLL a thread, looked at together until every one carries the launch's tag
+    const float tot = tf_sum_set(m.ts_part + (size_t)l * IGMC_TS_BLOCKS * ts, sl, ts, R, fin, c, 0, ncol_a < 16 ? ncol_a : 16, sred4);
+    if (wave == 0 && (lane >> 2) < ncol_a) rows[lane] = tot;
+    TF_STAMP(mb == 0, 2);      // the set is reduced (the partial tables' round trip)
+    // ---- this row's share of d att for the relations of set 0
+    unsigned long long* words = m.fold_w + (size_t)l * 32 * IGMC_FOLD_NA;
+    if (wave == 0) tf_datt_pub(tot, lane >> 5, R, pvb, words + c * IGMC_FOLD_NA, tag, l == mute_layer && mute_role == 0);
+    TF_STAMP(mb == 0, 3);      // the row's words are published
+    // ---- the words this workgroup needs, in ONE loop: its row's other sets, the layer's fin x 4 R d att products and the
+    // layer's bias row -- <= IGMC_TF_POLL a thread, looked at together until every one carries the launch's tag; each goes to
+    // its place in LDS (rows / s_datt)
     {
-      const int nw = fin * na;
+      const int nrw = 4 * ncol_a - 64, ndw = fin * na, nw = nrw + ndw + 32, npoll = (nw + IGMC_BLOCK - 1) / IGMC_BLOCK;
+      const unsigned long long* wrow = m.fold_w + IGMC_FOLD_O_ROWS + (size_t)(l * 32 + c) * IGMC_FOLD_PSETS * 64;
       const unsigned long long* wp[IGMC_TF_POLL];
-      int wi[IGMC_TF_POLL];
+      int wi[IGMC_TF_POLL];      // destination, in floats of S
 #pragma unroll
       for (int u = 0; u < IGMC_TF_POLL; ++u) {
         const int w = tid + u * IGMC_BLOCK, wc = w < nw ? w : nw - 1;
-        wi[u] = (wc / na) * IGMC_FOLD_NA + wc % na;
-        wp[u] = words + wi[u];
+        if (wc < nrw) {                  // (sets 1.. are contiguous: [set - 1][64])
+          wp[u] = wrow + wc;
+          wi[u] = IGMC_TF_O_ROWS + 64 + wc;
+        } else if (wc < nrw + ndw) {
+          const int x = wc - nrw, y = (x / na) * IGMC_FOLD_NA + x % na;
+          wp[u] = words + y;
+          wi[u] = IGMC_TF_O_DATT + y;
+        } else {
+          const int x = wc - nrw - ndw;
+          wp[u] = m.fold_w + IGMC_FOLD_O_BIAS + l * 32 + x;
+          wi[u] = IGMC_TF_O_ROWS + (R + 1) * 32 + x;
+        }
       }
       bool ok = false;
 #ifndef IGMC_HIPEMU
@@ -2353,12 +2401,14 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m,
         unsigned long long w[IGMC_TF_POLL];
         bool all = true;
 #pragma unroll
-        for (int u = 0; u < IGMC_TF_POLL; ++u) w[u] = g2_ld_word(wp[u]);
+        for (int u = 0; u < IGMC_TF_POLL; ++u)
+          if (u < npoll) w[u] = g2_ld_word(wp[u]);      // (uniform over the workgroup)
 #pragma unroll
-        for (int u = 0; u < IGMC_TF_POLL; ++u) all = all && (uint32_t)(w[u] >> 32) == tag;
+        for (int u = 0; u < IGMC_TF_POLL; ++u) all = all && (u >= npoll || (uint32_t)(w[u] >> 32) == tag);
         if (all) {
 #pragma unroll
-          for (int u = 0; u < IGMC_TF_POLL; ++u) s_datt[wi[u]] = __uint_as_float((uint32_t)w[u]);     // (clamped repeats: the same value again)
+          for (int u = 0; u < IGMC_TF_POLL; ++u)
+            if (u < npoll) S[wi[u]] = __uint_as_float((uint32_t)w[u]);     // (clamped repeats: the same value again)
           ok = true;
           break;
         }
@@ -2373,7 +2423,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m,
       if (!ok) *s_flag = 1;
     }
     __syncthreads();
-    TF_STAMP(blk == 0, 5);      // the layer's words are in
+    TF_STAMP(mb == 0, 5);      // the words are in
     if (*s_flag) {      // nothing of this workgroup's is updated
       if (tid == 0) {
         *m.gs_err = 1;
@@ -2406,7 +2456,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m,
 #pragma unroll
       for (int q = 0; q < 5; ++q) s_pn[q * 32 + f] = pn[q];
     }
-    TF_STAMP(blk == 0, 6);      // the main pass is stored
+    TF_STAMP(mb == 0, 6);      // the main pass is stored
     __syncthreads();
     {   // the image words of the 32 columns: thread -> (relation tid >> 5 of eight at a time, column f)
       float pn[5];
@@ -2414,14 +2464,14 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m,
       for (int q = 0; q < 5; ++q) pn[q] = s_pn[q * 32 + f];
       fts_image_col(m, ng, l, R, fin, c, f, s_attn, pn, tid >> 5, IGMC_BLOCK / 32);
     }
-    TF_STAMP(blk == 0, 7);      // the image words are stored
-  } else if (blk < nconv + nlin) {
+    TF_STAMP(mb == 0, 7);      // the image words are stored
+  } else if (mb < nconv + nlin) {
     // ---- d lin1 / d lin2 and Adam on exactly the elements this workgroup formed: the 16 x 64 tile of lin1.weight and, for the
     // first column tile, 16 entries of lin1.bias / lin2.weight (+ lin2.bias)
-    const int bx = (blk - nconv) & 7, by = (blk - nconv) >> 3, D = m.D;
+    const int bx = (mb - nconv) & 7, by = (mb - nconv) >> 3, D = m.D;
     head_bwd_w_body(b, m, P, nullptr, 1, grad_scale, mult, drop_scale, grad, bx, by, B);
     __syncthreads();
-    TF_STAMP(blk == nconv, 17);      // the tile's gradient is formed
+    TF_STAMP(mb == nconv, 17);      // the tile's gradient is formed
     int64_t ix[5];
     bool okx[5];
     float gv[5], pv[5], av[5], vv[5];
@@ -2446,7 +2496,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m,
     for (int k = 0; k < 5; ++k)
       if (okx[k]) adam_store_sep(at.p, at.m1, at.m2, ix[k], gv[k], pv[k], av[k], vv[k], at.step_size, at.inv_sqrt_bc2, at.beta1,
                                  at.beta2, at.eps, at.wd);      // (adam_range's bits: k_finalize_ts's lin workgroups)
-    TF_STAMP(blk == nconv, 18);
+    TF_STAMP(mb == nconv, 18);
   } else {                                                     // loss, epoch total, control-block tick, sequence number
     if (bump_seq && tid == 0) m.gs_bar[1] += 1;               // (every workgroup of k_graph_step2 is done)
     loss_body(at.b, m, at.ARR, at.loss, at.total, S + IGMC_TF_O_SMF);
@@ -2664,15 +2714,21 @@ static void launch_tail_fin(const ModelDev& m, const BatchDev& b, const float* P
                             float arr_coef, const AdamTail& at, int nlin, int nparts, int stride, int bump_seq, void* stream) {
   int mute = -1;
 #ifdef IGMC_HIPEMU
-  // (emulator only -- the timeout test: the workgroups of this layer publish nothing, its pollers give up)
-  if (const char* e = getenv("IGMC_EMU_FOLD_MUTE")) mute = atoi(e);
-  // the workgroups of a layer wait for each other's words: they run together (32 consecutive workgroups = layer 1, 2, 3, then
-  // layer 0's in front of the lin workgroups)
+  // (emulator only -- the timeout test: the publishers of this layer stay silent and its pollers give up; with
+  // IGMC_EMU_FOLD_MUTE_ROLE=rows / bias only the layer's row producers / its bias producer)
+  if (const char* e = getenv("IGMC_EMU_FOLD_MUTE")) {
+    mute = atoi(e);
+    const char* role = getenv("IGMC_EMU_FOLD_MUTE_ROLE");
+    if (mute >= 0 && role) mute |= (!strcmp(role, "rows") ? 1 : !strcmp(role, "bias") ? 2 : 0) << 8;
+  }
+  // the mains of a layer wait for each other's words and for producers: aligned groups of 32 consecutive workgroups run
+  // together, one group after the other (layout: above k_tail_fin)
   hipemu::rt().co_cs = 32;
   hipemu::rt().co_stride = -1;
   hipemu::rt().co_block = 0;
 #endif
-  IGMC_PLAUNCH("k_tail_fin", k_tail_fin, 96 + m.L + nlin + 1, IGMC_BLOCK, (size_t)IGMC_TF_WORDS * sizeof(float), stream, b, m, P,
+  const int nconv = 96 + m.L, nsets = (8 * (m.R + 1) + 15) / 16, nprod = ((nsets - 1) * nconv + 4 + 31) & ~31;
+  IGMC_PLAUNCH("k_tail_fin", k_tail_fin, nprod + nconv + nlin + 1, IGMC_BLOCK, (size_t)IGMC_TF_WORDS * sizeof(float), stream, b, m, P,
                grad_scale, mult, 2.f, grad, arr_coef, at, nlin, nparts, stride, B, bump_seq, mute);
 }
 

@@ -168,7 +168,7 @@ void igmc_step_plan(const ModelDev& m, const BatchDev& b, int B, int kind, StepP
     p->tail = fts ? IGMC_TAIL_TS : IGMC_TAIL_HANDOFF;
     p->exchange_inside = fused && fts;
     // the tail as ONE launch (k_tail_fin): a workgroup per input row of a layer, which takes no more than 32 of them and hands
-    // over no more than IGMC_FOLD_NA d att entries.  The call decides the rest: Adam with the weight images, no exchange
+    // over no more than IGMC_FOLD_NA d att entries (R <= 8: also no more than IGMC_FOLD_PSETS row producers a row).  The call decides the rest: Adam with the weight images, no exchange
     // (the four stash workgroups appended to the subgraph kernel's launch take a CU each -- the launch's dynamic LDS -- and are
     //  resident with the rest: a clustered grid is <= 224 on >= 240 CUs (gs_cluster), any other <= IGMC_WG_BLOCKS)
     p->tail_fold = fused && fts && hk.tail_fold != 0 && m.fold_w && m.L <= 32 && 4 * m.R <= IGMC_FOLD_NA;

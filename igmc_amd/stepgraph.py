@@ -30,6 +30,7 @@ the step's stream) sits between the gradient kernels and the Adam kernel of ever
 runtime refuses to capture it the same launches run eagerly.
 """
 import ctypes as C
+import gc
 import os
 import struct
 import sys
@@ -688,6 +689,11 @@ class StepGraph(GroupPipeline):
         for qq in (0, 1):                   # (arenas and arena sets are created on first use: never inside a capture)
             self._arena(qq, self.M - 1)
             self._batch_sets(qq)
+        # finalizers of unreachable workspaces, arenas and graphs free device memory, which a capture that polices every thread
+        # does not survive: what is garbage goes now, and the cyclic collector stays off until the capture has ended
+        gc.collect()
+        gc_on = gc.isenabled()
+        gc.disable()
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         dist = parallel.is_dist()
@@ -704,6 +710,9 @@ class StepGraph(GroupPipeline):
                              % str(e).splitlines()[0])
             self.use_graph, self.graph, self.graph1, g = False, None, [None, None], None
             torch.cuda.synchronize()
+        finally:
+            if gc_on:
+                gc.enable()
         # every rank is through its capture (or has given it up) before any rank replays: the first replay of a fast rank
         # would otherwise poll the exchange words of a rank that is still capturing (the polls are bounded by wall-clock time)
         if self.comm is not None:
