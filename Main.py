@@ -96,6 +96,10 @@ def build_parser():
                    help='rank the held-out links (test split under --testing, else validation split) among every user\'s '
                         'unseen items on the device, write hr / recall / precision / ndcg @K and mrr, and stop; uses '
                         '--recommend-users to restrict the users')
+    p.add_argument('--new-ratings', default=None, metavar='FILE',
+                   help='rating changes applied to the training graph ON THE DEVICE before --recommend / --rank-eval: lines '
+                        '"user item rating" (ids as recommendations_*.tsv prints them, "#" comments; rating 0 removes the '
+                        'entry, ids beyond the graph create new users / items)')
     p.add_argument('--rank-min-rating', type=float, default=None, metavar='X',
                    help='--rank-eval: only held-out links rated >= X are relevant (default: all of them)')
     p.add_argument('--ensemble', action='store_true', default=False)
@@ -196,8 +200,30 @@ def write_ranking(model, train_graphs, heldout_graphs, args):
     return path
 
 
+def apply_new_ratings(train_graphs, class_values, args):
+    """``--new-ratings FILE``: the training set's extraction settings over its rating graph after the file's changes
+    (``engine.Graph.updated``: built on the device, the training graph itself stays as it is)."""
+    import time
+    from igmc_amd.new_ratings import read_new_ratings
+    from igmc_amd.recommend import GraphView
+    u, v, r = read_new_ratings(args.new_ratings, class_values)
+    old = train_graphs.graph
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    graph = old.updated(u, v, r)          # (synchronous)
+    dt = time.perf_counter() - t0
+    print('Applied {} rating change(s) on the device in {:.3f} ms: {} x {} with {} ratings -> {} x {} with {}'.format(
+        len(u), dt * 1e3, old.n_users, old.n_items, old.nnz, graph.n_users, graph.n_items, graph.nnz))
+    return GraphView(train_graphs, graph)
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    from igmc_amd.new_ratings import flag_error
+    bad = flag_error(args.new_ratings, args.recommend, args.rank_eval, args.use_features)
+    if bad:
+        parser.error(bad)
     rank, world = parallel.init_from_env()
     torch.manual_seed(args.seed)
     if torch.cuda.is_available():
@@ -335,10 +361,11 @@ def main(argv=None):
             rank_eval_ks(args.rank_eval)
         model.load_state_dict(torch.load(args.model_pos, map_location='cpu'))
         if rank == 0:
+            over = apply_new_ratings(train_graphs, class_values, args) if args.new_ratings else train_graphs
             if args.recommend > 0:
-                write_recommendations(model, train_graphs, args)
+                write_recommendations(model, over, args)
             if args.rank_eval:
-                write_ranking(model, train_graphs, test_graphs, args)
+                write_ranking(model, over, test_graphs, args)
         parallel.barrier()
         return rmse
 

@@ -28,6 +28,9 @@ SIGNATURES = {
     'igmc_graph_create': (i32, [i32, i32, i64, vp, vp, vp, i32, C.POINTER(vp)]),
     'igmc_graph_destroy': (None, [vp]),
     'igmc_graph_hbm_bytes': (i64, [vp]),
+    'igmc_graph_apply': (i32, [vp, i32, i32, vp, vp, vp, i64, vp, C.POINTER(vp)]),
+    'igmc_graph_info': (i32, [vp, vp]),
+    'igmc_graph_download': (i32, [vp, vp, vp, vp, vp, vp, vp]),
     'igmc_batch_create': (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
     'igmc_batch_destroy': (None, [vp]),
     'igmc_extract_batch': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f64, u64, u64, vp]),

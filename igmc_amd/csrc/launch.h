@@ -101,6 +101,33 @@ void igmc_launch_rank_segments(const float* keys, const int32_t* ids, int64_t n,
                                int32_t* err, void* stream);
 void igmc_launch_rank_metrics(const int32_t* q_rank, const int64_t* q_off, const uint8_t* q_rel, const int32_t* ks, int nk,
                               int ns, int64_t nq, int grid, int32_t* cnt, double* dcg, int32_t* err, void* stream);
+// graph_update.hip: rating changes applied to a resident graph -- one orientation at a time (side 0: rows are users, side 1:
+// rows are items).  plan: the sorted change list, the new row lengths, their prefix sums, nnz and the longest row; write: the
+// rows of the new graph, once the caller has read nnz and allocated them.
+struct GuStats {
+  int32_t err;              // bit 0: a user id out of range, bit 1: an item id out of range, bit 2: nnz does not fit int32
+  int32_t max_deg[2];
+  int32_t max_rel;
+  long long nnz[2];
+};
+struct GuSide {
+  const int32_t* optr;      // the old graph's arrays of this orientation
+  const int32_t* oidx;
+  const uint8_t* orel;
+  int rows_old, rows_new;
+  unsigned long long* keys; // [padded n] sorted (row << 32 | col) words
+  uint32_t* idx;            // [padded n] their list positions
+  int16_t* s_new;           // [n] -1: overridden, 0: the winner removes, else the winner's rating
+  int16_t* s_old;           // [n] a winner's relation in the old row, or -1
+  uint8_t* touched;         // [rows_new] the row has changes in the list
+  int32_t* nptr;            // the new graph's arrays
+  int32_t* nidx;
+  uint8_t* nrel;
+};
+int64_t igmc_graph_update_padded(int64_t n);
+void igmc_launch_graph_update_plan(const GuSide& s, int side, const int32_t* user, const int32_t* item, const uint8_t* rating,
+                                   int64_t n, int n_users, int n_items, GuStats* st, void* stream);
+void igmc_launch_graph_update_write(const GuSide& s, int side, int64_t n, int64_t nnz_old, GuStats* st, void* stream);
 int igmc_model_prepare(const ModelDev& m);
 void igmc_launch_adam(float* p, const float* g, float* m1, float* m2, int64_t n, float step_size,
                       float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd, int64_t* ctrl, int tick,

@@ -48,6 +48,91 @@ class Graph(object):
     def hbm_bytes(self):
         return int(self.lib.igmc_graph_hbm_bytes(self.handle))
 
+    @classmethod
+    def _from_handle(cls, handle, device, lib):
+        self = cls.__new__(cls)
+        self.lib, self.handle, self.device = lib, handle, device
+        i = self.info()
+        self.n_users, self.n_items, self.nnz, self.max_rel = i['n_users'], i['n_items'], i['nnz'], i['max_rel']
+        return self
+
+    def info(self):
+        """The six sizes of ``igmc_graph_info``."""
+        out = np.zeros(6, np.int64)
+        self.lib.call('igmc_graph_info', self.handle, _p(out))
+        return dict(zip(('n_users', 'n_items', 'nnz', 'max_rel', 'max_deg_u', 'max_deg_v'), (int(x) for x in out)))
+
+    def download(self):
+        """The resident arrays on the host: ``u_ptr``, ``u_idx``, ``u_rel`` (rows by (relation, item)), ``v_ptr``, ``v_idx``,
+        ``v_rel`` (columns by (relation, user))."""
+        i = self.info()
+        d = dict(u_ptr=np.zeros(i['n_users'] + 1, np.int32), u_idx=np.zeros(i['nnz'], np.int32), u_rel=np.zeros(i['nnz'], np.uint8),
+                 v_ptr=np.zeros(i['n_items'] + 1, np.int32), v_idx=np.zeros(i['nnz'], np.int32), v_rel=np.zeros(i['nnz'], np.uint8))
+        self.lib.call('igmc_graph_download', self.handle, _p(d['u_ptr']), _p(d['u_idx']), _p(d['u_rel']), _p(d['v_ptr']),
+                      _p(d['v_idx']), _p(d['v_rel']))
+        return d
+
+    def to_scipy(self):
+        """The rating matrix as a CSR with values rating label + 1 (what the constructor takes)."""
+        import scipy.sparse as ssp
+        d = self.download()
+        A = ssp.csr_matrix((d['u_rel'].astype(np.float32) + 1.0, d['u_idx'], d['u_ptr']), shape=(self.n_users, self.n_items))
+        A.sort_indices()
+        return A
+
+    def updated(self, users, items, ratings, n_users=None, n_items=None, stream=None):
+        """A NEW graph: this one after ``A[users[j], items[j]] = ratings[j]`` for j = 0, 1, .. in order (``igmc_graph_apply``:
+        ratings are rating label + 1, 0 removes the entry, the last assignment of a pair wins), built on the device; this
+        graph and everything bound to it stay as they are.  ``users`` / ``items`` / ``ratings``: integer arrays of one length,
+        host (numpy, lists) or device (torch).  ``n_users`` / ``n_items``: the new sizes, by default the larger of the present
+        size and the greatest id + 1 -- ids beyond the graph create new, otherwise empty, rows and columns."""
+        keep = []
+        u, mu = self._change_array(users, np.int32, 'users', keep)
+        v, mv = self._change_array(items, np.int32, 'items', keep)
+        r, _ = self._change_array(ratings, np.uint8, 'ratings', keep)
+        if not len(u) == len(v) == len(r):
+            raise ValueError('users, items and ratings differ in length')
+        n_users = max(self.n_users, mu + 1) if n_users is None else int(n_users)
+        n_items = max(self.n_items, mv + 1) if n_items is None else int(n_items)
+        if stream is None and keep and hasattr(keep[0], 'data_ptr'):
+            import torch
+            stream = torch.cuda.current_stream().cuda_stream
+        h = C.c_void_p()
+        ptr = lambda a: _p(a.data_ptr() if hasattr(a, 'data_ptr') else a) if len(a) else None
+        self.lib.call('igmc_graph_apply', self.handle, n_users, n_items, ptr(u), ptr(v), ptr(r), len(u), _p(stream), C.byref(h))
+        return Graph._from_handle(h, self.device, self.lib)
+
+    def _change_array(self, x, dtype, what, keep):
+        """``x`` as a contiguous array of ``dtype`` where the library reads it (the GPU for the product library; the host
+        emulation build of the tests reads numpy memory) and its greatest entry (-1: none)."""
+        if hasattr(x, 'data_ptr'):          # a torch tensor, host or device
+            import torch
+            if x.dim() != 1 or x.dtype.is_floating_point or x.dtype == torch.bool:
+                raise ValueError('%s: a 1-D integer array' % what)
+            top = int(x.max().item()) if x.numel() else -1
+            low = int(x.min().item()) if x.numel() else 0
+            if dtype == np.uint8 and (low < 0 or top > 255):
+                raise ValueError('ratings must be rating label + 1 in 1..255, or 0 to remove')
+            t = x.to(device='cuda:%d' % self.device, dtype=torch.uint8 if dtype == np.uint8 else torch.int32).contiguous()
+            keep.append(t)
+            return t, top
+        a = np.asarray(x)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in 'iu'):
+            raise ValueError('%s: a 1-D integer array' % what)
+        top = int(a.max()) if a.size else -1
+        if dtype == np.uint8 and a.size and (int(a.min()) < 0 or top > 255):
+            raise ValueError('ratings must be rating label + 1 in 1..255, or 0 to remove')
+        if a.size and (int(a.min()) < -2 ** 31 or top >= 2 ** 31):
+            raise ValueError('%s: ids must fit int32' % what)
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if self.lib is _lib._cached:        # the product library reads device memory
+            import torch
+            t = torch.from_numpy(a).to('cuda:%d' % self.device)
+            keep.append(t)
+            return t, top
+        keep.append(a)
+        return a, top
+
     def close(self):
         if getattr(self, 'handle', None):
             self.lib.igmc_graph_destroy(self.handle)

@@ -49,6 +49,33 @@ def _dev_int32(x, dev, what):
     return t.to(device=dev, dtype=torch.int32).contiguous()
 
 
+def _refuse_side_features(dataset):
+    if getattr(dataset, '_side', None) is not None or getattr(dataset, 'u_features', None) is not None or \
+            getattr(dataset, 'v_features', None) is not None:
+        raise NotImplementedError('candidate links carry no side features: recommend over a dataset built without '
+                                  '--use-features (u_features / v_features)')
+
+
+class GraphView(object):
+    """The extraction settings of ``dataset`` over ANOTHER rating graph -- normally ``dataset.graph.updated(...)``, the
+    graph after new ratings (``engine.Graph.updated``: built on the device) --, shaped like a dataset as far as
+    :class:`CandidateLinks` reads one: ``graph``, ``device``, ``h``, ``sample_ratio``, ``seed``, ``max_nodes_per_hop``, a
+    ``link_y`` on the dataset's device (empty: a view has no links of its own) and no side features.  :func:`recommend`,
+    :func:`candidate_passes`, :func:`score_candidates` and ``rank_eval.rank_eval`` take it as they take a dataset; users and
+    items the graph gained are scored from their enclosing subgraphs like any other.  A dataset with side features is
+    refused: new users have no feature rows."""
+
+    def __init__(self, dataset, graph):
+        _refuse_side_features(dataset)
+        self.source = dataset
+        self.graph = graph
+        self.device = dataset.device
+        self.h, self.sample_ratio, self.seed = dataset.h, dataset.sample_ratio, dataset.seed
+        self.max_nodes_per_hop = dataset.max_nodes_per_hop
+        self.link_y = torch.zeros(0, dtype=torch.float32, device=dataset.link_y.device)
+        self._side, self.u_features, self.v_features = None, None, None
+
+
 class CandidateLinks(object):
     """Links without labels over the rating graph of an existing dataset, shaped like a dataset (``link_u``, ``link_v``,
     ``link_y``, ``extract``, ``arena``, ``h``, ``seed``, ``max_nodes_per_hop``, ``sample_ratio``, ``num_features``,
@@ -60,10 +87,7 @@ class CandidateLinks(object):
     dynamic = True          # subgraphs are extracted on the fly, under the sampling key of the pass
 
     def __init__(self, dataset, capacity):
-        if getattr(dataset, '_side', None) is not None or getattr(dataset, 'u_features', None) is not None or \
-                getattr(dataset, 'v_features', None) is not None:
-            raise NotImplementedError('candidate links carry no side features: recommend over a dataset built without '
-                                      '--use-features (u_features / v_features)')
+        _refuse_side_features(dataset)
         capacity = int(capacity)
         if not 1 <= capacity <= _INT32_MAX:
             raise ValueError('capacity must be in [1, 2^31): link positions are int32')

@@ -374,6 +374,32 @@ int64_t igmc_select_scratch_bytes(int64_t n, int num, int grid);
 int igmc_select_extremes(const float* d_keys, int64_t n, int num, int32_t* d_idx_low, int32_t* d_idx_high, float* d_key_low,
                          float* d_key_high, int32_t* d_count, void* d_scratch, int64_t scratch_bytes, int grid, void* stream);
 
+/* ---- Rating changes applied to a resident graph (no reference counterpart: the reference rebuilds SparseRowIndexer /
+ * SparseColIndexer from scratch, util_functions.py:20-66, and so does igmc_graph_create, through the host).
+ *
+ * igmc_graph_apply is a FUNCTIONAL update: *out is a new graph, g -- and every arena and captured launch bound to it -- stays
+ * valid.  d_user / d_item (int32) / d_rating (uint8) are DEVICE arrays of n >= 0 changes; the result is the matrix after
+ * A[d_user[j], d_item[j]] = d_rating[j] for j = 0 .. n-1 IN ORDER: d_rating is rating label + 1 as in igmc_graph_create,
+ * 0 removes the entry; of a pair that occurs more than once the last occurrence wins; removing an absent entry and re-writing
+ * the present rating change nothing.  n_users_new >= n_users and n_items_new >= n_items: the graph may grow, new rows and
+ * columns start empty (n == 0: a copy, possibly grown).  The arrays of *out -- rows by (relation, item), columns by
+ * (relation, user) -- and its nnz, max_rel, max_deg_u, max_deg_v are bit for bit those igmc_graph_create builds from the
+ * changed matrix, whatever the launch geometry.  Errors (non-zero, igmc_last_error, *out not written, nothing kept): a null
+ * argument, a shrinking size, an id outside [0, n_users_new) / [0, n_items_new), n above 2^30, a resulting nnz that does not
+ * fit int32.  SYNCHRONOUS like igmc_graph_create (the new nnz sizes the allocation); what crosses to the host is one block of
+ * sizes and the error word, twice -- never an array of the graph.  A row's cost is (old length + its changes) x log(its
+ * changes) up to 256 changes of one row in one call, (old length + its changes) x its changes beyond.  The library keeps the
+ * call's scratch (sorted lists, flags, pointers: ~32 bytes per change, one allocation per device, at most 64 MB) between calls;
+ * *out is one allocation of exactly its six arrays.  Calls are serialised by a lock.
+ *
+ * igmc_graph_info: n_users, n_items, nnz, max_rel, max_deg_u, max_deg_v.  igmc_graph_download: the six arrays to HOST buffers
+ * (u_ptr int32[n_users + 1], u_idx int32[nnz], u_rel uint8[nnz], v_* alike); any pointer may be NULL. */
+int igmc_graph_apply(const igmc_graph* g, int n_users_new, int n_items_new, const int32_t* d_user, const int32_t* d_item,
+                     const uint8_t* d_rating, int64_t n, void* stream, igmc_graph** out);
+int igmc_graph_info(const igmc_graph* g, int64_t out6[6]);
+int igmc_graph_download(const igmc_graph* g, int32_t* u_ptr, int32_t* u_idx, uint8_t* u_rel, int32_t* v_ptr, int32_t* v_idx,
+                        uint8_t* v_rel);
+
 /* ---- Candidate links and the best of every user's segment (no reference counterpart: the reference has no recommendation
  * path; by hand it would be a host loop over the complement of every user's row, an upload of the pairs and a host argsort of
  * the scores pulled back).
