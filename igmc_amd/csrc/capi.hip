@@ -1362,8 +1362,12 @@ extern "C" int igmc_model_set_ctrl(igmc_model* m, const int64_t* d_ctrl) {
 // whole plane image of the opposite side, rows past that side's extent included -- whatever an earlier launch left in the
 // subgraph slot --, and relies on 0 * stale == 0 (the A-block bytes there are zero).  Steps that ran on non-finite parameters
 // can leave NaN / Inf rows behind which would poison every later gather of the slot, even after the parameters are restored:
-// the regions are cleared (flags included: 0 is never a launch's tag) whenever parameters are loaded (models.load_state_dict)
-// and when an exchange timed out (igmc_model_check below).
+// the regions are cleared (flags included: 0 is never a launch's tag) whenever parameters are replaced wholesale and when an
+// exchange timed out (igmc_model_check below).  The Python entry points that uphold it: models.IGMC.load_state_dict and
+// models.IGMC.reset_parameters (DGCNN_RS too; train_multiple_epochs re-initialises a reused model with the latter), both
+// through IGMC._params_replaced, and models.IGMC.reset_exchange for callers that write the flat parameter buffer themselves.
+// A caller of the C ABI that restores parameters after a diverged step calls this function itself
+// (tests/history_checks.py: run_nonfinite_history holds the kernels to it).
 extern "C" int igmc_model_reset_exchange(igmc_model* m, void* stream) {
   if (!m) IGMC_FAIL("null model");
   hipStream_t st = (hipStream_t)stream;

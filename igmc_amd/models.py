@@ -166,11 +166,23 @@ class IGMC(nn.Module):
         that ran on diverged (non-finite) parameters may have left NaN rows in a subgraph slot, which every later gather of that
         slot would multiply by its zero block entries -- cleared whenever parameters are restored (``igmc_model_reset_exchange``)."""
         out = super().load_state_dict(state_dict, *args, **kwargs)
+        self._params_replaced()
+        return out
+
+    def _params_replaced(self):
+        """Every parameter has just been given a new value (``load_state_dict``, ``reset_parameters``): clear what steps on
+        the previous values left in the workspaces' exchange regions (``igmc_model_reset_exchange``)."""
         if self._flat.device.type == 'cuda':
             st = torch.cuda.current_stream(self._flat.device).cuda_stream
             for ws in self._ws.values():
                 ws.lib.call('igmc_model_reset_exchange', ws.handle, engine._p(st))
-        return out
+
+    def reset_exchange(self):
+        """For callers that write ``flat_parameters()`` (``_flat``) directly: call this after restoring finite parameters
+        when a step may have run on non-finite ones (a diverged run, a poisoned checkpoint).  Such a step can leave NaN rows
+        in a subgraph slot of the engine's exchange regions, and every later prediction on that slot would be a constant;
+        ``load_state_dict`` and ``reset_parameters`` do this themselves."""
+        self._params_replaced()
 
     def flat_parameters(self):
         return self._flat
@@ -185,11 +197,13 @@ class IGMC(nn.Module):
         return self._flat_grad
 
     def reset_parameters(self):
-        """reference ``models.py:31-35`` (called by ``train_multiple_epochs``, ``train_eval.py:53``)."""
+        """reference ``models.py:31-35`` (called by ``train_multiple_epochs``, ``train_eval.py:53``, at the start of every
+        run on a reused model: a run that diverged must not reach into the next, see ``load_state_dict``)."""
         for conv in self.convs:
             conv.reset_parameters()
         self.lin1.reset_parameters()
         self.lin2.reset_parameters()
+        self._params_replaced()
 
     # ------------------------------------------------------------------ engine workspace
     def _workspace(self, data):
@@ -324,6 +338,7 @@ class DGCNN_RS(IGMC):
         self.conv1d_params2.reset_parameters()
         self.lin1.reset_parameters()
         self.lin2.reset_parameters()
+        self._params_replaced()
 
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
