@@ -100,6 +100,13 @@ def build_parser():
                    help='rating changes applied to the training graph ON THE DEVICE before --recommend / --rank-eval: lines '
                         '"user item rating" (ids as recommendations_*.tsv prints them, "#" comments; rating 0 removes the '
                         'entry, ids beyond the graph create new users / items)')
+    p.add_argument('--explain', type=int, default=0, metavar='M',
+                   help='write the M neighbours that move each prediction most (leave-one-out attribution on the device) and '
+                        'stop; explains the links of --explain-links, or with --recommend N every recommended (user, item); '
+                        '0 = off')
+    p.add_argument('--explain-links', default=None, metavar='FILE',
+                   help='--explain: the links to explain, lines "user item" (ids as recommendations_*.tsv prints them, "#" '
+                        'comments)')
     p.add_argument('--rank-min-rating', type=float, default=None, metavar='X',
                    help='--rank-eval: only held-out links rated >= X are relevant (default: all of them)')
     p.add_argument('--ensemble', action='store_true', default=False)
@@ -161,6 +168,45 @@ def write_recommendations(model, train_graphs, args):
                 f.write('%d\t%d\t%d\t%.6f\n' % (u, r + 1, row[r], srow[r]))
     print('Recommended for {} users: {} candidates scored in {} pass(es), {:.0f} candidates/s; wrote {}'.format(
         stats['users'], stats['candidates'], stats['passes'], stats['candidates'] / max(dt, 1e-9), path))
+    # (--explain without --explain-links: the recommended pairs, in the file's order)
+    args.recommended_pairs = (np.repeat(np.asarray(ids, np.int32), counts),
+                              np.concatenate([row[:int(c)] for row, c in zip(items, counts)] or [np.zeros(0, np.int32)]))
+    return path
+
+
+def write_explanations(model, train_graphs, class_values, args):
+    """``--explain M``: ``<res_dir>/explanations_<data_name>.tsv`` -- a header line, then per explained link its (up to) M
+    neighbours by falling |delta| with the columns ``user item score place side node rating delta score_without``: ``score`` the
+    link's prediction, ``side`` ``user`` (someone who rated the item) or ``item`` (something the user rated), ``rating`` the
+    ``class_values`` entry that joins the neighbour to the opposite target or ``-``, ``delta`` = ``score_without`` - ``score``.
+    A link whose targets have no neighbours gets one line with place 0 and ``-`` for side, node and rating."""
+    import time
+    from igmc_amd.explain import explain, read_links
+    if args.explain_links:
+        u, v = read_links(args.explain_links)
+    else:
+        u, v = args.recommended_pairs
+    path = os.path.join(args.res_dir, 'explanations_{}.tsv'.format(args.data_name))
+    stats = {}
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = explain(model, train_graphs, u, v, m=args.explain, batch_size=args.batch_size, stats=stats) if len(u) else None
+    res = {k: t.cpu().numpy() for k, t in res.items()} if res else None      # (synchronises)
+    dt = time.perf_counter() - t0
+    values = np.asarray(class_values).tolist()
+    with open(path, 'w') as f:
+        f.write('user\titem\tscore\tplace\tside\tnode\trating\tdelta\tscore_without\n')
+        for i in range(len(u)):
+            b = float(res['base'][i])
+            if res['counts'][i] == 0:
+                f.write('%d\t%d\t%.6f\t0\t-\t-\t-\t%.6f\t%.6f\n' % (u[i], v[i], b, 0.0, b))
+            for r in range(int(res['counts'][i])):
+                code, d = int(res['ratings'][i, r]), float(res['deltas'][i, r])
+                f.write('%d\t%d\t%.6f\t%d\t%s\t%d\t%s\t%.6f\t%.6f\n' % (
+                    u[i], v[i], b, r + 1, 'item' if res['sides'][i, r] else 'user', res['nodes'][i, r],
+                    '%g' % values[code - 1] if code else '-', d, b + d))
+    print('Explained {} links: {} leave-one-out variants scored in {} pass(es), {:.0f} variants/s; wrote {}'.format(
+        len(u), stats.get('variants', 0), stats.get('passes', 0), stats.get('variants', 0) / max(dt, 1e-9), path))
     return path
 
 
@@ -221,9 +267,17 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     from igmc_amd.new_ratings import flag_error
-    bad = flag_error(args.new_ratings, args.recommend, args.rank_eval, args.use_features)
+    bad = flag_error(args.new_ratings, args.recommend or args.explain, args.rank_eval, args.use_features)
     if bad:
         parser.error(bad)
+    if args.explain < 0 or args.explain > 64:
+        parser.error('--explain takes M in [1, 64]')
+    if args.explain > 0 and not args.explain_links and not args.recommend > 0:
+        parser.error('--explain needs the links to explain: --explain-links FILE, or --recommend N for the recommended pairs')
+    if args.explain_links and not args.explain > 0:
+        parser.error('--explain-links names the links of --explain M: give M')
+    if args.explain > 0 and args.use_features:
+        parser.error('--explain takes no --use-features: leave-one-out variants carry no side features')
     rank, world = parallel.init_from_env()
     torch.manual_seed(args.seed)
     if torch.cuda.is_available():
@@ -353,9 +407,10 @@ def main(argv=None):
     # only rank 0 writes checkpoints (inside `logger`): nobody may look for them before it is done
     parallel.barrier()
 
-    if args.recommend > 0 or args.rank_eval:
+    if args.recommend > 0 or args.rank_eval or args.explain > 0:
         # no reference counterpart: the checkpoint's N best unseen items per user over adj_train, with the training set's
-        # extraction settings, and / or where the held-out links (test split under --testing, else validation split) stand
+        # extraction settings, and / or why it predicts what it predicts for given links (--explain: the neighbours whose
+        # removal moves the score most), and / or where the held-out links (test split under --testing, else validation split) stand
         # among those items (and nothing else of what follows).  Rank 0 does the work; the other ranks wait at the barrier.
         if args.rank_eval:
             rank_eval_ks(args.rank_eval)
@@ -366,6 +421,8 @@ def main(argv=None):
                 write_recommendations(model, over, args)
             if args.rank_eval:
                 write_ranking(model, over, test_graphs, args)
+            if args.explain > 0:
+                write_explanations(model, over, class_values, args)
         parallel.barrier()
         return rmse
 

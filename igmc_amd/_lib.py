@@ -80,6 +80,9 @@ SIGNATURES = {
     'igmc_select_segments': (i32, [vp, vp, i32, i32, vp, vp, vp, vp, i64, i32, vp]),
     'igmc_rank_segments': (i32, [vp, vp, i64, vp, i32, vp, vp, i64, vp, vp, vp, i32, vp]),
     'igmc_rank_metrics': (i32, [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, i32, vp]),
+    'igmc_loo_count': (i32, [vp, i32, vp, vp, vp, vp]),
+    'igmc_loo_fill': (i32, [vp, vp, i32, i64, vp, vp, vp, i64, i64, i64] + [vp] * 10 + [vp, vp]),
+    'igmc_loo_deltas': (i32, [vp, vp, i64, vp, vp, vp, vp, vp]),
     'igmc_comm_unique_id': (i32, [vp]),
     'igmc_comm_create': (i32, [vp, i32, i32, i32, C.POINTER(vp)]),
     'igmc_comm_destroy': (None, [vp]),

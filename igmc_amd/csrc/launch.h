@@ -128,6 +128,30 @@ int64_t igmc_graph_update_padded(int64_t n);
 void igmc_launch_graph_update_plan(const GuSide& s, int side, const int32_t* user, const int32_t* item, const uint8_t* rating,
                                    int64_t n, int n_users, int n_items, GuStats* st, void* stream);
 void igmc_launch_graph_update_write(const GuSide& s, int side, int64_t n, int64_t nnz_old, GuStats* st, void* stream);
+// explain.hip: leave-one-out variants of the links of an extracted arena written into a node-set cache (count, then fill at
+// the offsets of the counts), and the variant scores turned into per-link attribution segments
+struct LooCache {
+  const int64_t* var_off;   // [B + 1] each: the batch's slice of the prefix sums of the three counts
+  const int64_t* uent_off;
+  const int64_t* vent_off;
+  int64_t cap_var, cap_uent, cap_vent;
+  int64_t* uoff;            // [cap_var + 1]  the cache arrays igmc_launch_load_nodes reads
+  int32_t* unodes;          // [cap_uent]
+  uint8_t* udist;
+  int64_t* voff;
+  int32_t* vnodes;          // [cap_vent]
+  uint8_t* vdist;
+  int32_t* var_link;        // [cap_var] each
+  uint8_t* var_side;
+  int32_t* var_node;
+  uint8_t* var_rating;
+};
+void igmc_launch_loo_count(const BatchDev& b, int B, int64_t* nvar, int64_t* nu_ids, int64_t* nv_ids, void* stream);
+int igmc_loo_default_chunks();
+void igmc_launch_loo_fill(const GraphDev& g, const BatchDev& b, int B, int64_t link0, const LooCache& c, int chunks, int32_t* err,
+                          void* stream);
+void igmc_launch_loo_deltas(const float* scores, const int64_t* var_off, int64_t n_links, float* base, float* delta, float* key,
+                            const int64_t* seg_off, void* stream);
 int igmc_model_prepare(const ModelDev& m);
 void igmc_launch_adam(float* p, const float* g, float* m1, float* m2, int64_t n, float step_size,
                       float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd, int64_t* ctrl, int tick,

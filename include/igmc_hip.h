@@ -480,6 +480,55 @@ int igmc_rank_metrics(const int32_t* d_q_rank, const int64_t* d_q_off, const uin
                       int ns, const int32_t* d_ks, int nk, int32_t* d_cnt, double* d_dcg, int32_t* d_err, int grid,
                       void* stream);
 
+/* ---- Leave-one-out neighbour attribution (no reference counterpart: the reference's `visualize` draws an enclosing subgraph
+ * and leaves the reading to the eye; by hand an attribution is the subgraph pulled to the host, one node deleted, the node
+ * sets rebuilt and replayed one variant at a time).
+ *
+ * The link in slot i of an EXTRACTED arena `base` has users U[0..nu) and items V[0..nv) in slot order (target first, the rest
+ * by ascending id).  Its VARIANTS, in this order: 0 = the whole node set (the base); 1 .. nu-1 = the set without U[k];
+ * nu .. nu+nv-2 = the set without V[k - nu + 1].  The two targets are never removed; every remaining node keeps the hop
+ * distance -- and so the label -- it has in the whole set: at hop 2 a node reachable only through the removed one STAYS, with
+ * its old label.  Scoring the variants is the caller's business (igmc_extract_batch_cached + a forward: the induced edges of
+ * the remaining nodes, without the target edge); the attribution of a node is score(variant without it) - score(base).
+ *
+ * igmc_loo_count (no reference counterpart): for the B links of `base`, d_nvar[i] = nu + nv - 1, d_nu_ids[i] = the user
+ * entries the link's variants occupy in a cache, nu + (nu-1)(nu-1) + (nv-1) nu, d_nv_ids[i] = the item entries,
+ * nv + (nu-1) nv + (nv-1)(nv-1) (int64[B] each).  B: at most the links the last extraction call put into the arena (after a
+ * replayed launch: igmc_batch_assume_size).  Reads the sizes of the arena only: works on lean arenas and on arenas without
+ * dense blocks and never makes an arena emit its CSR. */
+int igmc_loo_count(const igmc_batch* base, int B, int64_t* d_nvar, int64_t* d_nu_ids, int64_t* d_nv_ids, void* stream);
+/* igmc_loo_fill (no reference counterpart): writes every variant of the B links of `base` (an arena of graph g) into a cache of
+ * the format igmc_extract_batch_cached reads.  d_var_off / d_uent_off / d_vent_off: int64[B + 1], the batch's slice of the
+ * exclusive prefix sums of the three counts over the pass, so that link i owns the variants [d_var_off[i], d_var_off[i + 1])
+ * and the entries [d_uent_off[i], d_uent_off[i + 1]) of d_unodes / d_udist (items alike).  Variant k of link i at v =
+ * d_var_off[i] + k:
+ *   d_uoff[v], d_voff[v]   int64, the variant's first entry -- and d_uoff / d_voff[d_var_off[i + 1]] = the end of the link's
+ *                          last variant, so d_uoff / d_voff need cap_var + 1 entries
+ *   d_unodes / d_vnodes    int32 ids, target first, then ascending;  d_udist / d_vdist  uint8 hop distances (slot label / 2)
+ *   d_var_link[v]          int32  link0 + i
+ *   d_var_side[v]          uint8  0 = a user was removed, 1 = an item, 255 = the base
+ *   d_var_node[v]          int32  the removed global id, -1 for the base
+ *   d_var_rating[v]        uint8  rating + 1 of the entry of g that joins the removed node to the OPPOSITE target -- (u', v) for a
+ *                          removed user u', (u, v') for a removed item v' --, 0 if they share none (and for the base)
+ * d_err[0] (int32, ZEROED BY THE CALLER, read after the launch): bits 0 / 1 / 2 = a link's variants / user entries / item
+ * entries reach past cap_var / cap_uent / cap_vent; bit 3 = the offsets of a link are not the prefix sums of its counts;
+ * bit 4 = a slot's sizes are not those of an extracted link.  A link that raises a bit has NOTHING written, the other links are complete.
+ * Nothing is written outside the capacities.  The output is a function of the inputs alone (plain stores, no atomics besides
+ * the error word); one launch, capturable; nothing is allocated. */
+int igmc_loo_fill(const igmc_graph* g, const igmc_batch* base, int B, int64_t link0, const int64_t* d_var_off,
+                  const int64_t* d_uent_off, const int64_t* d_vent_off, int64_t cap_var, int64_t cap_uent, int64_t cap_vent,
+                  int64_t* d_uoff, int32_t* d_unodes, uint8_t* d_udist, int64_t* d_voff, int32_t* d_vnodes, uint8_t* d_vdist,
+                  int32_t* d_var_link, uint8_t* d_var_side, int32_t* d_var_node, uint8_t* d_var_rating, int32_t* d_err,
+                  void* stream);
+/* igmc_loo_deltas (no reference counterpart): d_scores float[d_var_off[n_links]] = one score per variant, d_var_off int64
+ * [n_links + 1] over the whole pass.  d_base[i] = the score of link i's variant 0; for its variants k >= 1,
+ * d_delta[d_seg_off[i] + k - 1] = score - base and d_key[...] = |delta| (a NaN score or base gives a NaN key), with
+ * d_seg_off[i] = d_var_off[i] - i (int64[n_links + 1], computed by the caller): the base entries drop out and the segments
+ * [d_seg_off[i], d_seg_off[i + 1]) are what igmc_select_segments takes -- its order (key descending, index ascending, NaNs
+ * last) ranks, among equal |delta|, users before items and lower ids first.  One launch, capturable. */
+int igmc_loo_deltas(const float* d_scores, const int64_t* d_var_off, int64_t n_links, float* d_base, float* d_delta,
+                    float* d_key, const int64_t* d_seg_off, void* stream);
+
 /* Per-kernel timing of the last call (HIP events on the launch stream); names/ms arrays are
  * filled up to `cap` (ms = total over `calls` launches of that kernel since the last fetch);
  * returns the number of distinct kernels recorded, or <0 on error. */
