@@ -184,6 +184,7 @@ int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan
   a.ts_part = m.ts_part; a.g2_px = m.g2_px; a.g2_fx = m.g2_fx; a.g2_px_stride = m.g2_px_stride; a.g2_w = m.g2_w;
   a.gs_bar = m.gs_bar; a.gs_err = m.gs_err; a.a1 = m.a1; a.dz = m.dz; a.feat = m.feat; a.gfeat = m.gfeat; a.err = m.err;
   a.lmask = m.lmask; a.ctrl = m.ctrl;
+  a.off_basis3 = (int)m.off_basis[3]; a.off_att3 = (int)m.off_att[3]; a.off_root3 = (int)m.off_root[3];
   a.off_l1w = (int)m.off_l1w; a.off_l1b = (int)m.off_l1b; a.off_l2w = (int)m.off_l2w; a.off_l2b = (int)m.off_l2b;
   a.P = P;
   a.inj_mask = inj_mask;

@@ -32,6 +32,7 @@ struct G2Args {
   const int64_t* ctrl;
   int off_bias[4];
   int off_l1w, off_l1b, off_l2w, off_l2b;
+  int off_basis3, off_att3, off_root3;      // conv layer 3 in f32: its backward runs in closed form (no staged image)
   // call
   const float* P;
   const uint8_t* inj_mask;
@@ -77,6 +78,12 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
   float* sdz = skeep + 128;               // [128]
   float* sred = sdz + 128;                // [512] head: reduction slots; backward: column sums of dPre_l [2 (parity of l)][4 bundles][32] (d bias_l)
   float* misc = sred + 512;               // [16]
+  // layer 3 only feeds the readout, so dPre_3 lives on the two centre rows and its backward is a closed form (TRAIN):
+  float* D3 = sred + 256;                 // [2 sides][32] dPre_3 of the side's centre row (upper half of sred: free behind the head)
+  float* TC = TILES + (G2_THREADS / 64) * 256;      // [2 sides][G2_NR][32] T_r of the centre row, left by layer 3's forward gather
+                                          // (behind the head's d feat partials; T' tiles are not written before backward layer 2)
+  float* QV = HSS;                        // [2 sides][4 bases + root][32] basis_b . dPre_3, root . dPre_3 (h tiles: dead until backward layer 2)
+  float* ATT3 = S + lay.att;              // [R][4] att of layer 3
   const int R = a.R, L = a.L, RL = R * L;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, kq = lane >> 4;
@@ -93,6 +100,9 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
   // members of its clusters one after the other, so the residency argument above holds per XCD.
   const int cm = (cs > 1) ? (int)((blockIdx.x >> 3) % cs) : 0;
   const int half = 2 * cs;                              // waves of the cluster per side
+  // bundle 0 of a side -- its centre (target) row -- sits in member 0 (users) and in the member that holds bundle `half` (items)
+  const bool own_u = cm == 0, own_v = half >= G2_NB * cm && half < G2_NB * cm + G2_NB;
+  const bool wg_centre = own_u || own_v;                // (workgroup-uniform)
   const uint32_t seq = g2_ld_seq(a.gs_bar);
   const uint32_t tag0 = seq * 8u + 1u;
   const uint64_t step = a.ctrl ? (uint64_t)a.ctrl[IGMC_CTRL_STEP] : a.step;
@@ -199,7 +209,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
     {
       const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
       // (the plane image is NOT cleared: its first reader is layer 1's gather, behind a fetch that copies the whole image
-      //  from the exchange region -- planes_load -- and what dPre_3 needs is cleared behind layer 3's forward; there is no block image)
+      //  from the exchange region -- planes_load --, and so is every later one: dPre_3 never enters it; there is no block image)
       for (int i = tid; i < 2 * G2_NB * 16 * G2_XP / 4; i += G2_THREADS) ((float4*)XOA)[i] = z4;
       for (int i = tid; i < G2_NB * 16 * G2_XP / 4; i += G2_THREADS) ((float4*)HIST)[i] = z4;
     }
@@ -334,10 +344,13 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
         g2_publish_planes(px_of(l, side), kp, 16 * nt + li, row0 + 4 * kq, v);
         g2_flag_raise(px_of(l, side), 2 * bi + hf, xtag(l), lane);
       }
+      // (h_3 is read by the readout alone, on the centre rows, which travel in the readout words: no tile, no a.h[3])
+      if (l < 3) {
 #pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        xo[rr * G2_XP + 16 * nt] = v[rr];
-        if (TRAIN && row0 + 4 * kq + rr < n_own) hrow[rr * 32 + 16 * nt] = v[rr];
+        for (int rr = 0; rr < 4; ++rr) {
+          xo[rr * G2_XP + 16 * nt] = v[rr];
+          if (TRAIN && row0 + 4 * kq + rr < n_own) hrow[rr * 32 + 16 * nt] = v[rr];
+        }
       }
       if (bi == 0 && kq == 0) g2_pub_f32(fx + side * 128 + l * 32 + 16 * nt + li, v[0], tag0 + G2_FXTAG);
     };
@@ -406,49 +419,55 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
       float* XOc = (l & 1) ? XO0 : XO1;             // x of the bundle's own rows (h_{l-1})
       float* XOn = (l & 1) ? XO1 : XO0;             // h_l
       G2_STAMP(6 + 3 * (l - 1));
-      const float bias0 = P[a.off_bias[l] + 16 * hf + li];
-      // the opposite side's h_{l-1} as bf16 planes, and the layer's weight image (the previous one died at the previous
-      // layer's barrier): both global -> LDS, landed by the barrier below
-      fetch(l - 1);
-      if (l > 1) wload(l, 0);
-      __syncthreads();
+      // Layer 3 runs on the centre bundles only: the readout takes h_3 of the two target rows and nothing else reads it.  A
+      // workgroup without a centre bundle skips the layer as a whole (uniform: its barriers go with it; what they ordered --
+      // the pair's halves of h_2, the reuse of PX -- is ordered by the barrier behind the readout poll).
+      const bool lrun = l < 3 || wg_centre;
+      const bool act = active && (l < 3 || bi == 0);
+      float bias0 = 0.f;
+      if (lrun) {
+        bias0 = P[a.off_bias[l] + 16 * hf + li];
+        // the opposite side's h_{l-1} as bf16 planes, and the layer's weight image (the previous one died at the previous
+        // layer's barrier): both global -> LDS, landed by the barrier below
+        fetch(l - 1);
+        if (l > 1) wload(l, 0);
+        __syncthreads();
+      }
       G2_STAMP(7 + 3 * (l - 1));
-      float bias0_ = bias0;                       // landed: no wait for it is left inside the epilogue (a wait there
-      G2_OPAQUE(bias0_);                          // would also drain the epilogue's own stores, one round trip each)
-      f32x4 o[2];
-      if (active) {
-        int lane_ = lane;
-        G2_OPAQUE(lane_);
-        const int li_ = lane_ & 15, kq_ = lane_ >> 4;
-        f32x4 acc[G2_NR];
-        g2_gather_h(pl, kp, nks, frag_f, li_, kq_, hf, acc);
-        if (l == 2) G2_STAMP(40);
-        g2_transform_h(acc, XOc, (const uint32_t*)sW2, li_, kq_, hf, o);
-        if (l == 2) G2_STAMP(41);
-        *PXo = hf ? o[0] : o[1];                    // the partner's tile: this wave's half of its K
-      }
-      __syncthreads();                              // the pair's partials are exchanged (planes / sW2 are dead as well)
-      if (l == 2) G2_STAMP(42);
-      if (active) {
-        const f32x4 po = *PXi;
-        f32x4 of;
+      if (lrun) {
+        float bias0_ = bias0;                       // landed: no wait for it is left inside the epilogue (a wait there
+        G2_OPAQUE(bias0_);                          // would also drain the epilogue's own stores, one round trip each)
+        f32x4 o[2];
+        if (act) {
+          int lane_ = lane;
+          G2_OPAQUE(lane_);
+          const int li_ = lane_ & 15, kq_ = lane_ >> 4;
+          f32x4 acc[G2_NR];
+          g2_gather_h(pl, kp, nks, frag_f, li_, kq_, hf, acc);
+          if (l == 2) G2_STAMP(40);
+          if (TRAIN && l == 3 && li_ == 0) {
+            // T_r of the centre row (features 16 hf + 4 kq ..): the layer-3 weight gradient is its outer product with dPre_3
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr) of[rr] = hf ? po[rr] + o[1][rr] : o[0][rr] + po[rr];      // (K half 0 + K half 1)
-        fwd_out(l, of, bias0_, XOn);
-      }
-      if (TRAIN && l == 3) {
-        G2_STAMP(39);
-        // dPre_3's regions are cleared HERE, behind the wave's last forward stores and under the members' readout words
-        // on their way: the first k-step of the plane image (nodes 0..31 of every term / feature row: all that layer 3's
-        // backward gather reads; the rest still holds h_2 -- finite values the next exchange overwrites) and the bundle's
-        // XO0 (h_2 of its rows).  Both died at the pair barrier above; the barriers of the head order the clears in front of
-        // the centre-row writes of the set-up.
-        for (int i = tid; i < nsides * G2_NT * 32 * 16; i += G2_THREADS) {
-          const int s2 = i / (G2_NT * 32 * 16), r2 = i - s2 * (G2_NT * 32 * 16);
-          PLN[s2 * lay.pside + (r2 >> 4) * (kp >> 1) + (r2 & 15)] = 0u;
+            for (int r = 0; r < G2_NR; ++r)
+              *(float4*)(TC + side * (G2_NR * 32) + r * 32 + 16 * hf + 4 * kq_) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+          }
+          g2_transform_h(acc, XOc, (const uint32_t*)sW2, li_, kq_, hf, o);
+          if (l == 2) G2_STAMP(41);
+          *PXo = hf ? o[0] : o[1];                    // the partner's tile: this wave's half of its K
         }
-        for (int i = lane + 64 * hf; i < 16 * G2_XP; i += 128) XO0[i] = 0.f;      // (the pair shares the bundle's tile)
+        __syncthreads();                              // the pair's partials are exchanged (planes / sW2 are dead as well)
+        if (l == 2) G2_STAMP(42);
+        if (act) {
+          const f32x4 po = *PXi;
+          f32x4 of;
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) of[rr] = hf ? po[rr] + o[1][rr] : o[0][rr] + po[rr];      // (K half 0 + K half 1)
+          fwd_out(l, of, bias0_, XOn);
+        }
       }
+      // (nothing of dPre_3 is staged in LDS tiles or planes any more: backward layer 3 overwrites every row of the active
+      //  bundles' XO1, backward layer 2 every row of their XO0, idle bundles keep the zeros of the set-up, and the plane image
+      //  is next read behind a fetch that copies all of it)
       G2_STAMP(36 + (l - 1));
       // (no barrier here: planes / sW2 were dead at the barrier above; the pair's two halves of h_l in XOn and the reuse of
       //  PX are ordered by the next phase's barrier -- behind the next layer's reload, or the readout poll)
@@ -463,9 +482,25 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
     const int ju_h = 16 * wave + ((lane >> 1) & 15);
     float hd_l1b = P[a.off_l1b + ju_h], hd_l2w = P[a.off_l2w + ju_h], hd_l2b = P[a.off_l2b], hd_y = a.y[g];
     float hd_l2wt = TRAIN ? P[a.off_l2w + (tid & 127)] : 0.f;
+    float hd_att3 = (TRAIN && tid < 4 * R) ? P[a.off_att3 + tid] : 0.f;
+    if (TRAIN) {
+      // layer 3's bases and root in f32, global -> LDS into the weight region (its last image died at the last pair barrier this
+      // workgroup ran; the next one is requested behind the closed-form backward of layer 3): 16 + 4 pieces of 1 KB, landed
+      // by the head's barriers
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const int c = wave + j * (G2_THREADS / 64);
+        if (c < 20) g2_glds16((c < 16) ? (const float4*)(P + a.off_basis3) + c * 64 : (const float4*)(P + a.off_root3) + (c - 16) * 64,
+                              (float4*)sW2 + c * 64, lane);
+      }
+    }
     if (tid < 256) sfeat[tid] = g2_poll_f32(fx + tid, tag0 + G2_FXTAG, a.gs_err);
     __syncthreads();
     G2_OPAQUE(hd_l1b); G2_OPAQUE(hd_l2w); G2_OPAQUE(hd_l2b); G2_OPAQUE(hd_y); G2_OPAQUE(hd_l2wt);      // (landed with the poll)
+    if (TRAIN) {
+      G2_OPAQUE(hd_att3);
+      if (tid < 4 * R) ATT3[tid] = hd_att3;
+    }
     G2_STAMP(15);
     // (the wave's sixteen lin1 rows stay in registers: d feat = dz @ lin1.weight below needs exactly these rows and columns
     //  again -- a second round trip to the weights, behind a data-dependent row selection, was 2 k cycles of the chain)
@@ -565,43 +600,19 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
         }
         *(float4*)(TILES + wave * 256 + 4 * lane) = s4;
       }
-      wload(3, 1);            // the first backward layer's image: lands under the dPre_3 set-up and the first backward gather
       __syncthreads();
       if (tid < 256) {
         const float v = ((TILES[tid] + TILES[256 + tid]) + (TILES[512 + tid] + TILES[768 + tid])) +
                         ((TILES[1024 + tid] + TILES[1280 + tid]) + (TILES[1536 + tid] + TILES[1792 + tid]));
         sgf[tid] = v;
         if (cm == 0) a.gfeat[(size_t)g * a.D + tid] = v;
+        if ((tid & 127) >= 96) {      // dPre_3: non-zero on the two centre rows only
+          const float hv = sfeat[tid];
+          D3[(tid >> 7) * 32 + (tid & 31)] = v * (1.f - hv * hv);
+        }
       }
       __syncthreads();
       G2_STAMP(17);
-      // ---- dPre_3: non-zero on the two centre rows only.  Own rows -> XO0 (h_3 sits in XO1), the opposite side's
-      //      planes are rebuilt locally (node 0 of every feature; everything else zero): no exchange
-      //      (only the first k-step -- nodes 0..31 of every term / feature row -- is read by layer 3's gather; the rest of
-      //      the planes still holds h_2: finite values that the next exchange overwrites -- cleared, with XO0, behind layer 3's
-      //      pair barrier in the forward; only the centre-row writes are left here)
-      if (tid < 32 * nsides) {
-        const int s2 = tid >> 5, f = tid & 31;
-        const int sd = (nsides == 2) ? s2 : 1 - side;
-        const float hv = sfeat[sd * 128 + 96 + f];
-        const float d = sgf[sd * 128 + 96 + f] * (1.f - hv * hv);
-        uint32_t h, mi, lo;
-        g2_split2(d, 0.f, h, mi, lo);
-        uint32_t* p2 = PLN + s2 * lay.pside + (f * kp >> 1);
-        p2[0] = h & 0xFFFFu;
-        p2[32 * kp >> 1] = mi & 0xFFFFu;
-        p2[2 * (32 * kp >> 1)] = lo & 0xFFFFu;
-      }
-      if (hf == 0 && lane < 32) {
-        // (d bias_3: the column sums of dPre_3 over a bundle's rows are its centre row, or zero)
-        const float hv = sfeat[side * 128 + 96 + lane];
-        const float d = (active && bi == 0) ? sgf[side * 128 + 96 + lane] * (1.f - hv * hv) : 0.f;
-        if (active && bi == 0) XO0[lane] = d;
-        sred[(1 * G2_NB + bw) * 32 + lane] = d;
-      }
-      __syncthreads();
-      G2_STAMP(18);
-
       // ============================================================== conv layers 3..1, backward
 #pragma unroll
       for (int l = 3; l >= 1; --l) {
@@ -621,12 +632,38 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
             for (int rr = 0; rr < 4; ++rr)
               if (row0 + 4 * kq + rr < n_own) hreg[rr] = hrow[rr * 32];
           }
+        }
+        if (l == 3) {
+          // ---- layer 3 in closed form.  dPre_3 lives on the two centre rows, so T'_r of an own-side row j is dPre_3[c_opp] where
+          //      the kept edge j -> c_opp has relation r (zero elsewhere) and dX[j] = g_{r(j)} with g_r = dPre_3[c_opp] @ W_r^T =
+          //      sum_b att[r,b] q_b,  q_b = basis_b . dPre_3[c_opp]; the centre row adds dPre_3[c_own] @ root^T.  No gather, no
+          //      transform, no tiles, no image: 2 sides x (4 bases + root) matvecs of 32 x 32 in f32, one output per thread,
+          //      every thread in one fixed order (rotated by its row: bank-conflict free)
+          if (tid < 2 * 5 * 32) {
+            const int sd = tid / 160, mi = tid - sd * 160, i = mi & 31;
+            const float* wr = (const float*)sW2 + mi * 32;      // row i of matrix mi >> 5 (bases 0..3, root)
+            const float* dv = D3 + sd * 32;
+            float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+            for (int o2 = 0; o2 < 32; o2 += 2) {
+              const int oa = (o2 + i) & 31, ob = (o2 + 1 + i) & 31;
+              DL_FMAC(s0, wr[oa], dv[oa]);
+              DL_FMAC(s1, wr[ob], dv[ob]);
+            }
+            QV[tid] = s0 + s1;
+          }
+          if (hf == 0 && lane < 32) {
+            // (d bias_3: the column sums of dPre_3 over a bundle's rows are its centre row, or zero)
+            sred[(1 * G2_NB + bw) * 32 + lane] = (active && bi == 0) ? D3[side * 32 + lane] : 0.f;
+          }
+          G2_STAMP(18);
+        } else if (active) {
           int lane_ = lane;
           G2_OPAQUE(lane_);
           const int li_ = lane_ & 15, kq_ = lane_ >> 4;
           f32x4 acc[G2_NR];
           if (l == 2) G2_STAMP(43);
-          g2_gather_h(pl, kp, (l == 3) ? 1 : nks, frag_b, li_, kq_, hf, acc);
+          g2_gather_h(pl, kp, nks, frag_b, li_, kq_, hf, acc);
           if (l == 2) G2_STAMP(44);
           // T' rows of the bundle -> LDS (B operand of the weight-gradient table): lane = row, 4 consecutive features of
           // this wave's tile
@@ -643,7 +680,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) G2_OPAQUE(hreg[rr]);      // landed here: behind the image request below a wait for
                                                                    // them would wait for the whole image as well
-        } else if (hf == 0) {
+        } else if (l < 3 && hf == 0) {
           // idle bundle: its tile / h rows are K entries of the workgroup's table product
           for (int i = lane; i < 16 * G2_TP; i += 64) T[i] = 0.f;
           for (int i = lane; i < 16 * G2_XP; i += 64) HS[i] = 0.f;
@@ -654,13 +691,45 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
         if (l == 2) G2_STAMP(47);
         if (active) {
           // + readout gradient on the centre row, * tanh'(h_{l-1}): output features 16 hf + li of rows 4 kq + rr
-          const f32x4 po = *PXi;
           const int f = 16 * hf + li;
           float v[4];
+          f32x4 dx;
+          if (l == 3) {
+            // relation of the kept edge  row -> c_opp: byte 0 of k-step 0, held (masked by the row's validity, `active` and
+            // n_opp like every fragment) by lane (row, kq = 0); keep bit of the direction own -> opposite, as in frag_b
+            int relv = -1;
+            if constexpr (FLAGS) {
+              const uint32_t b0 = RB[0][0] & 0xFFu, code = b0 & IGMC_RELM_CODE;
+              if (code >= 1u && code <= (uint32_t)R && ((b0 >> kb) & 1u)) relv = (int)code - 1;
+            } else {
+#pragma unroll
+              for (int r = 0; r < G2_NR; ++r)
+                if (r < R && (AM[r][0][0] & 0xFFu)) relv = r;
+            }
+            const float* qo = QV + (1 - side) * 160 + f;
+            const float q0 = qo[0], q1 = qo[32], q2 = qo[64], q3 = qo[96];
+            const float rootc = QV[side * 160 + 128 + f];
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+              const int row = 4 * kq + rr;
+              const int rl = __shfl(relv, row);
+              float d = 0.f;
+              if (rl >= 0) {
+                const float4 a4 = *(const float4*)(ATT3 + 4 * rl);
+                d = fmaf(a4.w, q3, fmaf(a4.z, q2, fmaf(a4.y, q1, a4.x * q0)));
+              }
+              if (bi == 0 && row == 0) d += rootc;
+              dx[rr] = d;
+            }
+          } else {
+            const f32x4 po = *PXi;
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) dx[rr] = hf ? po[rr] + o[1][rr] : o[0][rr] + po[rr];
+          }
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr) {
             const int row = 4 * kq + rr;
-            float d = hf ? po[rr] + o[1][rr] : o[0][rr] + po[rr];
+            float d = dx[rr];
             if (bi == 0 && row == 0) d += sgf[side * 128 + (l - 1) * 32 + f];
             const float x = hreg[rr];
             v[rr] = (row0 + row < n_own) ? d * (1.f - x * x) : 0.f;
@@ -693,7 +762,29 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
         //  just written are ordered by the barrier at the end of the layer)
         G2_STAMP(21 + 5 * (3 - l));
         if (l > 1) wload(l - 1, 1);                  // next image: lands under the table product (LDS + matrix work only)
-        {
+        if (l == 3) {
+          // layer-3 partial table of the workgroup [r][in][out] (+ root block): T_r[c] (x) dPre_3[c] and h_2[c] (x) dPre_3[c] of
+          // the centres this workgroup owns, users' then items'; exact zeros elsewhere (the tail sums every slot).  Behind the
+          // flag raise: the stores sit under the wait for the other side's dPre_2
+          for (int e4 = tid; e4 < (R + 1) * 256; e4 += G2_THREADS) {
+            const int blk = e4 >> 8, in = (e4 >> 3) & 31, o4 = (e4 & 7) * 4;
+            const float tu = own_u ? ((blk < R) ? TC[blk * 32 + in] : sfeat[64 + in]) : 0.f;
+            const float tv = own_v ? ((blk < R) ? TC[G2_NR * 32 + blk * 32 + in] : sfeat[128 + 64 + in]) : 0.f;
+            const float4 du = *(const float4*)(D3 + o4), dv = *(const float4*)(D3 + 32 + o4);
+            float4 w;
+            w.x = (own_u ? tu * du.x : 0.f) + (own_v ? tv * dv.x : 0.f);
+            w.y = (own_u ? tu * du.y : 0.f) + (own_v ? tv * dv.y : 0.f);
+            w.z = (own_u ? tu * du.z : 0.f) + (own_v ? tv * dv.z : 0.f);
+            w.w = (own_u ? tu * du.w : 0.f) + (own_v ? tv * dv.w : 0.f);
+            float4* pp = (float4*)wpart + e4;
+            if (first_graph) {
+              *pp = w;
+            } else {
+              const float4 c = *pp;
+              *pp = make_float4(c.x + w.x, c.y + w.y, c.z + w.z, c.w + w.w);
+            }
+          }
+        } else {
           // weight-gradient table h_{l-1}^T [T' | dPre_l], split by OUTPUT tile: wave w computes 3 of the 2 x 12 tiles
           // (row half m2 = in-features, column tile nt: 0..9 = T' of relation nt >> 1, 10..11 = dPre -> d root) over
           // K = the 64 rows of the workgroup's four bundles -- no cross-wave reduction

@@ -20,13 +20,17 @@ from igmc_amd.util_functions import MyDynamicDataset  # noqa: E402
 
 NAMES = {1: 'T0 table staged', 2: 'labels + zero fills', 3: 'relm staged + one-hot planes', 4: 'A fragments built', 5: 'layer 0',
          6: 'L1 stage W', 7: 'L1 reload h0', 8: 'L1 compute + sync', 9: 'L2 stage W', 10: 'L2 reload h1', 11: 'L2 compute + sync',
-         12: 'L3 stage W', 13: 'L3 reload h2', 14: 'L3 compute + sync', 15: 'readout polled', 16: 'head forward', 17: 'd feat',
-         18: 'dPre3 centre rows + d bias3', 19: 'B3 layer start', 20: 'B3 wave compute + d bias2', 21: 'B3 sync', 22: 'B3 table product', 23: 'B3 reload dPre2',
+         12: 'L3 stage W', 13: 'L3 reload h2 (centre wg)', 14: 'L3 centre bundle + sync', 15: 'readout polled', 16: 'head forward',
+         17: 'd feat + dPre3 centre rows', 18: 'B3 q = basis,root . dPre3', 19: 'B3 layer start', 20: 'B3 sync + closed-form dX',
+         21: 'B3 (no phase)', 22: 'B3 rank-1 tables', 23: 'B3 reload dPre2',
          24: 'B2 layer start', 25: 'B2 wave compute + d bias1', 26: 'B2 sync', 27: 'B2 table product', 28: 'B2 reload dPre1',
          29: 'B1 layer start', 30: 'B1 wave compute', 31: 'B1 sync', 32: 'B1 table product', 33: 'B1 sync', 34: 'layer-0 table',
          35: 'kernel end'}
 # (stamps 19 / 24 / 29, the top of a backward layer, follow 18 / 23 / 28 directly since d bias_l is formed in the epilogue that
-#  forms dPre_l: no phase is left there, and none is printed)
+#  forms dPre_l: no phase is left there, and none is printed.  Layer 3 runs on the centre bundles only in the forward and in
+#  closed form in the backward: stamp 19 sits in front of 18 there -- the h_2 rows are requested, then the q vectors formed --,
+#  and a library from before that change shows its own phases under these lines: 18 = dPre3 centre rows + d bias3, 20 = B3 wave
+#  compute (gather, tiles, transform) + d bias2, 22 = B3 table product)
 ORDER = [k for k in range(1, 36) if k not in (19, 24, 29)]
 
 
@@ -114,7 +118,7 @@ def fine(c):
     print('B2 wave 0: h loads issued %d | gather %d | tile + HS writes %d | transform %d | pair barrier %d | epilogue %d' % (
         c[43] - c[24], c[44] - c[43], c[45] - c[44], c[46] - c[45], c[47] - c[46], c[25] - c[47]))
     print('head: readout -> lin1 dot done %d | rest of head forward %d' % (c[54] - c[15], c[16] - c[54]))
-    if c[39]:      # (inside 'L3 compute + sync': the zero fills of dPre_3's regions behind layer 3's epilogue, wave 0 of member 0)
+    if c[39]:      # (a library from before layer 3's closed-form backward: the zero fills of dPre_3's regions behind layer 3's epilogue)
         print('dPre3 clears behind the L3 epilogue: %d' % (c[38] - c[39]))
 
 
