@@ -20,8 +20,8 @@ isolated node would still take part in ``DGCNN_RS``'s sort-pool, and removal nee
 
 HOW (``igmc_amd/csrc/explain.hip``).  The pairs are extracted in batches through a ``CandidateLinks.from_pairs`` arena;
 ``igmc_loo_count`` sizes every link's variants from the arena, ``igmc_loo_fill`` writes them -- straight from the arena's
-slots -- into the node-set cache of a :class:`LeaveOneOutLinks`, ``score_links`` scores that dataset-shaped object like any
-static dataset (a captured ``ScoreGraph`` is replayed by every later pass), ``igmc_loo_deltas`` turns the scores into
+slots -- into the node-set cache of a :class:`LeaveOneOutLinks`, ``score_links`` scores that ``links.LinkSource`` like any
+static dataset (a captured ``ScoreGraph``, sized by its ``capacity``, is replayed by every later pass), ``igmc_loo_deltas`` turns the scores into
 contiguous attribution segments and ``igmc_select_segments`` takes the ``m`` largest ``|delta|`` of each.  Per pass ONE host
 read -- the three totals of the counts -- crosses to the host; the error words are read once per call.
 
@@ -35,7 +35,8 @@ import numpy as np
 import torch
 
 from . import engine
-from .recommend import CandidateLinks, _refuse_side_features, score_candidates
+from .links import LinkSource, kept
+from .recommend import CandidateLinks, score_candidates
 
 # Capacities of a LeaveOneOutLinks where the caller names none.  A link with nu users and nv items has nu + nv - 1 variants
 # holding nu + (nu-1)^2 + (nv-1) nu user entries and nv + (nu-1) nv + (nv-1)^2 item entries.  At the headline shape (one hop,
@@ -52,82 +53,50 @@ _ERRORS = ((1, 'a link\'s variants reach past the variant capacity'),
            (16, 'an arena slot without an extracted link'))
 
 
-class LeaveOneOutLinks(object):
-    """The leave-one-out variants of a pass of links as a STATIC dataset (``dynamic = False``, a ``_cache`` of node sets in
-    HBM), shaped like a dataset the way ``CandidateLinks`` is: ``graph``, ``device``, ``h``, ``seed``, ``sample_ratio``,
-    ``max_nodes_per_hop``, ``num_features``, ``arena``, ``extract``, ``__len__``, ``link_y`` of zeros.  ``ScoreGraph._extract``'s
-    cached branch and ``score_links``' eager branch take it unchanged.
+class LeaveOneOutLinks(LinkSource):
+    """The leave-one-out variants of a pass of links as a STATIC source (``dynamic = False``, a ``_cache`` of node sets in
+    HBM): a ``links.LinkSource`` with the settings of ``dataset_or_view`` and a ``link_y`` of zeros, whose batches are rebuilt
+    from the cache (nothing is sampled, the epoch does not matter).
 
     The six cache tensors and the per-variant arrays have FIXED ADDRESSES AND CAPACITIES and are refilled in place by every
     pass, so the hipGraph a scoring pass captured is replayed by the later ones.  ``len()`` is the number of variants the
-    last pass wrote.  ``dataset_or_view``: a dataset or a ``recommend.GraphView``; side features are refused."""
+    last pass wrote, ``capacity`` (= ``capacity_variants``) the number they have room for.  ``dataset_or_view``: a dataset or a
+    ``recommend.GraphView``; side features are refused."""
     dynamic = False
 
     def __init__(self, dataset_or_view, capacity_variants=DEFAULT_VARIANTS, capacity_entries=DEFAULT_ENTRIES):
-        _refuse_side_features(dataset_or_view)
+        self._configure_from(dataset_or_view)
         cv, ce = int(capacity_variants), int(capacity_entries)
         if not 1 <= cv <= 2 ** 31 - 1 or ce < 1:
             raise ValueError('capacity_variants must be in [1, 2^31) and capacity_entries at least 1')
-        ds = dataset_or_view
-        self.source = ds
-        self.graph = ds.graph
-        self.lib = ds.graph.lib
-        self.device = ds.device
-        self.h, self.sample_ratio, self.seed = ds.h, ds.sample_ratio, ds.seed
-        self.max_nodes_per_hop = ds.max_nodes_per_hop
-        self.capacity = self.capacity_variants = cv
-        self.capacity_entries = ce
-        dev = ds.link_y.device
+        self.capacity_variants, self.capacity_entries = cv, ce
+        dev = dataset_or_view.link_y.device
         z = lambda n, dt: torch.zeros(n, dtype=dt, device=dev)
         # A replayed launch prefetches past the end of a short pass (as CandidateLinks' zero-initialised link buffers say):
         # positions behind the last variant must describe valid node sets.  Every pass points the unused tail of uoff / voff
         # at one-entry sets BEHIND its own entries (_close_tail), so the node arrays carry capacity_variants + 1 entries more
         # than the capacity the kernels may fill; whatever those entries hold -- zeros, or ids an earlier pass wrote -- is a
         # valid id with a valid distance.
-        self._t = dict(uoff=z(cv + 1, torch.int64), voff=z(cv + 1, torch.int64),
-                       unodes=z(ce + cv + 1, torch.int32), vnodes=z(ce + cv + 1, torch.int32),
-                       udist=z(ce + cv + 1, torch.uint8), vdist=z(ce + cv + 1, torch.uint8))
-        self._cache = {k: t.data_ptr() for k, t in self._t.items()}
+        self._cache_t = dict(uoff=z(cv + 1, torch.int64), voff=z(cv + 1, torch.int64),
+                             unodes=z(ce + cv + 1, torch.int32), vnodes=z(ce + cv + 1, torch.int32),
+                             udist=z(ce + cv + 1, torch.uint8), vdist=z(ce + cv + 1, torch.uint8))
+        self._cache = {k: t.data_ptr() for k, t in self._cache_t.items()}
         self.link_y = z(cv, torch.float32)
         self.var_link, self.var_node = z(cv, torch.int32), z(cv, torch.int32)
         self.var_side, self.var_rating = z(cv, torch.uint8), z(cv, torch.uint8)
         self._ramp = torch.arange(cv + 1, dtype=torch.int64, device=dev)
         self.n = 0
         self._close_tail(0, 0, 0)
-        self._arenas = {}
-        self._side, self.n_side_features = None, 0
-        self._sizing = False
 
     def _close_tail(self, n_variants, n_uent, n_vent):
         """Positions n_variants .. capacity: sets of one user and one item (see the constructor)."""
         self.n = int(n_variants)
         k = self.capacity - self.n
-        self._t['uoff'][self.n:] = self._ramp[:k + 1] + int(n_uent)
-        self._t['voff'][self.n:] = self._ramp[:k + 1] + int(n_vent)
+        self._cache_t['uoff'][self.n:] = self._ramp[:k + 1] + int(n_uent)
+        self._cache_t['voff'][self.n:] = self._ramp[:k + 1] + int(n_vent)
 
-    # ---- dataset surface
     def __len__(self):
-        return self.capacity if self._sizing else self.n
-
-    @property
-    def num_features(self):
-        return 2 * self.h + 2
-
-    def arena(self, max_graphs, slot=0):
-        key = (int(max_graphs), slot)
-        if key not in self._arenas:
-            self._arenas[key] = engine.Batch(self.graph, int(max_graphs), self.h, self.max_nodes_per_hop)
-        return self._arenas[key]
-
-    def extract(self, positions, first, B, epoch=0, slot=0, max_graphs=None, stream=None):
-        """Variants ``positions[first:first+B]`` (device int32 tensor, or None = identity) rebuilt from the cache into an
-        arena (``MyDataset.extract``'s cached branch; nothing is sampled, ``epoch`` does not matter)."""
-        from .util_functions import DeviceBatch
-        arena = self.arena(max_graphs or B, slot)
-        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        arena.extract_cached(self._cache, self.link_y.data_ptr(), None if positions is None else positions.data_ptr(),
-                             first, B, st)
-        return DeviceBatch(self, arena, B, positions, first, None)
+        return self.n
 
 
 def _pass_plan(cands, loo, n, batch_size, links_per_pass):
@@ -148,25 +117,22 @@ def _variant_passes(model, dataset, u, v, batch_size, links_per_pass, capacity_v
     if model.flat_parameters().device.type != train_eval.device.type:
         model.to(train_eval.device)
     B = int(batch_size)
-    cands = getattr(dataset, '_explain_pairs', None)
-    if cands is None or cands.source is not dataset or cands.graph is not dataset.graph or cands.capacity < len(u):
-        cands = dataset._explain_pairs = CandidateLinks(dataset, max(1, len(u)))
+    cands = kept(dataset, '_explain_pairs', lambda c: c.capacity >= len(u), lambda: CandidateLinks(dataset, max(1, len(u))))
     cands.set_pairs(u, v)                                     # (ValueError for a pair outside the graph)
     n = len(cands)
     if n < 1:
         raise ValueError('no links to explain')
     dev = cands.link_y.device
-    loo = getattr(dataset, '_explain_links', None)
     cv = DEFAULT_VARIANTS if capacity_variants is None else int(capacity_variants)
     ce = DEFAULT_ENTRIES if capacity_entries is None else int(capacity_entries)
-    if loo is None or loo.source is not dataset or loo.graph is not dataset.graph or \
-            (capacity_variants is not None and loo.capacity_variants != cv) or \
-            (capacity_entries is not None and loo.capacity_entries != ce):
-        loo = dataset._explain_links = LeaveOneOutLinks(dataset, cv, ce)
+    loo = kept(dataset, '_explain_links',          # (a capacity the caller does not name: whatever the kept one has)
+               lambda o: (capacity_variants is None or o.capacity_variants == cv) and
+                         (capacity_entries is None or o.capacity_entries == ce),
+               lambda: LeaveOneOutLinks(dataset, cv, ce))
     lpp = _pass_plan(cands, loo, n, B, links_per_pass)
     lib, P = loo.lib, engine._p
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    t = loo._t
+    t = loo._cache_t
     n_var, n_pass = 0, 0
     for l0 in range(0, n, lpp):
         L = min(lpp, n - l0)

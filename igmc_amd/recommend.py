@@ -9,9 +9,10 @@ recommendation is a scoring pass (:func:`igmc_amd.train_eval.score_links`) with 
 * ``igmc_select_segments`` takes the ``n`` best of every user's contiguous score segment in the order (score descending, item
   id ascending, NaNs last).
 
-:class:`CandidateLinks` is the dataset-shaped object in between: it shares the rating graph and the extraction settings of an
+:class:`CandidateLinks` is the ``links.LinkSource`` in between: it shares the rating graph and the extraction settings of an
 existing dataset, and its link buffers are device tensors of FIXED ADDRESS AND CAPACITY that every pass refills in place, so
-the hipGraph a scoring pass captured (``stepgraph.ScoreGraph``) is replayed by every later pass.
+the hipGraph a scoring pass captured (``stepgraph.ScoreGraph``, its buffers sized by the list's ``capacity`` whatever its
+length of the moment) is replayed by every later pass.
 
 SAMPLER POSITIONS.  The extraction's sampler is keyed by (seed, epoch, link position), and a candidate's position is its index
 in ITS PASS's list.  Where a per-hop cap binds (a neighbourhood larger than ``max_nodes_per_hop`` is sampled), a candidate's
@@ -22,13 +23,11 @@ the extraction draws nothing and the scores do not depend on how the users are d
 ``link_y`` of a candidate list is zeros: the squared-error sums a scoring pass accumulates over candidates are MEANINGLESS and
 are dropped here.
 """
-import os
-
 import numpy as np
 import torch
 
 from . import engine
-from .stepgraph import ScoreGraph, _group_size_for
+from .links import LinkSource, kept
 from .train_eval import score_links
 
 DEFAULT_CAPACITY = 1 << 22      # candidates of one pass where the caller names no ``users_per_pass``: 4 Mi links are 48 MB of
@@ -49,14 +48,7 @@ def _dev_int32(x, dev, what):
     return t.to(device=dev, dtype=torch.int32).contiguous()
 
 
-def _refuse_side_features(dataset):
-    if getattr(dataset, '_side', None) is not None or getattr(dataset, 'u_features', None) is not None or \
-            getattr(dataset, 'v_features', None) is not None:
-        raise NotImplementedError('candidate links carry no side features: recommend over a dataset built without '
-                                  '--use-features (u_features / v_features)')
-
-
-class GraphView(object):
+class GraphView(LinkSource):
     """The extraction settings of ``dataset`` over ANOTHER rating graph -- normally ``dataset.graph.updated(...)``, the
     graph after new ratings (``engine.Graph.updated``: built on the device) --, shaped like a dataset as far as
     :class:`CandidateLinks` reads one: ``graph``, ``device``, ``h``, ``sample_ratio``, ``seed``, ``max_nodes_per_hop``, a
@@ -65,21 +57,16 @@ class GraphView(object):
     items the graph gained are scored from their enclosing subgraphs like any other.  A dataset with side features is
     refused: new users have no feature rows."""
 
+    u_features = v_features = None
+
     def __init__(self, dataset, graph):
-        _refuse_side_features(dataset)
-        self.source = dataset
-        self.graph = graph
-        self.device = dataset.device
-        self.h, self.sample_ratio, self.seed = dataset.h, dataset.sample_ratio, dataset.seed
-        self.max_nodes_per_hop = dataset.max_nodes_per_hop
+        self._configure_from(dataset, graph)
         self.link_y = torch.zeros(0, dtype=torch.float32, device=dataset.link_y.device)
-        self._side, self.u_features, self.v_features = None, None, None
 
 
-class CandidateLinks(object):
-    """Links without labels over the rating graph of an existing dataset, shaped like a dataset (``link_u``, ``link_v``,
-    ``link_y``, ``extract``, ``arena``, ``h``, ``seed``, ``max_nodes_per_hop``, ``sample_ratio``, ``num_features``,
-    ``__len__``): ``score_links`` and ``ScoreGraph`` take it as it is.
+class CandidateLinks(LinkSource):
+    """Links without labels over the rating graph of an existing dataset (a ``links.LinkSource`` with the dataset's
+    settings): ``score_links`` and ``ScoreGraph`` take it as it is.
 
     The link buffers hold ``capacity`` entries at fixed addresses; ``len()`` is the number of links the last
     :meth:`refill` / :meth:`set_pairs` wrote.  After :meth:`refill`, ``users`` (int32 ``[nq]``) and ``offsets`` (int64
@@ -87,26 +74,16 @@ class CandidateLinks(object):
     dynamic = True          # subgraphs are extracted on the fly, under the sampling key of the pass
 
     def __init__(self, dataset, capacity):
-        _refuse_side_features(dataset)
+        self._configure_from(dataset)
         capacity = int(capacity)
         if not 1 <= capacity <= _INT32_MAX:
             raise ValueError('capacity must be in [1, 2^31): link positions are int32')
-        self.source = dataset
-        self.graph = dataset.graph
-        self.lib = dataset.graph.lib
-        self.device = dataset.device
-        self.h, self.sample_ratio, self.seed = dataset.h, dataset.sample_ratio, dataset.seed
-        self.max_nodes_per_hop = dataset.max_nodes_per_hop
-        self.capacity = capacity
         dev = dataset.link_y.device
         self.link_u = torch.zeros(capacity, dtype=torch.int32, device=dev)      # (zeros: user 0 / item 0, valid ids -- a replayed
         self.link_v = torch.zeros(capacity, dtype=torch.int32, device=dev)      #  launch prefetches past the end of a short pass)
         self.link_y = torch.zeros(capacity, dtype=torch.float32, device=dev)
         self.n = 0
         self.users, self.offsets = None, None
-        self._arenas = {}
-        self._side, self.n_side_features = None, 0
-        self._sizing = False
 
     # ---- constructors
     @classmethod
@@ -174,28 +151,8 @@ class CandidateLinks(object):
         self.n, self.users, self.offsets = u.numel(), None, None
         return self
 
-    # ---- dataset surface
     def __len__(self):
-        return self.capacity if self._sizing else self.n
-
-    @property
-    def num_features(self):
-        return 2 * self.h + 2
-
-    def arena(self, max_graphs, slot=0):
-        key = (int(max_graphs), slot)
-        if key not in self._arenas:
-            self._arenas[key] = engine.Batch(self.graph, int(max_graphs), self.h, self.max_nodes_per_hop)
-        return self._arenas[key]
-
-    def extract(self, positions, first, B, epoch=0, slot=0, max_graphs=None, stream=None):
-        """Extract links ``positions[first:first+B]`` (device int32 tensor, or None = identity) into an arena."""
-        from .util_functions import DeviceBatch
-        arena = self.arena(max_graphs or B, slot)
-        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        arena.extract(self.link_u.data_ptr(), self.link_v.data_ptr(), self.link_y.data_ptr(),
-                      None if positions is None else positions.data_ptr(), first, B, self.sample_ratio, self.seed, epoch, st)
-        return DeviceBatch(self, arena, B, positions, first, None)
+        return self.n
 
 
 def _item_mask(graph, item_mask, dev):
@@ -218,36 +175,12 @@ def _count(graph, users, mask, exclude_seen):
     return counts, err
 
 
-def _ensure_scoregraph(model, cands, B):
-    """``score_links`` builds a dataset's ``ScoreGraph`` on first use and sizes its position / score buffers by the length the
-    dataset has THEN; a candidate list has another length every pass.  So the object is built here, while the list reports
-    its capacity, and ``score_links`` finds it in place: the passes that follow replay what the first one captured."""
-    if hasattr(model, 'forward_into') or cands.capacity // B < 8 or os.environ.get('IGMC_NO_EVAL_GRAPH', '0') == '1':
-        return None
-    flat = model.flat_parameters()
-    sg = getattr(cands, '_scoregraph', None)
-    if sg is not None and sg.model is model and sg.B == B and sg.params_ptr == flat.data_ptr():
-        return sg
-    if sg is not None:
-        sg.detach()
-    cands._sizing = True
-    try:
-        # (buffers by the capacity; the group size by the pass at hand -- the steps outside whole graph launches run eagerly at
-        #  about twice the cost, and the passes of one call are of one size but the last)
-        sg = ScoreGraph(model, cands, B, group=_group_size_for(max(cands.n, 8 * B) // B))
-    finally:
-        cands._sizing = False
-    cands._scoregraph = sg
-    return sg
-
-
 def score_candidates(model, cands, batch_size=50):
     """One prediction per candidate of ``cands``: a float32 device tensor of ``len(cands)`` entries in the list's order,
     computed by ``score_links`` under the sampling key ``SCORE_EPOCH`` (position = index in the list)."""
     B = int(batch_size)
     if len(cands) < 1:
         return torch.zeros(0, dtype=torch.float32, device=cands.link_y.device)
-    _ensure_scoregraph(model, cands, B)
     R, _, _ = score_links(model, cands, B)          # (labels are zeros: the squared-error sums mean nothing)
     return R
 
@@ -301,9 +234,7 @@ def candidate_passes(model, dataset, users=None, batch_size=50, exclude_seen=Tru
         raise ValueError('no users')
     mask = _item_mask(g, item_mask, dev)
     upp, capacity = pass_plan(g, nq, mask, users_per_pass)
-    cands = getattr(dataset, '_recommend_links', None)
-    if cands is None or cands.capacity < capacity or cands.source is not dataset:
-        cands = dataset._recommend_links = CandidateLinks(dataset, capacity)
+    cands = kept(dataset, '_recommend_links', lambda c: c.capacity >= capacity, lambda: CandidateLinks(dataset, capacity))
     for q0 in range(0, nq, upp):
         cands.refill(users[q0:q0 + upp], exclude_seen, mask)
         yield q0, cands, score_candidates(model, cands, batch_size)

@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib, parallel
+from .links import DeviceBatch
 
 MAX_GROUP = 50               # steps of a group (arenas of an arena set); 32 until round 6: a group's fixed costs -- fork / join, its first
                              # step, the first launches of its extraction chain -- are ~60 us, 64.4 -> 63.2 us/step from 25 to 50
@@ -331,7 +332,7 @@ class StepGraph(GroupPipeline):
         # permutation buffer, padded so that the (discarded) prefetch of the group after the last one stays in range: a
         # launch that starts at step k <= n/B - 2 M reads positions below (k + 3 M) B <= n + M B
         self.pad = 4 * MAX_GROUP * self.B          # (twice that: a launch started anywhere inside the epoch stays in range)
-        self.perm = torch.zeros(max(len(dataset), 1) + self.pad, dtype=torch.int32, device=self.dev)
+        self.perm = torch.zeros(max(dataset.capacity, 1) + self.pad, dtype=torch.int32, device=self.dev)
         self.sets = [[], []]                   # arenas of the even / odd groups (created on first use)
         self.ws = None
         self.sp = None                         # sort-pool readout family (DGCNN_RS): its own step kernels
@@ -353,7 +354,6 @@ class StepGraph(GroupPipeline):
     # ------------------------------------------------------------------ arenas
     def _arena(self, q, i):
         """Arena i of the set of group parity q."""
-        from .util_functions import DeviceBatch
         while len(self.sets[q]) <= i:
             a = self.ds.arena(self.B, slot='%s%d.%d' % (self.SLOT, q, len(self.sets[q])))
             # models the subgraph kernel does not take although the dense blocks exist (sort-pool readout, side features):
@@ -404,12 +404,7 @@ class StepGraph(GroupPipeline):
         """Extraction (+ edge dropout) of the batch selected by ``sel`` = q | (i << 1) (batch i of the group of parity q,
         resolved on the device from the control block) into ``arena`` on the current stream."""
         m, st = self.model, torch.cuda.current_stream().cuda_stream
-        cache = getattr(self.ds, '_cache', None)
-        if cache is not None:       # static dataset (reference MyDataset): node sets from the HBM-resident cache
-            arena.extract_cached(cache, self.ds.link_y.data_ptr(), self.perm.data_ptr(), sel, B, st)
-        else:
-            arena.extract(self.ds.link_u.data_ptr(), self.ds.link_v.data_ptr(), self.ds.link_y.data_ptr(),
-                          self.perm.data_ptr(), sel, B, self.ds.sample_ratio, self.ds.seed, 0, st)
+        self.ds.extract_into(arena, self.perm.data_ptr(), sel, B, 0, st)      # (the epoch comes from the control block)
         if self.TRAINING and m.adj_dropout > 0:
             arena.edge_dropout(m.adj_dropout, m.force_undirected, m.seed, sel, st)
 
@@ -425,8 +420,8 @@ class StepGraph(GroupPipeline):
             # average): a batch's extraction is so short that one launch sequence per batch, beside every step, disturbs the
             # steps less than a launch of two beside every other step -- douban 63.5 -> 62.6, flixster 88.3 -> 87.0 us/step;
             # ml_100k (165 candidates) 103.0 -> 103.5, the MovieLens-1M shape (435) 64.3 -> 66.4 (round 6, same box)
-            g = getattr(self.ds, 'graph', None)
-            if self.TRAINING and g is not None and g.nnz * (1.0 / max(1, g.n_users) + 1.0 / max(1, g.n_items)) < SPARSE_CANDIDATES:
+            g = self.ds.graph
+            if self.TRAINING and g.nnz * (1.0 / max(1, g.n_users) + 1.0 / max(1, g.n_items)) < SPARSE_CANDIDATES:
                 c = 1
         return max(0, min(c, self.M))
 
@@ -434,8 +429,7 @@ class StepGraph(GroupPipeline):
         """The arena set of group parity ``q`` as engine.BatchSets of ``_chunk()`` arenas each (created outside any capture),
         or None where group extraction does not apply."""
         c = self._chunk()
-        if c < 2 or getattr(self.ds, '_cache', None) is not None or getattr(self.ds, '_side', None) is not None or \
-                not self._attached:
+        if c < 2 or not self.ds.group_extractable or not self._attached:
             return None
         n = max(count, self.M)
         arenas = [self._arena(q, i) for i in range(n)]
@@ -451,21 +445,10 @@ class StepGraph(GroupPipeline):
     def _extract_group(self, q, count):
         """igmc_extract_group: chunks of the group in one launch per stage (dynamic datasets, lean arenas with dense blocks,
         no side features); False = not applicable here."""
-        m = self.model
-        sets = self._batch_sets(q, count)
-        if sets is None:
+        if self._batch_sets(q, count) is None:
             return False
-        st = torch.cuda.current_stream().cuda_stream
-        i0 = 0
-        for bs in sets:
-            n = min(len(bs.arenas), count - i0)
-            if n <= 0:
-                break
-            bs.extract(n, self.ds.link_u.data_ptr(), self.ds.link_v.data_ptr(), self.ds.link_y.data_ptr(),
-                       self.perm.data_ptr(), q | (i0 << 1), self.B, self.ds.sample_ratio, self.ds.seed,
-                       drop_p=m.adj_dropout if (self.TRAINING and m.adj_dropout > 0) else 0.0, force_undirected=m.force_undirected,
-                       drop_seed=m.seed, stream=st)
-            i0 += n
+        for launch in self._extract_plan(q, count):
+            launch()
         return True
 
     def _extract_plan(self, q, count):
@@ -890,7 +873,7 @@ class ScoreGraph(EvalGraph):
 
     def __init__(self, model, dataset, batch_size, use_graph=None, overlap=None, group=None):
         EvalGraph.__init__(self, model, dataset, batch_size, use_graph=use_graph, overlap=overlap, group=group)
-        n = max(len(dataset), 1)
+        n = max(dataset.capacity, 1)
         self.scores = torch.zeros(n, dtype=torch.float32, device=self.dev)
         self.labels = torch.zeros(n, dtype=torch.float32, device=self.dev)
         self.err = torch.zeros(1, dtype=torch.int32, device=self.dev)

@@ -349,6 +349,8 @@ def score_links(model, graphs, batch_size=50):
         raise ValueError('score_links: the dataset has no links')
     perm = torch.arange(n)
     if not hasattr(model, 'forward_into') and n // B >= 8 and os.environ.get('IGMC_NO_EVAL_GRAPH', '0') != '1':
+        # THE keeper of a source's ScoreGraph: built on the first pass long enough to replay, sized by the source's capacity (a
+        # list refilled in place has another length every pass, and every later pass replays what this one captured).
         sg = getattr(graphs, '_scoregraph', None)
         # (a captured launch holds the ADDRESS of the flat parameter buffer: model.to() re-creates that buffer, and the
         #  graphs captured before it would read freed memory)

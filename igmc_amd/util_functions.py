@@ -25,6 +25,7 @@ import scipy.sparse as ssp
 import torch
 
 from . import engine
+from .links import DeviceBatch, LinkSource          # noqa: F401  (DeviceBatch: importable from here as before)
 
 
 class Data(object):
@@ -161,90 +162,32 @@ def construct_pyg_graph(u, v, r, node_labels, max_node_label, y, node_features):
     return data
 
 
-class DeviceBatch(object):
-    """One extracted + collated batch living in an engine arena (valid until the arena is reused).
-
-    Carries what ``IGMC.forward`` / the train loop need (``num_graphs``, ``y``) and materialises the
-    PyG-style tensors (``x, edge_index, edge_type, batch``) lazily on request (host round trip; only for
-    inspection / compatibility -- the model consumes the arena directly)."""
-
-    def __init__(self, dataset, arena, num_graphs, positions, first, side=None):
-        self.dataset = dataset
-        self.arena = arena
-        self.num_graphs = int(num_graphs)
-        self._positions, self._first = positions, int(first)
-        self.side = side            # [B, n_side] device tensor or None
-        self._pyg = None
-        self._y = None
-
-    @property
-    def link_pos(self):
-        """Dataset positions of the batch's links (device int64)."""
-        if self._positions is None:
-            return torch.arange(self._first, self._first + self.num_graphs, device=self.dataset.link_y.device)
-        return self._positions[self._first:self._first + self.num_graphs].long()
-
-    @property
-    def y(self):
-        """Rating values of the batch (lazy: the kernels read them straight from the dataset's link array)."""
-        if self._y is None:
-            self._y = self.dataset.link_y.index_select(0, self.link_pos)
-        return self._y
-
-    def to(self, device):
-        return self
-
-    def _materialise(self):
-        if self._pyg is None:
-            d = self.arena.download(torch.cuda.current_stream().cuda_stream)
-            N = d['N']
-            dst = np.repeat(np.arange(N, dtype=np.int64), np.diff(d['row_ptr']).astype(np.int64))
-            x = np.zeros((N, self.arena.num_labels), np.float32)
-            x[np.arange(N), d['node_label']] = 1.0
-            self._pyg = dict(x=torch.from_numpy(x), edge_index=torch.from_numpy(np.stack([d['col'].astype(np.int64), dst], 0)),
-                             edge_type=torch.from_numpy(d['erel'].astype(np.int64)),
-                             batch=torch.from_numpy(d['node_graph'].astype(np.int64)), raw=d)
-        return self._pyg
-
-    x = property(lambda self: self._materialise()['x'])
-    edge_index = property(lambda self: self._materialise()['edge_index'])
-    edge_type = property(lambda self: self._materialise()['edge_type'])
-    batch = property(lambda self: self._materialise()['batch'])
-
-
-class _EngineDataset(object):
-    """Shared machinery of MyDataset / MyDynamicDataset."""
-    dynamic = True
+class _EngineDataset(LinkSource):
+    """Shared machinery of MyDataset / MyDynamicDataset: the links of a split, their labels and side-feature rows."""
 
     def _setup(self, root, A, links, labels, h, sample_ratio, max_nodes_per_hop, u_features, v_features,
                class_values, max_num, device=None, seed=0):
         self.root = root
-        self.device = torch.cuda.current_device() if device is None else int(device)
+        device = torch.cuda.current_device() if device is None else int(device)
         self.A = ssp.csr_matrix(A)
         self.Arow = SparseRowIndexer(self.A)
         self.Acol = None            # CSC orientation is built on the device (reference builds it with A.tocsc())
         self.links = (np.asarray(links[0]), np.asarray(links[1]))
         self.labels = np.asarray(labels)
-        self.h = int(h)
-        self.sample_ratio = float(sample_ratio)
-        self.max_nodes_per_hop = None if max_nodes_per_hop is None else int(max_nodes_per_hop)
         self.u_features, self.v_features = u_features, v_features
         self.class_values = np.asarray(class_values, dtype=np.float64)
         self.max_num = max_num
-        self.seed = int(seed)
         if max_num is not None:                       # reference :84-90 / :127-133
             np.random.seed(123)
             num_links = len(self.links[0])
             perm = np.random.permutation(num_links)[:max_num]
             self.links = (self.links[0][perm], self.links[1][perm])
             self.labels = self.labels[perm]
-        dev = 'cuda:%d' % self.device
-        self.graph = _graph_for(self.A, self.device)
+        dev = 'cuda:%d' % device
+        self._configure(_graph_for(self.A, device), device, h, sample_ratio, seed, max_nodes_per_hop)
         self.link_u = torch.from_numpy(np.ascontiguousarray(self.links[0], dtype=np.int32)).to(dev)
         self.link_v = torch.from_numpy(np.ascontiguousarray(self.links[1], dtype=np.int32)).to(dev)
         self.link_y = torch.from_numpy(self.class_values[self.labels].astype(np.float32)).to(dev)   # reference :247
-        self._arenas = {}
-        self._side = None
         if u_features is not None and v_features is not None:
             # only the two target nodes' features are used (reference :272-275, models.py:208-209)
             uf = ssp.csr_matrix(u_features)[self.links[0]]
@@ -252,45 +195,8 @@ class _EngineDataset(object):
             side = np.asarray(ssp.hstack([uf, vf]).todense(), dtype=np.float32)
             self._side = torch.from_numpy(np.ascontiguousarray(side)).to(dev)
             self.n_side_features = side.shape[1]
-        else:
-            self.n_side_features = 0
 
     # ---- reference surface
-    def __len__(self):
-        return len(self.links[0])
-
-    @property
-    def num_features(self):
-        return 2 * self.h + 2          # one-hot of the node label (reference :246, :285)
-
-    def arena(self, max_graphs, slot=0):
-        key = (int(max_graphs), slot)
-        if key not in self._arenas:
-            a = engine.Batch(self.graph, int(max_graphs), self.h, self.max_nodes_per_hop)
-            if self._side is not None:
-                # the target nodes' feature rows are gathered by the extraction launch itself (device-side, also
-                # under hipGraph replay of the training step)
-                a.bind_side_source(self._side.data_ptr(), self.n_side_features)
-            self._arenas[key] = a
-        return self._arenas[key]
-
-    def extract(self, positions, first, B, epoch=0, slot=0, max_graphs=None, stream=None):
-        """Extract links ``positions[first:first+B]`` (device int32 tensor, or None = identity) into an arena."""
-        arena = self.arena(max_graphs or B, slot)
-        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        ep = epoch if self.dynamic else 0
-        arena.extract(self.link_u.data_ptr(), self.link_v.data_ptr(), self.link_y.data_ptr(),
-                      None if positions is None else positions.data_ptr(), first, B, self.sample_ratio,
-                      self.seed, ep, st)
-        side = None
-        if self._side is not None:        # view of the rows the extraction launch gathered (for inspection / get())
-            if positions is None:
-                idx = torch.arange(first, first + B, device=self.link_y.device)
-            else:
-                idx = positions[first:first + B].long()
-            side = self._side.index_select(0, idx)
-        return DeviceBatch(self, arena, B, positions, first, side)
-
     def get(self, idx):
         """One subgraph as a PyG-style ``Data`` (reference ``MyDynamicDataset.get``, ``:138-145``)."""
         db = self.extract(None, int(idx), 1, epoch=getattr(self, '_epoch', 0), slot=-1)
@@ -332,7 +238,6 @@ class MyDataset(_EngineDataset):
         self.parallel = parallel
         self._setup(root, A, links, labels, h, sample_ratio, max_nodes_per_hop, u_features, v_features,
                     class_values, max_num, device, seed)
-        self._cache = None
         if cache is None:
             cache = root is not None and os.environ.get('IGMC_STATIC_CACHE', '1') != '0'
         if cache and root is not None:
@@ -426,20 +331,6 @@ class MyDataset(_EngineDataset):
         self._cache_t = {k: torch.from_numpy(np.ascontiguousarray(z[k])).to(dev) for k in
                          ('uoff', 'voff', 'unodes', 'vnodes', 'udist', 'vdist')}
         self._cache = {k: t.data_ptr() for k, t in self._cache_t.items()}
-
-    def extract(self, positions, first, B, epoch=0, slot=0, max_graphs=None, stream=None):
-        if self._cache is None:
-            return super().extract(positions, first, B, epoch=epoch, slot=slot, max_graphs=max_graphs, stream=stream)
-        arena = self.arena(max_graphs or B, slot)
-        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
-        arena.extract_cached(self._cache, self.link_y.data_ptr(), None if positions is None else positions.data_ptr(),
-                             first, B, st)
-        side = None
-        if self._side is not None:
-            idx = (torch.arange(first, first + B, device=self.link_y.device) if positions is None
-                   else positions[first:first + B].long())
-            side = self._side.index_select(0, idx)
-        return DeviceBatch(self, arena, B, positions, first, side)
 
 
 def links2subgraphs(Arow, Acol, links, labels, h=1, sample_ratio=1.0, max_nodes_per_hop=None, u_features=None,

@@ -115,7 +115,7 @@ def _host_built(ds, A, u, v):
     want = EX.reference_variants(lists, A)
     host = LeaveOneOutLinks(ds)
     for k in EX.CACHE_KEYS:
-        host._t[k][:len(want[k])].copy_(torch.from_numpy(want[k]))
+        host._cache_t[k][:len(want[k])].copy_(torch.from_numpy(want[k]))
     host._close_tail(len(want['var_link']), len(want['unodes']), len(want['vnodes']))
     return host, want, lists
 
