@@ -96,6 +96,11 @@ def build_parser():
                    help='rank the held-out links (test split under --testing, else validation split) among every user\'s '
                         'unseen items on the device, write hr / recall / precision / ndcg @K and mrr, and stop; uses '
                         '--recommend-users to restrict the users')
+    p.add_argument('--rank-negatives', type=int, default=None, metavar='K',
+                   help='--rank-eval: rank every held-out link among K uniformly sampled unseen items of its user (drawn on '
+                        'the device; the user\'s other held-out items stay in the list) instead of among all of them')
+    p.add_argument('--rank-draw', type=int, default=0, metavar='D',
+                   help='--rank-negatives: which draw of the negatives (default 0); another D gives another sample')
     p.add_argument('--new-ratings', default=None, metavar='FILE',
                    help='rating changes applied to the training graph ON THE DEVICE before --recommend / --rank-eval: lines '
                         '"user item rating" (ids as recommendations_*.tsv prints them, "#" comments; rating 0 removes the '
@@ -223,7 +228,8 @@ def rank_eval_ks(spec):
 
 def write_ranking(model, train_graphs, heldout_graphs, args):
     """``--rank-eval``: ``<res_dir>/ranking_<data_name>.tsv`` with lines ``metric\tvalue`` -- the ranking metrics of the held-out
-    links among every user's unseen items of the training graph (``igmc_amd/rank_eval.py``)."""
+    links among every user's unseen items of the training graph (``igmc_amd/rank_eval.py``); with ``--rank-negatives K`` among
+    K sampled ones, and two more lines ``negatives\tK`` and ``draw\tD``."""
     import time
     from igmc_amd.rank_eval import HeldOut, metric_names, rank_eval
     ks = rank_eval_ks(args.rank_eval)
@@ -232,13 +238,17 @@ def write_ranking(model, train_graphs, heldout_graphs, args):
     stats = {}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    res = rank_eval(model, train_graphs, heldout, ks=ks, batch_size=args.batch_size, users=users, stats=stats)      # (synchronises)
+    sampled = {} if args.rank_negatives is None else dict(negatives=args.rank_negatives, draw=args.rank_draw)
+    res = rank_eval(model, train_graphs, heldout, ks=ks, batch_size=args.batch_size, users=users, stats=stats,
+                    **sampled)      # (synchronises)
     dt = time.perf_counter() - t0
     names = metric_names(ks)
     path = os.path.join(args.res_dir, 'ranking_{}.tsv'.format(args.data_name))
     with open(path, 'w') as f:
         for k in names:
             f.write('%s\t%.6f\n' % (k, res[k]))
+        if sampled:
+            f.write('negatives\t%d\ndraw\t%d\n' % (args.rank_negatives, args.rank_draw))
     print('Ranked {} held-out links of {} users ({} not among the candidates; means over {} users) among {} candidates in '
           '{} pass(es), {:.0f} candidates/s: {}; wrote {}'.format(
               stats['queries'], stats['users'], stats['not_candidates'], res['users_evaluated'], stats['candidates'],
@@ -270,6 +280,14 @@ def main(argv=None):
     bad = flag_error(args.new_ratings, args.recommend or args.explain, args.rank_eval, args.use_features)
     if bad:
         parser.error(bad)
+    if args.rank_negatives is not None and not args.rank_eval:
+        parser.error('--rank-negatives samples the negatives of --rank-eval: give its cut-offs K[,K...]')
+    if args.rank_negatives is not None and not 0 <= args.rank_negatives < 2 ** 31:
+        parser.error('--rank-negatives takes K in [0, 2^31)')
+    if args.rank_draw and args.rank_negatives is None:
+        parser.error('--rank-draw names the draw of --rank-negatives K: give K')
+    if args.rank_draw < 0:
+        parser.error('--rank-draw takes D >= 0')
     if args.explain < 0 or args.explain > 64:
         parser.error('--explain takes M in [1, 64]')
     if args.explain > 0 and not args.explain_links and not args.recommend > 0:

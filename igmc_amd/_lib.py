@@ -76,6 +76,8 @@ SIGNATURES = {
     'igmc_select_extremes': (i32, [vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, i32, vp]),
     'igmc_candidates_count': (i32, [vp, vp, i32, vp, i32, vp, vp, vp]),
     'igmc_candidates_fill': (i32, [vp, vp, i32, vp, i32, vp, vp, vp, i64, vp, vp]),
+    'igmc_candidates_sample_count': (i32, [vp, vp, i32, vp, i32, vp, vp, i64, i64, vp, vp, vp]),
+    'igmc_candidates_sample_fill': (i32, [vp, vp, i32, vp, i32, vp, vp, i64, i64, u64, u64, vp, vp, vp, vp, i64, vp, vp]),
     'igmc_select_segments_scratch_bytes': (i64, [i32, i32, i32]),
     'igmc_select_segments': (i32, [vp, vp, i32, i32, vp, vp, vp, vp, i64, i32, vp]),
     'igmc_rank_segments': (i32, [vp, vp, i64, vp, i32, vp, vp, i64, vp, vp, vp, i32, vp]),

@@ -1272,6 +1272,41 @@ extern "C" int igmc_candidates_fill(const igmc_graph* g, const int32_t* d_users,
   HIPCHECK(hipGetLastError());
   return 0;
 }
+// ... cut down to k sampled negatives + the must items of every request (sampled_candidates.hip)
+static const char* sampled_args(const igmc_graph* g, const int32_t* d_users, int nq, const int64_t* d_must_off,
+                                const int32_t* d_must_item, int64_t n_must, int64_t k, const int32_t* d_err) {
+  if (!g || !d_users || !d_err) return "null argument";
+  if (nq < 1) return "nq must be at least 1";
+  if (k < 0 || k > (int64_t)INT32_MAX) return "k must be in [0, 2^31)";
+  if (n_must < 0 || n_must > (int64_t)INT32_MAX) return "n_must must be in [0, 2^31)";
+  if (d_must_off && n_must > 0 && !d_must_item) return "null argument";
+  return nullptr;
+}
+extern "C" int igmc_candidates_sample_count(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
+                                            int exclude_seen, const int64_t* d_must_off, const int32_t* d_must_item,
+                                            int64_t n_must, int64_t k, int64_t* d_counts, int32_t* d_err, void* stream) {
+  const char* bad = sampled_args(g, d_users, nq, d_must_off, d_must_item, n_must, k, d_err);
+  if (bad) IGMC_FAIL(bad);
+  if (!d_counts) IGMC_FAIL("null argument");
+  igmc_launch_sampled_count(g->d, d_users, nq, d_item_ok, exclude_seen != 0, d_must_off, d_must_item, n_must, (int)k, d_counts,
+                            d_err, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int igmc_candidates_sample_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
+                                           int exclude_seen, const int64_t* d_must_off, const int32_t* d_must_item,
+                                           int64_t n_must, int64_t k, uint64_t seed, uint64_t draw, const int64_t* d_offsets,
+                                           int32_t* d_link_u, int32_t* d_link_v, uint8_t* d_forced, int64_t capacity,
+                                           int32_t* d_err, void* stream) {
+  const char* bad = sampled_args(g, d_users, nq, d_must_off, d_must_item, n_must, k, d_err);
+  if (bad) IGMC_FAIL(bad);
+  if (!d_offsets || !d_link_u || !d_link_v) IGMC_FAIL("null argument");
+  if (capacity < 1 || capacity > (int64_t)INT32_MAX) IGMC_FAIL("capacity must be in [1, 2^31)");
+  igmc_launch_sampled_fill(g->d, d_users, nq, d_item_ok, exclude_seen != 0, d_must_off, d_must_item, n_must, (int)k, seed, draw,
+                           d_offsets, d_link_u, d_link_v, d_forced, capacity, d_err, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
 static int segsel_split(int ns, int num, int geometry) {
   if (ns < 1 || num < 1 || num > IGMC_SELECT_MAX_NUM || geometry < 0 || geometry > IGMC_SEGSEL_MAX_SPLIT) return -1;
   return geometry > 0 ? geometry : igmc_segsel_default_split(ns);

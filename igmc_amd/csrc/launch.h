@@ -90,6 +90,14 @@ void igmc_launch_candidates_count(const GraphDev& g, const int32_t* users, int n
 void igmc_launch_candidates_fill(const GraphDev& g, const int32_t* users, int nq, const uint8_t* item_ok, int exclude_seen,
                                  const int64_t* off, int32_t* link_u, int32_t* link_v, int64_t capacity, int32_t* err,
                                  void* stream);
+// sampled_candidates.hip: the same segments cut down to k sampled negatives + the must items of every request
+void igmc_launch_sampled_count(const GraphDev& g, const int32_t* users, int nq, const uint8_t* item_ok, int exclude_seen,
+                               const int64_t* must_off, const int32_t* must_item, int64_t n_must, int k, int64_t* counts,
+                               int32_t* err, void* stream);
+void igmc_launch_sampled_fill(const GraphDev& g, const int32_t* users, int nq, const uint8_t* item_ok, int exclude_seen,
+                              const int64_t* must_off, const int32_t* must_item, int64_t n_must, int k, uint64_t seed,
+                              uint64_t draw, const int64_t* off, int32_t* link_u, int32_t* link_v, uint8_t* forced,
+                              int64_t capacity, int32_t* err, void* stream);
 int igmc_segsel_default_split(int ns);
 void igmc_launch_select_segments(const float* keys, const int64_t* seg_off, int ns, int num, int k, void* scratch,
                                  int32_t* idx_out, float* key_out, int32_t* count, void* stream);

@@ -29,6 +29,16 @@ candidate's position is its index in ITS PASS's list.  Where a per-hop cap binds
 ``max_nodes_per_hop`` is sampled), a candidate's score -- and so a held-out link's RANK -- depends on where it sits in its
 pass, hence on ``users_per_pass`` and on the users evaluated with it; every result is still a deterministic function of
 (seed, users, ``users_per_pass``).  Where no cap binds the ranks do not depend on how the users are divided into passes.
+
+SAMPLED NEGATIVES (``negatives=K``): the protocol most of the top-N literature reports -- every user's held-out items ranked
+among K uniformly sampled unseen items (NCF's "99 negatives") instead of among all of them.  The pass's list of a user is then
+its held-out items (the must items of ``recommend.CandidateLinks.refill``) and the K items of the REST of its candidates with
+the smallest hash key under (the dataset's seed, ``draw``, the user id): a user's negatives do not depend on the users
+evaluated with it or on ``users_per_pass``.  A user's OTHER held-out items stay in the list and compete with each of them,
+exactly as they do in the exhaustive evaluation, so ``negatives`` >= every user's number of other candidates reproduces the
+exhaustive result bit for bit; ranking each positive against the negatives alone is not offered.  ``not_candidates`` is what
+it is in the exhaustive run.  SAMPLER POSITIONS carries over, and positions in a sampled list differ from those in the full
+list: under a binding per-hop cap the sampled and the exhaustive score of the same pair may differ.
 """
 import numpy as np
 import torch
@@ -128,7 +138,7 @@ def reduce_metrics(cnt, dcg, ks):
 
 
 def rank_eval(model, dataset, heldout, ks=(5, 10, 20), batch_size=50, exclude_seen=True, item_mask=None, users=None,
-              users_per_pass=None, stats=None):
+              users_per_pass=None, stats=None, negatives=None, draw=0):
     """Ranking metrics of ``heldout`` (a :class:`HeldOut`, or a dataset: :meth:`HeldOut.from_links`) over the rating graph
     and with the extraction settings of ``dataset`` (normally the training set), for the held-out users -- or those of
     them that are in ``users`` --: for every pass of ``recommend`` (same candidates, same scores, same ``users_per_pass``)
@@ -141,8 +151,12 @@ def rank_eval(model, dataset, heldout, ks=(5, 10, 20), batch_size=50, exclude_se
     ``engine.rank_metrics`` returns them, and per link ``rank`` and ``pos``, its position in ITS PASS's candidate list
     (both -1 for a link that is no candidate), ``index`` (its place in ``heldout``; None = the same place).
 
-    ``stats`` receives ``users``, ``candidates``, ``passes``, ``queries`` and ``not_candidates``.  Side-feature datasets
-    raise ``NotImplementedError`` (``CandidateLinks``).  Works for ``DGCNN_RS`` too."""
+    ``negatives=K``: among ``K`` sampled negatives per user, drawn under ``draw`` (module docstring: SAMPLED NEGATIVES); the
+    default ranks among every candidate.
+
+    ``stats`` receives ``users``, ``candidates``, ``passes``, ``queries`` and ``not_candidates`` -- and ``negatives`` and
+    ``draw`` where ``negatives`` is given.  Side-feature datasets raise ``NotImplementedError`` (``CandidateLinks``).  Works
+    for ``DGCNN_RS`` too, and over a ``recommend.GraphView``."""
     if not isinstance(heldout, HeldOut):
         heldout = HeldOut.from_links(heldout)
     ks = [int(k) for k in ks]
@@ -155,7 +169,9 @@ def rank_eval(model, dataset, heldout, ks=(5, 10, 20), batch_size=50, exclude_se
     bounds = q_off.tolist()                 # (per user, once: the passes' slices of the query list)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
     pos, rank, total, passes = [], [], 0, 0
-    for q0, cands, R in candidate_passes(model, dataset, sel_users, batch_size, exclude_seen, item_mask, users_per_pass):
+    sampled = {} if negatives is None else dict(negatives=int(negatives), must=(q_off, items), draw=int(draw))
+    for q0, cands, R in candidate_passes(model, dataset, sel_users, batch_size, exclude_seen, item_mask, users_per_pass,
+                                         **sampled):
         m = cands.users.numel()
         a, b = bounds[q0], bounds[q0 + m]
         p, r = engine.rank_segments(R, cands.link_v[:len(cands)], cands.offsets, (q_off[q0:q0 + m + 1] - a).contiguous(),
@@ -173,6 +189,8 @@ def rank_eval(model, dataset, heldout, ks=(5, 10, 20), batch_size=50, exclude_se
     if stats is not None:
         stats.update(users=sel_users.numel(), candidates=total, passes=passes, queries=items.numel(),
                      not_candidates=int(host[-2]))
+        if negatives is not None:
+            stats.update(negatives=int(negatives), draw=int(draw))
     out = dict(zip(metric_names(ks), host[:-3]))
     out['users_evaluated'] = int(host[-3])
     out['per_user'] = dict(users=sel_users, offsets=q_off, items=items, relevant=relevant, cnt=cnt, dcg=dcg, rank=rank,

@@ -20,6 +20,15 @@ sampled subgraph -- and so its score -- depends on where it sits in its pass, he
 requested with it; every result is still a deterministic function of (seed, users, ``users_per_pass``).  Where no cap binds
 the extraction draws nothing and the scores do not depend on how the users are divided into passes.
 
+SAMPLED NEGATIVES (``negatives=K``; ``igmc_amd/csrc/sampled_candidates.hip``).  ``igmc_candidates_sample_count`` / ``_fill``
+write, per user, the K unseen items with the smallest ``igmc_sample_key(igmc_negative_salt(seed, draw, user), item)`` -- a
+uniform K-subset keyed by the source's ``seed``, ``draw`` and the user ID, never by the users asked for with it, by
+``users_per_pass`` or by the launch -- next to the request's MUST items (``must``: the held-out items of
+``rank_eval.rank_eval``), which are always listed where they are candidates and are no part of the pool the K are drawn from.
+A user with fewer than K other candidates gets them all.  SAMPLER POSITIONS applies unchanged, and a candidate's position in a
+sampled list is not its position in the full list: under a binding per-hop cap the sampled and the exhaustive score of the
+same pair may differ.
+
 ``link_y`` of a candidate list is zeros: the squared-error sums a scoring pass accumulates over candidates are MEANINGLESS and
 are dropped here.
 """
@@ -36,7 +45,9 @@ _INT32_MAX = 2 ** 31 - 1
 
 _ERRORS = ((1, 'a user\'s candidates reach past the capacity of the link buffers'),
            (2, 'a user id outside [0, n_users)'),
-           (4, 'segment offsets that are not the prefix sums of the counts'))
+           (4, 'segment offsets that are not the prefix sums of the counts'),
+           (8, 'a must item outside [0, n_items)'),
+           (16, 'must offsets that decrease or leave the must list'))
 
 
 def _dev_int32(x, dev, what):
@@ -70,7 +81,8 @@ class CandidateLinks(LinkSource):
 
     The link buffers hold ``capacity`` entries at fixed addresses; ``len()`` is the number of links the last
     :meth:`refill` / :meth:`set_pairs` wrote.  After :meth:`refill`, ``users`` (int32 ``[nq]``) and ``offsets`` (int64
-    ``[nq + 1]``) describe the per-user segments; after :meth:`set_pairs` they are ``None``."""
+    ``[nq + 1]``) describe the per-user segments; after :meth:`set_pairs` they are ``None``.  After a refill with
+    ``negatives``, ``forced`` (uint8 ``[len()]``) is 1 where the link is a must item and 0 where it was drawn; else ``None``."""
     dynamic = True          # subgraphs are extracted on the fly, under the sampling key of the pass
 
     def __init__(self, dataset, capacity):
@@ -83,23 +95,23 @@ class CandidateLinks(LinkSource):
         self.link_v = torch.zeros(capacity, dtype=torch.int32, device=dev)      #  launch prefetches past the end of a short pass)
         self.link_y = torch.zeros(capacity, dtype=torch.float32, device=dev)
         self.n = 0
-        self.users, self.offsets = None, None
+        self.users, self.offsets, self.forced, self._forced = None, None, None, None
 
     # ---- constructors
     @classmethod
-    def for_users(cls, dataset, users, exclude_seen=True, item_mask=None, capacity=None):
+    def for_users(cls, dataset, users, exclude_seen=True, item_mask=None, capacity=None, negatives=None, must=None, draw=0):
         """The candidates of ``users`` (ids, host or device; duplicates allowed, each gets its own segment): every item --
         of ``item_mask`` (bool / uint8 ``[n_items]``) where given -- that the user has no entry for in the dataset's rating
         graph (``exclude_seen``), users in the order given, item id ascending.  ``capacity``: entries of the link buffers
-        (default: what these users need)."""
+        (default: what these users need).  ``negatives`` / ``must`` / ``draw``: see :meth:`refill`."""
         dev = dataset.link_y.device
         users = _dev_int32(users, dev, 'users')
         mask = _item_mask(dataset.graph, item_mask, dev)
         if capacity is None:
-            counts, _ = _count(dataset.graph, users, mask, exclude_seen)
+            counts, _ = _count(dataset.graph, users, mask, exclude_seen, negatives, _must(must, users, dev, negatives))
             capacity = max(1, int(counts.sum().item()))
         self = cls(dataset, capacity)
-        self.refill(users, exclude_seen, mask)
+        self.refill(users, exclude_seen, mask, negatives, must, draw)
         return self
 
     @classmethod
@@ -110,28 +122,42 @@ class CandidateLinks(LinkSource):
         return self
 
     # ---- refilling in place
-    def refill(self, users, exclude_seen=True, item_mask=None):
-        """Enumerate the candidates of ``users`` into the link buffers (two launches, one host read: the total)."""
+    def refill(self, users, exclude_seen=True, item_mask=None, negatives=None, must=None, draw=0):
+        """Enumerate the candidates of ``users`` into the link buffers (two launches, one host read: the total).
+
+        ``negatives=K``: every user's ``K`` sampled candidates only (module docstring: SAMPLED NEGATIVES) under the source's
+        ``seed`` and ``draw``, plus the user's must items -- ``must = (offsets int64 [nq + 1], items int32)``, device tensors:
+        request ``q`` must list ``items[offsets[q]:offsets[q + 1]]`` --; ``forced`` then tells the two apart.
+        ``negatives=None``: ``igmc_candidates_count`` / ``_fill``, every candidate."""
         dev = self.link_y.device
         users = _dev_int32(users, dev, 'users')
         if users.numel() < 1:
             raise ValueError('no users')
         mask = _item_mask(self.graph, item_mask, dev)
-        counts, err = _count(self.graph, users, mask, exclude_seen)
+        must = _must(must, users, dev, negatives)
+        counts, err = _count(self.graph, users, mask, exclude_seen, negatives, must)
         offsets = torch.zeros(users.numel() + 1, dtype=torch.int64, device=dev)
         torch.cumsum(counts, 0, out=offsets[1:])
         total = int(offsets[-1].item())
         if total > self.capacity:
             raise ValueError('%d candidates do not fit the link buffers (capacity %d)' % (total, self.capacity))
         st = torch.cuda.current_stream().cuda_stream
-        self.lib.call('igmc_candidates_fill', self.graph.handle, engine._p(users.data_ptr()), users.numel(),
-                      engine._p(None if mask is None else mask.data_ptr()), int(bool(exclude_seen)),
-                      engine._p(offsets.data_ptr()), engine._p(self.link_u.data_ptr()), engine._p(self.link_v.data_ptr()),
-                      self.capacity, engine._p(err.data_ptr()), engine._p(st))
+        head = (self.graph.handle, engine._p(users.data_ptr()), users.numel(),
+                engine._p(None if mask is None else mask.data_ptr()), int(bool(exclude_seen)))
+        tail = (engine._p(offsets.data_ptr()), engine._p(self.link_u.data_ptr()), engine._p(self.link_v.data_ptr()))
+        if negatives is None:
+            self.lib.call('igmc_candidates_fill', *(head + tail + (self.capacity, engine._p(err.data_ptr()), engine._p(st))))
+        else:
+            if self._forced is None:
+                self._forced = torch.zeros(self.capacity, dtype=torch.uint8, device=dev)
+            self.lib.call('igmc_candidates_sample_fill', *(head + _must_args(must) + (int(negatives), self.seed, int(draw)) + tail +
+                                                           (engine._p(self._forced.data_ptr()), self.capacity,
+                                                            engine._p(err.data_ptr()), engine._p(st))))
         e = int(err.item())
         if e:
             raise RuntimeError('candidate enumeration: %s (err=%d)' % ('; '.join(w for b, w in _ERRORS if e & b), e))
         self.n, self.users, self.offsets = total, users, offsets
+        self.forced = None if negatives is None else self._forced[:total]
         return self
 
     def set_pairs(self, u, v):
@@ -148,7 +174,7 @@ class CandidateLinks(LinkSource):
                                                                                          self.graph.n_items))
         self.link_u[:u.numel()].copy_(u)
         self.link_v[:v.numel()].copy_(v)
-        self.n, self.users, self.offsets = u.numel(), None, None
+        self.n, self.users, self.offsets, self.forced = u.numel(), None, None, None
         return self
 
     def __len__(self):
@@ -164,14 +190,40 @@ def _item_mask(graph, item_mask, dev):
     return (m != 0).to(device=dev, dtype=torch.uint8).contiguous()
 
 
-def _count(graph, users, mask, exclude_seen):
+def _must(must, users, dev, negatives):
+    """``must`` of :meth:`CandidateLinks.refill` as contiguous device tensors ``(offsets int64 [nq + 1], items int32)``, or
+    None."""
+    if must is None:
+        return None
+    if negatives is None:
+        raise ValueError('must items come with negatives=K: an exhaustive list holds every candidate already')
+    off, items = must
+    off = torch.as_tensor(off).to(device=dev, dtype=torch.int64).contiguous()
+    items = torch.as_tensor(items).to(device=dev, dtype=torch.int32).contiguous()
+    if off.dim() != 1 or off.numel() != users.numel() + 1 or items.dim() != 1:
+        raise ValueError('must: (offsets [nq + 1], items), one offset range per requested user')
+    return off, items
+
+
+def _must_args(must):
+    if must is None:
+        return None, None, 0
+    return engine._p(must[0].data_ptr()), engine._p(must[1].data_ptr() if must[1].numel() else None), must[1].numel()
+
+
+def _count(graph, users, mask, exclude_seen, negatives=None, must=None):
     """Per-user candidate counts (device int64) and the launch's error word (device int32, not read here)."""
     counts = torch.zeros(users.numel(), dtype=torch.int64, device=users.device)
     err = torch.zeros(1, dtype=torch.int32, device=users.device)
-    graph.lib.call('igmc_candidates_count', graph.handle, engine._p(users.data_ptr()), users.numel(),
-                   engine._p(None if mask is None else mask.data_ptr()), int(bool(exclude_seen)),
-                   engine._p(counts.data_ptr()), engine._p(err.data_ptr()),
-                   engine._p(torch.cuda.current_stream().cuda_stream))
+    head = (graph.handle, engine._p(users.data_ptr()), users.numel(), engine._p(None if mask is None else mask.data_ptr()),
+            int(bool(exclude_seen)))
+    tail = (engine._p(counts.data_ptr()), engine._p(err.data_ptr()), engine._p(torch.cuda.current_stream().cuda_stream))
+    if negatives is None:
+        graph.lib.call('igmc_candidates_count', *(head + tail))
+    else:
+        if not 0 <= int(negatives) <= _INT32_MAX:
+            raise ValueError('negatives must be in [0, 2^31)')
+        graph.lib.call('igmc_candidates_sample_count', *(head + _must_args(must) + (int(negatives),) + tail))
     return counts, err
 
 
@@ -203,11 +255,14 @@ def top_n(cands, scores, n, geometry=0):
     return items, key, count
 
 
-def pass_plan(graph, n_users_requested, item_mask=None, users_per_pass=None):
+def pass_plan(graph, n_users_requested, item_mask=None, users_per_pass=None, per_user=None):
     """``(users_per_pass, capacity)`` of :func:`recommend`: by default the largest number of users whose WORST-CASE candidate
-    count (every item, or every item of the mask) stays within ``DEFAULT_CAPACITY`` -- at least one user, at most those
-    requested --; positions stay below 2^31 in every case."""
+    count (every item, or every item of the mask; with sampled negatives at most ``per_user`` = negatives + the longest must
+    list) stays within ``DEFAULT_CAPACITY`` -- at least one user, at most those requested --; positions stay below 2^31 in
+    every case."""
     worst = max(1, graph.n_items if item_mask is None else int((torch.as_tensor(item_mask) != 0).sum().item()))
+    if per_user is not None:
+        worst = max(1, min(worst, int(per_user)))
     if users_per_pass is None:
         upp = max(1, min(int(n_users_requested), DEFAULT_CAPACITY // worst))
     else:
@@ -217,12 +272,16 @@ def pass_plan(graph, n_users_requested, item_mask=None, users_per_pass=None):
     return upp, upp * worst
 
 
-def candidate_passes(model, dataset, users=None, batch_size=50, exclude_seen=True, item_mask=None, users_per_pass=None):
+def candidate_passes(model, dataset, users=None, batch_size=50, exclude_seen=True, item_mask=None, users_per_pass=None,
+                     negatives=None, must=None, draw=0):
     """The pass loop of :func:`recommend` and of ``rank_eval.rank_eval``: ``users`` (default: every user of the rating graph)
     in passes of ``users_per_pass`` (:func:`pass_plan`); a generator of ``(q0, cands, scores)`` -- the index of the pass's
     first user in ``users``, the ONE :class:`CandidateLinks` every pass refills (kept as ``dataset._recommend_links`` and
     reused by later calls that fit it, so every pass replays one captured ``ScoreGraph``) and the pass's scores
-    (:func:`score_candidates`).  ``cands`` is refilled by the next pass: take what you need from it before asking for it."""
+    (:func:`score_candidates`).  ``cands`` is refilled by the next pass: take what you need from it before asking for it.
+    ``negatives`` / ``must`` / ``draw``: sampled lists (:meth:`CandidateLinks.refill`); ``must`` covers all of ``users`` and
+    every pass gets its slice (one host read of the offsets), and the passes are planned for ``negatives`` + the longest must
+    list per user instead of every item."""
     from . import train_eval
     if model.flat_parameters().device.type != train_eval.device.type:
         model.to(train_eval.device)
@@ -233,10 +292,19 @@ def candidate_passes(model, dataset, users=None, batch_size=50, exclude_seen=Tru
     if nq < 1:
         raise ValueError('no users')
     mask = _item_mask(g, item_mask, dev)
-    upp, capacity = pass_plan(g, nq, mask, users_per_pass)
+    must = _must(must, users, dev, negatives)
+    per_user, bounds = None, None
+    if negatives is not None:
+        bounds = None if must is None else must[0].tolist()
+        per_user = int(negatives) + (max(b - a for a, b in zip(bounds[:-1], bounds[1:])) if bounds else 0)
+    upp, capacity = pass_plan(g, nq, mask, users_per_pass, per_user)
     cands = kept(dataset, '_recommend_links', lambda c: c.capacity >= capacity, lambda: CandidateLinks(dataset, capacity))
     for q0 in range(0, nq, upp):
-        cands.refill(users[q0:q0 + upp], exclude_seen, mask)
+        mine = None
+        if bounds is not None:
+            m = min(upp, nq - q0)
+            mine = ((must[0][q0:q0 + m + 1] - bounds[q0]).contiguous(), must[1][bounds[q0]:bounds[q0 + m]])
+        cands.refill(users[q0:q0 + upp], exclude_seen, mask, negatives, mine, draw)
         yield q0, cands, score_candidates(model, cands, batch_size)
 
 

@@ -417,6 +417,26 @@ int igmc_candidates_count(const igmc_graph* g, const int32_t* d_users, int nq, c
 int igmc_candidates_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok /* may be NULL */,
                          int exclude_seen, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v, int64_t capacity,
                          int32_t* d_err, void* stream);
+/* igmc_candidates_sample_count / igmc_candidates_sample_fill: the same segments cut down to k SAMPLED negatives (no reference
+ * counterpart; the sampled ranking protocol of the top-N literature -- held-out items among k uniformly drawn unseen items).
+ * With C(u) = the candidates of igmc_candidates_fill, M(q) = the MUST items d_must_item[d_must_off[q] .. d_must_off[q + 1])
+ * of request q (int32[n_must], any order, duplicates allowed; d_must_off int64[nq + 1]; d_must_off == NULL = no must items)
+ * and N = C(u) \ M(q), the segment of q is (M(q) n C(u)) u S, item ascending, where S = the min(k, |N|) items of N with the
+ * smallest sampling key of igmc_rng.h under that header's negative salt of (seed, draw, u): a uniform subset keyed by the user
+ * ID, so it does not depend on the users asked for with it or on the launch.  A must item that is no candidate is not listed.
+ * 0 <= k < 2^31, 0 <= n_must < 2^31; k >= |N| writes all of C(u) (with no must items: the bytes of igmc_candidates_fill),
+ * k = 0 the must items only.  _count writes |M n C| + min(k, |N|) (it needs no seed); _fill also writes d_forced[p] (uint8,
+ * may be NULL) = 1 where the item at p is a must item, 0 where it was drawn.  d_err: bits 0 / 1 / 2 as above; bit 3 = a must
+ * item outside [0, n_items) (ignored); bit 4 = d_must_off[q] > d_must_off[q + 1] or outside [0, n_must] (that request's must
+ * list is treated as empty; nothing is read out of range).  One launch each, capturable. */
+int igmc_candidates_sample_count(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok /* may be NULL */,
+                                 int exclude_seen, const int64_t* d_must_off /* may be NULL */, const int32_t* d_must_item,
+                                 int64_t n_must, int64_t k, int64_t* d_counts, int32_t* d_err, void* stream);
+int igmc_candidates_sample_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok /* may be NULL */,
+                                int exclude_seen, const int64_t* d_must_off /* may be NULL */, const int32_t* d_must_item,
+                                int64_t n_must, int64_t k, uint64_t seed, uint64_t draw, const int64_t* d_offsets,
+                                int32_t* d_link_u, int32_t* d_link_v, uint8_t* d_forced /* may be NULL */, int64_t capacity,
+                                int32_t* d_err, void* stream);
 /* igmc_select_segments: the `num` first of every segment [d_seg_off[s], d_seg_off[s + 1]) of d_keys, s < ns (no reference
  * counterpart; by hand `np.lexsort` per user on the host), 1 <= num <= 64, d_seg_off[ns] < 2^31.
  * THE ORDER: key DESCENDING, then index ascending; every NaN behind every number (NaNs among themselves by index);

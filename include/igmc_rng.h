@@ -46,6 +46,15 @@ IGMC_HD uint64_t igmc_sample_salt(uint64_t seed, uint64_t epoch, uint64_t link, 
   return s;
 }
 
+/* salt for the sampled negatives of one (dataset seed, draw, user ID): keyed by the id, not by the user's place in a request,
+ * so a user's negatives do not depend on the users asked for with it */
+IGMC_HD uint64_t igmc_negative_salt(uint64_t seed, uint64_t draw, uint64_t user) {
+  uint64_t s = igmc_splitmix64(seed ^ 0x4E454753ull);
+  s = igmc_splitmix64(s ^ draw);
+  s = igmc_splitmix64(s ^ user);
+  return s;
+}
+
 /* bijective in `id` for fixed salt */
 IGMC_HD uint32_t igmc_sample_key(uint64_t salt, uint32_t id) {
   return igmc_fmix32(igmc_fmix32(id + (uint32_t)salt) ^ (uint32_t)(salt >> 32));
