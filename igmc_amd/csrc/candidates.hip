@@ -1,15 +1,36 @@
 // candidates.hip -- what surrounds a scoring pass over links NOBODY RATED: the candidate links of a set of users written straight
-// into device link arrays, and the `num` best of every user's score segment (no reference counterpart: the reference stops at the
-// test RMSE; a top-N list there would be a host loop over the complement of every user's row and a host argsort of its scores).
+// into device link arrays -- all of them, or cut down to K SAMPLED negatives --, and the `num` best of every user's score segment
+// (no reference counterpart: the reference stops at the test RMSE; a top-N list there would be a host loop over the complement
+// of every user's row and a host argsort of its scores, the sampled ranking protocol of the top-N literature -- every held-out
+// item ranked among K uniformly drawn unseen items -- a host loop of random.sample over that complement).
 //
-// k_candidates<0>  per-user counts; k_candidates<1>  the links, at offsets the caller derived from the counts.  One workgroup
-//                  per requested user (grid-stride).  The user's row -- sorted by (relation, item), so not searchable -- is
-//                  MARKED into an LDS bitmap over a tile of CAND_TILE items; wave w then takes the 64-item words w, w + 4, ...:
-//                  a lane per item, survivors (in range, not marked, item_ok) as one ballot; the word's place in the segment is
-//                  a block scan of the words' popcounts, a lane's place in its word the popcount of the ballot below it.
-//                  Output order = (users as given, item ascending), a function of the inputs alone: the only atomic is the
-//                  LDS bit-set of the marking, which commutes.  Graphs wider than a tile: the tiles one after the other, the
-//                  row walked once per tile.
+// THE SEGMENT of request q (user u = users[q]), igmc_hip.h states it for callers:
+//   C = the candidates: items in range, not in the user's row (exclude_seen), item_ok      -- cand_build_tile, the ONE definition
+//   exhaustive: segment = C, item ascending.
+//   sampled:    M = the must items of the request, must_item[must_off[q] .. must_off[q + 1])  (any order, duplicates allowed)
+//               N = C \ M, the negatives' pool;  S = the min(k, |N|) items of N with the smallest igmc_sample_key(salt, item),
+//               salt = igmc_negative_salt(seed, draw, u) -- keyed by the user ID, so S does not depend on q, on the users that
+//               share the launch or on the grid
+//               segment = (M n C) u S, item ascending; forced[pos] = 1 where the item is of M.
+//
+// k_candidates<FILL, SAMPLED>  <0, .> per-user counts (|C|, or |M n C| + min(k, |N|): no key is computed); <1, .> the links, at
+//                  offsets the caller derived from the counts.  One workgroup per requested user (grid-stride).  The user's row
+//                  -- sorted by (relation, item), so not searchable -- and, sampled, the must list are MARKED into LDS bitmaps
+//                  over a tile of CAND_TILE items; wave w then takes the 64-item words w, w + 4, ...: a lane per item, pool
+//                  and forced items as ballots; the word's place in the segment is a block scan of the words' popcounts, a
+//                  lane's place in its word the popcount of the ballot below it.  Output order = (users as given, item
+//                  ascending), a function of the inputs alone: the atomics are LDS bit-sets, which commute, and -- sampled
+//                  -- LDS histogram / list-cursor adds.
+//                  SAMPLED = false compiles the must bitmap, the forced ballots and every key out: the count is one walk,
+//                  the fill is one walk (the emission; it learns the segment's total there).
+//                  SAMPLED = true, the fill: the threshold T = the k-th smallest key of the pool: one histogram walk over the
+//                  keys' top byte finds the byte b that holds it, the keys OF b (|N| / 256 on average) are parked in a short
+//                  list and the r-th of them is found by counting; a byte with more keys than the list holds goes through
+//                  the remaining three radix passes instead.  Keys are a bijection of the id (igmc_rng.h): exactly k keys
+//                  are <= T either way.  The emission then keeps pool items with key <= T and every forced item.
+//                  Graphs wider than a tile (the definition knows no tiles): every walk -- count, histogram, parking, radix
+//                  passes, emission -- goes over the tiles one after the other and rebuilds the tile's ballots, the row
+//                  walked once per tile; a graph of one tile (every bundled dataset, ml_10m) builds them once per request.
 // k_segsel_part    workgroup (s, j) reduces slice j of the k contiguous slices of segment s to its `num` first words -- staged
 // k_segsel_merge   in LDS when the slice fits --; k == 1 writes the segment's result itself, k > 1 leaves partial lists that
 //                  one workgroup per segment merges.
@@ -28,74 +49,245 @@ static_assert(CAND_TILE == IGMC_CAND_TILE_ITEMS, "launch.h names the tile");
 #define SEG_LDS_WORDS 4096                         // selection words a workgroup stages (32 KB); also 64 lists of 64 to merge
 static_assert(IGMC_SEGSEL_MAX_SPLIT * IGMC_SELECT_MAX_NUM <= SEG_LDS_WORDS, "the merge stages every partial list");
 
-template <int FILL>
-__global__ __launch_bounds__(IGMC_BLOCK) void k_candidates(GraphDev g, const int32_t* __restrict__ users, int nq,
-                                                           const uint8_t* __restrict__ item_ok, int exclude_seen,
-                                                           int64_t* __restrict__ counts, const int64_t* __restrict__ off,
-                                                           int32_t* __restrict__ link_u, int32_t* __restrict__ link_v,
-                                                           int64_t capacity, int32_t* err) {
-  __shared__ uint32_t bm[2 * CAND_TILE_WORDS];              // items of the tile the user rated
-  __shared__ unsigned long long surv[CAND_TILE_WORDS];      // candidates of the tile
-  __shared__ int woff[CAND_TILE_WORDS];
-  __shared__ int smi[8];
+// LDS of one workgroup: the must bitmap, the forced ballots, the histogram and the parked keys exist in the SAMPLED
+// instantiations alone (members in this order: the sampled fill's register count depends on it)
+template <bool SAMPLED>
+struct CandLds;
+template <>
+struct CandLds<false> {
+  uint32_t row[2 * CAND_TILE_WORDS];               // items of the tile the user rated
+  unsigned long long pool[CAND_TILE_WORDS];        // C of the tile
+  int woff[CAND_TILE_WORDS];
+  int smi[16];
+};
+template <>
+struct CandLds<true> {
+  uint32_t row[2 * CAND_TILE_WORDS];
+  uint32_t must[2 * CAND_TILE_WORDS];              // must items of the tile
+  unsigned long long pool[CAND_TILE_WORDS];        // N of the tile; the emission overwrites it with the words it writes
+  unsigned long long forc[CAND_TILE_WORDS];        // M n C of the tile
+  int woff[CAND_TILE_WORDS];
+  int hist[IGMC_BLOCK];
+  uint32_t ckey[IGMC_BLOCK];                       // parked keys of the deciding byte
+  int smi[16];
+};
+
+// pool (and forc) of the tile at tile0 (nw words).  report: a must item outside [0, n_items) raises bit 3 (first walk only)
+template <bool SAMPLED>
+__device__ __forceinline__ void cand_build_tile(const CandArgs& a, CandLds<SAMPLED>& s, int lo, int hi, int64_t mo, int64_t me,
+                                                int tile0, int nw, bool report) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nwave = IGMC_BLOCK >> 6;
-  for (int q = blockIdx.x; q < nq; q += gridDim.x) {
-    const int u = users[q];
-    if (u < 0 || u >= g.n_users) {        // (uniform over the workgroup) no row is read; the segment is empty
+  s.row[2 * t] = s.row[2 * t + 1] = 0u;
+  if constexpr (SAMPLED) s.must[2 * t] = s.must[2 * t + 1] = 0u;
+  __syncthreads();
+  for (int p = lo + t; p < hi; p += IGMC_BLOCK) {
+    const int v = a.g.u_idx[p] - tile0;
+    if (v >= 0 && v < CAND_TILE) atomicOr(&s.row[v >> 5], 1u << (v & 31));
+  }
+  if constexpr (SAMPLED) {
+    for (int64_t p = mo + t; p < me; p += IGMC_BLOCK) {
+      const int id = a.must_item[p];
+      if (id < 0 || id >= a.g.n_items) {        // ignored and reported
+        if (report) atomicOr(a.err, 8);
+        continue;
+      }
+      const int v = id - tile0;
+      if (v >= 0 && v < CAND_TILE) atomicOr(&s.must[v >> 5], 1u << (v & 31));
+    }
+  }
+  __syncthreads();
+  for (int w = wave; w < nw; w += nwave) {
+    const int v = tile0 + w * 64 + lane;
+    const int h = 2 * w + (lane >> 5), bit = lane & 31;
+    const bool cand = v < a.g.n_items && !((s.row[h] >> bit) & 1u) && (!a.item_ok || a.item_ok[v] != 0);
+    const unsigned long long c = __ballot(cand);
+    if constexpr (SAMPLED) {
+      const unsigned long long m = __ballot(cand && ((s.must[h] >> bit) & 1u));
+      if (lane == 0) {
+        s.pool[w] = c & ~m;
+        s.forc[w] = m;
+      }
+    } else {
+      if (lane == 0) s.pool[w] = c;
+    }
+  }
+  __syncthreads();
+}
+
+template <bool FILL, bool SAMPLED>
+__global__ __launch_bounds__(IGMC_BLOCK) void k_candidates(CandArgs a) {
+  __shared__ CandLds<SAMPLED> s;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nwave = IGMC_BLOCK >> 6;
+  const int n_items = a.g.n_items;
+  const bool one_tile = n_items <= CAND_TILE;
+  for (int q = blockIdx.x; q < a.nq; q += gridDim.x) {
+    const int u = a.users[q];
+    if (u < 0 || u >= a.g.n_users) {        // (uniform over the workgroup) no row is read; the segment is empty
       if (t == 0) {
-        atomicOr(err, 2);
-        if (!FILL) counts[q] = 0;
+        atomicOr(a.err, 2);
+        if (!FILL) a.counts[q] = 0;
       }
       continue;
     }
-    const int lo = exclude_seen ? g.u_ptr[u] : 0, hi = exclude_seen ? g.u_ptr[u + 1] : 0;
-    const int64_t base = FILL ? off[q] : 0;
-    int64_t end = FILL ? off[q + 1] : 0;
-    if (end > capacity) end = capacity;
-    int total = 0;
-    for (int tile0 = 0; tile0 < g.n_items; tile0 += CAND_TILE) {
-      const int left = g.n_items - tile0;
-      const int nw = left >= CAND_TILE ? CAND_TILE_WORDS : (left + 63) >> 6;
-      bm[2 * t] = 0u;
-      bm[2 * t + 1] = 0u;
-      __syncthreads();
-      for (int p = lo + t; p < hi; p += IGMC_BLOCK) {
-        const int v = g.u_idx[p] - tile0;
-        if (v >= 0 && v < CAND_TILE) atomicOr(&bm[v >> 5], 1u << (v & 31));
+    const int lo = a.exclude_seen ? a.g.u_ptr[u] : 0, hi = a.exclude_seen ? a.g.u_ptr[u + 1] : 0;
+    int64_t mo = 0, me = 0;
+    if constexpr (SAMPLED) {
+      if (a.must_off) {
+        mo = a.must_off[q];
+        me = a.must_off[q + 1];
+        if (mo < 0 || me < mo || me > a.n_must) {        // not followed: the must list is empty
+          if (t == 0) atomicOr(a.err, 16);
+          mo = me = 0;
+        }
       }
-      __syncthreads();
-      for (int w = wave; w < nw; w += nwave) {
-        const int v = tile0 + w * 64 + lane;
-        const bool keep = v < g.n_items && !((bm[2 * w + (lane >> 5)] >> (lane & 31)) & 1u) && (!item_ok || item_ok[v] != 0);
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) surv[w] = m;
+    }
+    // every walk: the tiles one after the other, their ballots rebuilt unless the graph is one tile (built by the first walk)
+    bool built = false;
+    auto tiles = [&](auto&& body) {
+      for (int tile0 = 0; tile0 < n_items; tile0 += CAND_TILE) {
+        const int left = n_items - tile0;
+        const int nw = left >= CAND_TILE ? CAND_TILE_WORDS : (left + 63) >> 6;
+        if (!(one_tile && built)) cand_build_tile(a, s, lo, hi, mo, me, tile0, nw, !built);
+        body(tile0, nw);
       }
-      __syncthreads();
-      int tile_total;
-      const int ex = igmc_block_scan_excl(t < nw ? __popcll(surv[t]) : 0, &tile_total, smi);
-      if (FILL) {
-        woff[t] = ex;
-        __syncthreads();
-        for (int w = wave; w < nw; w += nwave) {
-          const unsigned long long m = surv[w];
-          if ((m >> lane) & 1ull) {
-            const int64_t pos = base + total + woff[w] + __popcll(m & ((1ull << lane) - 1ull));
-            if (pos >= 0 && pos < end) {        // (what has no place is reported below, never written)
-              link_u[pos] = u;
-              link_v[pos] = tile0 + w * 64 + lane;
+      built = true;
+    };
+
+    // ---- walk 1: |N| and |M n C|.  Not for the exhaustive fill: its emission is its only walk
+    int n_pool = 0, n_forc = 0;
+    if constexpr (SAMPLED || !FILL) {
+      tiles([&](int, int nw) {
+        int tp;
+        igmc_block_scan_excl(t < nw ? __popcll(s.pool[t]) : 0, &tp, s.smi);
+        n_pool += tp;
+        if constexpr (SAMPLED) {
+          int tf;
+          igmc_block_scan_excl(t < nw ? __popcll(s.forc[t]) : 0, &tf, s.smi);
+          n_forc += tf;
+        }
+      });
+    }
+    const int kk = SAMPLED && a.k < n_pool ? a.k : n_pool;
+    int total = n_forc + kk;
+    if constexpr (!FILL) {
+      if (t == 0) a.counts[q] = total;
+      __syncthreads();        // (the next request builds over the tile)
+    } else {
+      // ---- sampled: the threshold, for kk in (0, |N|) only -- nothing or everything of the pool otherwise
+      uint32_t T = 0u;
+      uint64_t salt = 0;
+      bool by_key = false, all = true;
+      if constexpr (SAMPLED) {
+        // keys of the pool items of a tile, a lane per item
+        auto keys = [&](int tile0, int nw, auto&& f) {
+          for (int w = wave; w < nw; w += nwave)
+            if ((s.pool[w] >> lane) & 1ull) f(igmc_sample_key(salt, (uint32_t)(tile0 + w * 64 + lane)));
+        };
+        by_key = kk > 0 && kk < n_pool;
+        all = kk == n_pool;
+        salt = igmc_negative_salt(a.seed, a.draw, (uint64_t)(uint32_t)u);
+        if (by_key) {
+          s.hist[t] = 0;
+          __syncthreads();
+          tiles([&](int tile0, int nw) {
+            keys(tile0, nw, [&](uint32_t key) { atomicAdd(&s.hist[key >> 24], 1); });
+            __syncthreads();
+          });
+          int tot;
+          int c = s.hist[t];
+          int ex = igmc_block_scan_excl(c, &tot, s.smi);
+          if (c > 0 && ex < kk && kk <= ex + c) {
+            s.smi[8] = t;
+            s.smi[9] = kk - ex;
+            s.smi[10] = c;
+          }
+          if (t == 0) s.smi[11] = 0;
+          __syncthreads();
+          const uint32_t b = (uint32_t)s.smi[8];
+          int r = s.smi[9];
+          const int cb = s.smi[10];
+          __syncthreads();
+          if (cb <= IGMC_SAMPLE_PARK) {
+            tiles([&](int tile0, int nw) {
+              keys(tile0, nw, [&](uint32_t key) {
+                if ((key >> 24) == b) s.ckey[atomicAdd(&s.smi[11], 1)] = key;
+              });
+              __syncthreads();
+            });
+            if (t < cb) {
+              const uint32_t mine = s.ckey[t];
+              int below = 0;
+              for (int j = 0; j < cb; ++j) below += s.ckey[j] < mine;
+              if (below == r - 1) s.smi[12] = (int)mine;        // (keys never tie: one thread)
             }
+            __syncthreads();
+            T = (uint32_t)s.smi[12];
+          } else {
+            uint32_t prefix = b << 24, mask = 0xFF000000u;
+            for (int pass = 2; pass >= 0; --pass) {
+              const int shift = pass * 8;
+              s.hist[t] = 0;
+              __syncthreads();
+              tiles([&](int tile0, int nw) {
+                keys(tile0, nw, [&](uint32_t key) {
+                  if ((key & mask) == prefix) atomicAdd(&s.hist[(key >> shift) & 255u], 1);
+                });
+                __syncthreads();
+              });
+              c = s.hist[t];
+              ex = igmc_block_scan_excl(c, &tot, s.smi);
+              if (c > 0 && ex < r && r <= ex + c) {
+                s.smi[8] = t;
+                s.smi[9] = r - ex;
+              }
+              __syncthreads();
+              prefix |= ((uint32_t)s.smi[8]) << shift;
+              mask |= 0xFFu << shift;
+              r = s.smi[9];
+              __syncthreads();
+            }
+            T = prefix;
           }
         }
       }
-      total += tile_total;
-      __syncthreads();
-    }
-    if (!FILL) {
-      if (t == 0) counts[q] = total;
-    } else {
+      // ---- the emission: every pool item -- sampled: those with key <= T (kk == |N|: all of them, kk == 0: none) and the
+      // forced ones
+      const int64_t base = a.off[q];
+      int64_t end = a.off[q + 1];
+      if (end > a.capacity) end = a.capacity;
+      int done = 0;
+      tiles([&](int tile0, int nw) {
+        if constexpr (SAMPLED) {
+          for (int w = wave; w < nw; w += nwave) {
+            const bool in = (s.pool[w] >> lane) & 1ull;
+            const unsigned long long m =
+                __ballot(in && (all || (by_key && igmc_sample_key(salt, (uint32_t)(tile0 + w * 64 + lane)) <= T)));
+            if (lane == 0) s.pool[w] = m | s.forc[w];
+          }
+          __syncthreads();
+        }
+        int tile_total;
+        s.woff[t] = igmc_block_scan_excl(t < nw ? __popcll(s.pool[t]) : 0, &tile_total, s.smi);
+        __syncthreads();
+        for (int w = wave; w < nw; w += nwave) {
+          const unsigned long long m = s.pool[w];
+          if ((m >> lane) & 1ull) {
+            const int64_t pos = base + done + s.woff[w] + __popcll(m & ((1ull << lane) - 1ull));
+            if (pos >= 0 && pos < end) {        // (what has no place is reported below, never written)
+              a.link_u[pos] = u;
+              a.link_v[pos] = tile0 + w * 64 + lane;
+              if constexpr (SAMPLED)
+                if (a.forced) a.forced[pos] = (uint8_t)((s.forc[w] >> lane) & 1ull);
+            }
+          }
+        }
+        done += tile_total;
+        __syncthreads();
+      });
+      if constexpr (!SAMPLED) total = done;        // (the exhaustive fill took no count walk)
       // bit 0: the segment reaches past `capacity` (nothing was written there); bit 2: the offsets are not the counts'
-      const int bad = ((base + total > capacity) ? 1 : 0) | ((base < 0 || off[q + 1] - base != (int64_t)total) ? 4 : 0);
-      if (t == 0 && bad) atomicOr(err, bad);
+      const int bad = ((base + total > a.capacity) ? 1 : 0) | ((base < 0 || a.off[q + 1] - base != (int64_t)total) ? 4 : 0);
+      if (t == 0 && bad) atomicOr(a.err, bad);
     }
   }
 }
@@ -217,17 +409,14 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_segsel_merge(const float* __rest
 // ------------------------------------------------------------------ host
 static int cand_grid(int64_t jobs) { return (int)(jobs < 1 ? 1 : jobs > 65536 ? 65536 : jobs); }
 
-void igmc_launch_candidates_count(const GraphDev& g, const int32_t* users, int nq, const uint8_t* item_ok, int exclude_seen,
-                                  int64_t* counts, int32_t* err, void* stream) {
-  IGMC_PLAUNCH("k_candidates_count", k_candidates<0>, cand_grid(nq), IGMC_BLOCK, 0, stream, g, users, nq, item_ok,
-               exclude_seen, counts, (const int64_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int64_t)0, err);
-}
-
-void igmc_launch_candidates_fill(const GraphDev& g, const int32_t* users, int nq, const uint8_t* item_ok, int exclude_seen,
-                                 const int64_t* off, int32_t* link_u, int32_t* link_v, int64_t capacity, int32_t* err,
-                                 void* stream) {
-  IGMC_PLAUNCH("k_candidates_fill", k_candidates<1>, cand_grid(nq), IGMC_BLOCK, 0, stream, g, users, nq, item_ok,
-               exclude_seen, (int64_t*)nullptr, off, link_u, link_v, capacity, err);
+void igmc_launch_candidates(const CandArgs& a, int fill, int sampled, void* stream) {
+  static const char* const names[2][2] = {{"k_candidates_count", "k_candidates_fill"},
+                                          {"k_sampled_candidates_count", "k_sampled_candidates_fill"}};
+  igmc_dispatch(
+      [&](auto fl, auto sa) {
+        IGMC_PLAUNCH(names[sa()][fl()], (k_candidates<fl(), sa()>), cand_grid(a.nq), IGMC_BLOCK, 0, stream, a);
+      },
+      fill != 0, sampled != 0);
 }
 
 // workgroups per segment where the caller names none.  The segments' lengths are on the device only, so the choice is made

@@ -1253,43 +1253,62 @@ extern "C" int igmc_select_extremes(const float* d_keys, int64_t n, int num, int
 }
 
 // ------------------------------------------------------------------ candidate links + the best of every segment (candidates.hip)
+// The four entry points -- every candidate, or (sample) cut down to k sampled negatives + the must items of every request --
+// fill ONE argument block: cand_args checks and files what all four take (the exhaustive pair: no must list, k = 0),
+// cand_fill_args what the two fills add.  Either returns the refusal, or null.
+static const char* cand_args(CandArgs* a, const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
+                             int exclude_seen, const int64_t* d_must_off, const int32_t* d_must_item, int64_t n_must, int64_t k,
+                             int32_t* d_err) {
+  if (!g || !d_users || !d_err) return "null argument";
+  if (nq < 1) return "nq must be at least 1";
+  if (k < 0 || k > (int64_t)INT32_MAX) return "k must be in [0, 2^31)";
+  if (n_must < 0 || n_must > (int64_t)INT32_MAX) return "n_must must be in [0, 2^31)";
+  if (d_must_off && n_must > 0 && !d_must_item) return "null argument";
+  *a = CandArgs{g->d, d_users, nq, d_item_ok, exclude_seen != 0, d_must_off, d_must_item, n_must, (int)k};
+  a->err = d_err;
+  return nullptr;
+}
+static const char* cand_fill_args(CandArgs* a, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v,
+                                  int64_t capacity) {
+  if (!d_offsets || !d_link_u || !d_link_v) return "null argument";
+  if (capacity < 1 || capacity > (int64_t)INT32_MAX) return "capacity must be in [1, 2^31)";
+  a->off = d_offsets;
+  a->link_u = d_link_u;
+  a->link_v = d_link_v;
+  a->capacity = capacity;
+  return nullptr;
+}
 extern "C" int igmc_candidates_count(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
                                      int exclude_seen, int64_t* d_counts, int32_t* d_err, void* stream) {
-  if (!g || !d_users || !d_counts || !d_err) IGMC_FAIL("null argument");
-  if (nq < 1) IGMC_FAIL("nq must be at least 1");
-  igmc_launch_candidates_count(g->d, d_users, nq, d_item_ok, exclude_seen != 0, d_counts, d_err, stream);
+  CandArgs a;
+  const char* bad = cand_args(&a, g, d_users, nq, d_item_ok, exclude_seen, nullptr, nullptr, 0, 0, d_err);
+  if (bad) IGMC_FAIL(bad);
+  if (!d_counts) IGMC_FAIL("null argument");
+  a.counts = d_counts;
+  igmc_launch_candidates(a, 0, 0, stream);
   HIPCHECK(hipGetLastError());
   return 0;
 }
 extern "C" int igmc_candidates_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
                                     int exclude_seen, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v,
                                     int64_t capacity, int32_t* d_err, void* stream) {
-  if (!g || !d_users || !d_offsets || !d_link_u || !d_link_v || !d_err) IGMC_FAIL("null argument");
-  if (nq < 1) IGMC_FAIL("nq must be at least 1");
-  if (capacity < 1 || capacity > (int64_t)INT32_MAX) IGMC_FAIL("capacity must be in [1, 2^31)");
-  igmc_launch_candidates_fill(g->d, d_users, nq, d_item_ok, exclude_seen != 0, d_offsets, d_link_u, d_link_v, capacity, d_err,
-                              stream);
+  CandArgs a;
+  const char* bad = cand_args(&a, g, d_users, nq, d_item_ok, exclude_seen, nullptr, nullptr, 0, 0, d_err);
+  if (!bad) bad = cand_fill_args(&a, d_offsets, d_link_u, d_link_v, capacity);
+  if (bad) IGMC_FAIL(bad);
+  igmc_launch_candidates(a, 1, 0, stream);
   HIPCHECK(hipGetLastError());
   return 0;
-}
-// ... cut down to k sampled negatives + the must items of every request (sampled_candidates.hip)
-static const char* sampled_args(const igmc_graph* g, const int32_t* d_users, int nq, const int64_t* d_must_off,
-                                const int32_t* d_must_item, int64_t n_must, int64_t k, const int32_t* d_err) {
-  if (!g || !d_users || !d_err) return "null argument";
-  if (nq < 1) return "nq must be at least 1";
-  if (k < 0 || k > (int64_t)INT32_MAX) return "k must be in [0, 2^31)";
-  if (n_must < 0 || n_must > (int64_t)INT32_MAX) return "n_must must be in [0, 2^31)";
-  if (d_must_off && n_must > 0 && !d_must_item) return "null argument";
-  return nullptr;
 }
 extern "C" int igmc_candidates_sample_count(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
                                             int exclude_seen, const int64_t* d_must_off, const int32_t* d_must_item,
                                             int64_t n_must, int64_t k, int64_t* d_counts, int32_t* d_err, void* stream) {
-  const char* bad = sampled_args(g, d_users, nq, d_must_off, d_must_item, n_must, k, d_err);
+  CandArgs a;
+  const char* bad = cand_args(&a, g, d_users, nq, d_item_ok, exclude_seen, d_must_off, d_must_item, n_must, k, d_err);
   if (bad) IGMC_FAIL(bad);
   if (!d_counts) IGMC_FAIL("null argument");
-  igmc_launch_sampled_count(g->d, d_users, nq, d_item_ok, exclude_seen != 0, d_must_off, d_must_item, n_must, (int)k, d_counts,
-                            d_err, stream);
+  a.counts = d_counts;
+  igmc_launch_candidates(a, 0, 1, stream);
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -1298,12 +1317,14 @@ extern "C" int igmc_candidates_sample_fill(const igmc_graph* g, const int32_t* d
                                            int64_t n_must, int64_t k, uint64_t seed, uint64_t draw, const int64_t* d_offsets,
                                            int32_t* d_link_u, int32_t* d_link_v, uint8_t* d_forced, int64_t capacity,
                                            int32_t* d_err, void* stream) {
-  const char* bad = sampled_args(g, d_users, nq, d_must_off, d_must_item, n_must, k, d_err);
+  CandArgs a;
+  const char* bad = cand_args(&a, g, d_users, nq, d_item_ok, exclude_seen, d_must_off, d_must_item, n_must, k, d_err);
+  if (!bad) bad = cand_fill_args(&a, d_offsets, d_link_u, d_link_v, capacity);
   if (bad) IGMC_FAIL(bad);
-  if (!d_offsets || !d_link_u || !d_link_v) IGMC_FAIL("null argument");
-  if (capacity < 1 || capacity > (int64_t)INT32_MAX) IGMC_FAIL("capacity must be in [1, 2^31)");
-  igmc_launch_sampled_fill(g->d, d_users, nq, d_item_ok, exclude_seen != 0, d_must_off, d_must_item, n_must, (int)k, seed, draw,
-                           d_offsets, d_link_u, d_link_v, d_forced, capacity, d_err, stream);
+  a.seed = seed;
+  a.draw = draw;
+  a.forced = d_forced;
+  igmc_launch_candidates(a, 1, 1, stream);
   HIPCHECK(hipGetLastError());
   return 0;
 }

@@ -29,6 +29,16 @@ void igmc_launch_gate(int64_t* ctrl, int q, int gk_min, long long delay_ticks, i
                       void* stream);
 void igmc_launch_fill_u8(uint8_t* p, int64_t n, uint8_t v, void* stream);
 int igmc_extract_prepare(size_t smem);
+// keys of the deciding byte that a k-th-key selection parks in its short list (extract.hip: sample_fringe; candidates.hip: the
+// sampled fill); more go through the radix passes
+#ifdef IGMC_HIPEMU
+// (CPU emulation only: the tests lower the bound through the environment to drive the four-pass path)
+#include <stdlib.h>
+static inline int igmc_sample_park() { const char* e = getenv("IGMC_SAMPLE_PARK"); return e ? atoi(e) : IGMC_BLOCK; }
+#define IGMC_SAMPLE_PARK igmc_sample_park()
+#else
+#define IGMC_SAMPLE_PARK IGMC_BLOCK
+#endif
 
 // model.hip
 // auxiliary streams / events of a model (created with it; no launch sequence uses them at present: see the note at k_wgrad)
@@ -81,23 +91,31 @@ void igmc_launch_scores_store(const BatchDev& b, const float* out, double* acc, 
 int igmc_select_default_grid(int64_t n);
 void igmc_launch_select(const float* keys, int64_t n, int num, int grid, void* scratch, int32_t* idx_low, int32_t* idx_high,
                         float* key_low, float* key_high, int32_t* count, void* stream);
-// candidates.hip: the candidate links of a set of users (count, then fill at the offsets of the counts) and the `num` first of
-// every segment of a key array in the order (key descending, index ascending)
+// candidates.hip: the candidate links of a set of users (count, then fill at the offsets of the counts) -- every candidate, or
+// (sampled) cut down to k sampled negatives + the must items of every request: ONE kernel template, k_candidates<fill, sampled>
+// -- and the `num` first of every segment of a key array in the order (key descending, index ascending)
 #define IGMC_CAND_TILE_ITEMS 16384      // items of one LDS bitmap tile of the enumeration (wider graphs: tile after tile)
 #define IGMC_SEGSEL_MAX_SPLIT 64        // workgroups per segment at most (64 lists of 64 words are what the merge stages)
-void igmc_launch_candidates_count(const GraphDev& g, const int32_t* users, int nq, const uint8_t* item_ok, int exclude_seen,
-                                  int64_t* counts, int32_t* err, void* stream);
-void igmc_launch_candidates_fill(const GraphDev& g, const int32_t* users, int nq, const uint8_t* item_ok, int exclude_seen,
-                                 const int64_t* off, int32_t* link_u, int32_t* link_v, int64_t capacity, int32_t* err,
-                                 void* stream);
-// sampled_candidates.hip: the same segments cut down to k sampled negatives + the must items of every request
-void igmc_launch_sampled_count(const GraphDev& g, const int32_t* users, int nq, const uint8_t* item_ok, int exclude_seen,
-                               const int64_t* must_off, const int32_t* must_item, int64_t n_must, int k, int64_t* counts,
-                               int32_t* err, void* stream);
-void igmc_launch_sampled_fill(const GraphDev& g, const int32_t* users, int nq, const uint8_t* item_ok, int exclude_seen,
-                              const int64_t* must_off, const int32_t* must_item, int64_t n_must, int k, uint64_t seed,
-                              uint64_t draw, const int64_t* off, int32_t* link_u, int32_t* link_v, uint8_t* forced,
-                              int64_t capacity, int32_t* err, void* stream);
+struct CandArgs {
+  GraphDev g;
+  const int32_t* users;
+  int nq;
+  const uint8_t* item_ok;
+  int exclude_seen;
+  const int64_t* must_off;      // sampled; null: no request has must items
+  const int32_t* must_item;
+  int64_t n_must;
+  int k;
+  uint64_t seed, draw;          // sampled fill
+  int64_t* counts;              // count
+  const int64_t* off;           // fill
+  int32_t* link_u;
+  int32_t* link_v;
+  uint8_t* forced;              // sampled fill; may be null
+  int64_t capacity;
+  int32_t* err;
+};
+void igmc_launch_candidates(const CandArgs& a, int fill, int sampled, void* stream);
 int igmc_segsel_default_split(int ns);
 void igmc_launch_select_segments(const float* keys, const int64_t* seg_off, int ns, int num, int k, void* scratch,
                                  int32_t* idx_out, float* key_out, int32_t* count, void* stream);

@@ -465,7 +465,55 @@ def select_segments(keys, seg_off, num, geometry=0, lib=None, stream=None):
     return idx, key, count
 
 
-RANK_ERRORS = ((1, 'query offsets that are not 0 = q_off[0] <= ... <= q_off[ns] = the number of queries'),
+def _must_args(must):
+    if must is None:
+        return None, None, 0
+    return _p(must[0].data_ptr()), _p(must[1].data_ptr() if must[1].numel() else None), must[1].numel()
+
+
+def _candidates_args(graph, users, mask, exclude_seen, negatives, must):
+    """The entry point's prefix (``igmc_candidates`` / ``igmc_candidates_sample``) and the leading arguments its count and its
+    fill share."""
+    head = (graph.handle, _p(users.data_ptr()), users.numel(), _p(None if mask is None else mask.data_ptr()),
+            int(bool(exclude_seen)))
+    if negatives is None:
+        return 'igmc_candidates', head
+    if not 0 <= int(negatives) <= 2 ** 31 - 1:
+        raise ValueError('negatives must be in [0, 2^31)')
+    return 'igmc_candidates_sample', head + _must_args(must) + (int(negatives),)
+
+
+def candidates_count(graph, users, mask, exclude_seen, negatives=None, must=None, stream=None):
+    """Per-user candidate counts of ``users`` (device int32) over ``graph`` (``igmc_candidates_count``; ``negatives=K``:
+    ``igmc_candidates_sample_count`` -- K sampled negatives + the must items, ``must = (offsets int64 [nq + 1], items
+    int32)``, device tensors; no reference counterpart).  ``mask``: device uint8 ``[n_items]`` or None.  Returns device
+    tensors ``(counts int64 [nq], err int32 [1])``; the error word is left to the caller to read."""
+    import torch
+    counts = torch.zeros(users.numel(), dtype=torch.int64, device=users.device)
+    err = torch.zeros(1, dtype=torch.int32, device=users.device)
+    name, args = _candidates_args(graph, users, mask, exclude_seen, negatives, must)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    graph.lib.call(name + '_count', *(args + (_p(counts.data_ptr()), _p(err.data_ptr()), _p(st))))
+    return counts, err
+
+
+def candidates_fill(graph, users, mask, exclude_seen, offsets, link_u, link_v, err, negatives=None, must=None, seed=0,
+                    draw=0, forced=None, stream=None):
+    """The candidate links of ``users`` written at ``offsets`` (device int64 ``[nq + 1]``: the prefix sums of
+    :func:`candidates_count` under the same arguments) into the device int32 buffers ``link_u`` / ``link_v``
+    (``igmc_candidates_fill``; ``negatives=K``: ``igmc_candidates_sample_fill`` under ``seed`` / ``draw``, which also marks
+    the must items in ``forced``, device uint8 or None).  ``err`` collects the error bits and is left to the caller."""
+    import torch
+    name, args = _candidates_args(graph, users, mask, exclude_seen, negatives, must)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    out = (_p(offsets.data_ptr()), _p(link_u.data_ptr()), _p(link_v.data_ptr()))
+    if negatives is not None:
+        args += (int(seed), int(draw))
+        out += (_p(None if forced is None else forced.data_ptr()),)
+    graph.lib.call(name + '_fill', *(args + out + (link_u.numel(), _p(err.data_ptr()), _p(st))))
+
+
+RANK_ERRORS = ((1,'query offsets that are not 0 = q_off[0] <= ... <= q_off[ns] = the number of queries'),
                (2, 'a segment outside the keys'))
 
 

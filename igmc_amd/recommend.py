@@ -2,7 +2,7 @@
 
 Scoring a link that is absent from the rating graph is the model's normal case (test links are not in ``adj_train``), so a
 recommendation is a scoring pass (:func:`igmc_amd.train_eval.score_links`) with two kernels around it
-(``igmc_amd/csrc/candidates.hip``):
+(``igmc_amd/csrc/candidates.hip``; their ctypes calls: ``engine.candidates_count`` / ``candidates_fill`` / ``select_segments``):
 
 * ``igmc_candidates_count`` / ``igmc_candidates_fill`` write the unseen items of the requested users straight into device link
   arrays -- users in the order given, item id ascending within a user;
@@ -20,7 +20,7 @@ sampled subgraph -- and so its score -- depends on where it sits in its pass, he
 requested with it; every result is still a deterministic function of (seed, users, ``users_per_pass``).  Where no cap binds
 the extraction draws nothing and the scores do not depend on how the users are divided into passes.
 
-SAMPLED NEGATIVES (``negatives=K``; ``igmc_amd/csrc/sampled_candidates.hip``).  ``igmc_candidates_sample_count`` / ``_fill``
+SAMPLED NEGATIVES (``negatives=K``; the same kernel's sampled instantiations).  ``igmc_candidates_sample_count`` / ``_fill``
 write, per user, the K unseen items with the smallest ``igmc_sample_key(igmc_negative_salt(seed, draw, user), item)`` -- a
 uniform K-subset keyed by the source's ``seed``, ``draw`` and the user ID, never by the users asked for with it, by
 ``users_per_pass`` or by the launch -- next to the request's MUST items (``must``: the held-out items of
@@ -108,7 +108,8 @@ class CandidateLinks(LinkSource):
         users = _dev_int32(users, dev, 'users')
         mask = _item_mask(dataset.graph, item_mask, dev)
         if capacity is None:
-            counts, _ = _count(dataset.graph, users, mask, exclude_seen, negatives, _must(must, users, dev, negatives))
+            counts, _ = engine.candidates_count(dataset.graph, users, mask, exclude_seen, negatives,
+                                                _must(must, users, dev, negatives))
             capacity = max(1, int(counts.sum().item()))
         self = cls(dataset, capacity)
         self.refill(users, exclude_seen, mask, negatives, must, draw)
@@ -135,24 +136,16 @@ class CandidateLinks(LinkSource):
             raise ValueError('no users')
         mask = _item_mask(self.graph, item_mask, dev)
         must = _must(must, users, dev, negatives)
-        counts, err = _count(self.graph, users, mask, exclude_seen, negatives, must)
+        counts, err = engine.candidates_count(self.graph, users, mask, exclude_seen, negatives, must)
         offsets = torch.zeros(users.numel() + 1, dtype=torch.int64, device=dev)
         torch.cumsum(counts, 0, out=offsets[1:])
         total = int(offsets[-1].item())
         if total > self.capacity:
             raise ValueError('%d candidates do not fit the link buffers (capacity %d)' % (total, self.capacity))
-        st = torch.cuda.current_stream().cuda_stream
-        head = (self.graph.handle, engine._p(users.data_ptr()), users.numel(),
-                engine._p(None if mask is None else mask.data_ptr()), int(bool(exclude_seen)))
-        tail = (engine._p(offsets.data_ptr()), engine._p(self.link_u.data_ptr()), engine._p(self.link_v.data_ptr()))
-        if negatives is None:
-            self.lib.call('igmc_candidates_fill', *(head + tail + (self.capacity, engine._p(err.data_ptr()), engine._p(st))))
-        else:
-            if self._forced is None:
-                self._forced = torch.zeros(self.capacity, dtype=torch.uint8, device=dev)
-            self.lib.call('igmc_candidates_sample_fill', *(head + _must_args(must) + (int(negatives), self.seed, int(draw)) + tail +
-                                                           (engine._p(self._forced.data_ptr()), self.capacity,
-                                                            engine._p(err.data_ptr()), engine._p(st))))
+        if negatives is not None and self._forced is None:
+            self._forced = torch.zeros(self.capacity, dtype=torch.uint8, device=dev)
+        engine.candidates_fill(self.graph, users, mask, exclude_seen, offsets, self.link_u, self.link_v, err, negatives, must,
+                               self.seed, draw, self._forced)
         e = int(err.item())
         if e:
             raise RuntimeError('candidate enumeration: %s (err=%d)' % ('; '.join(w for b, w in _ERRORS if e & b), e))
@@ -203,28 +196,6 @@ def _must(must, users, dev, negatives):
     if off.dim() != 1 or off.numel() != users.numel() + 1 or items.dim() != 1:
         raise ValueError('must: (offsets [nq + 1], items), one offset range per requested user')
     return off, items
-
-
-def _must_args(must):
-    if must is None:
-        return None, None, 0
-    return engine._p(must[0].data_ptr()), engine._p(must[1].data_ptr() if must[1].numel() else None), must[1].numel()
-
-
-def _count(graph, users, mask, exclude_seen, negatives=None, must=None):
-    """Per-user candidate counts (device int64) and the launch's error word (device int32, not read here)."""
-    counts = torch.zeros(users.numel(), dtype=torch.int64, device=users.device)
-    err = torch.zeros(1, dtype=torch.int32, device=users.device)
-    head = (graph.handle, engine._p(users.data_ptr()), users.numel(), engine._p(None if mask is None else mask.data_ptr()),
-            int(bool(exclude_seen)))
-    tail = (engine._p(counts.data_ptr()), engine._p(err.data_ptr()), engine._p(torch.cuda.current_stream().cuda_stream))
-    if negatives is None:
-        graph.lib.call('igmc_candidates_count', *(head + tail))
-    else:
-        if not 0 <= int(negatives) <= _INT32_MAX:
-            raise ValueError('negatives must be in [0, 2^31)')
-        graph.lib.call('igmc_candidates_sample_count', *(head + _must_args(must) + (int(negatives),) + tail))
-    return counts, err
 
 
 def score_candidates(model, cands, batch_size=50):

@@ -1,5 +1,5 @@
 """Cases, numpy references and checks of ``igmc_candidates_sample_count`` / ``igmc_candidates_sample_fill``
-(``igmc_amd/csrc/sampled_candidates.hip``): every user's candidate segment cut down to k sampled negatives, the must items of
+(``igmc_amd/csrc/candidates.hip``): every user's candidate segment cut down to k sampled negatives, the must items of
 the request always kept.  Shared by the emulator test (tests/test_emu_sampled_candidates.py) and the GPU test
 (tests/test_gpu_sampled_candidates.py), as ``selection_checks.py`` is; every function takes a backend ``be`` of parity_checks
 and calls the C entry points directly, every buffer a call can write -- and every input an offset could lead past -- sits

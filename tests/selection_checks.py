@@ -241,9 +241,10 @@ def check_enumeration(be, n_items):
     g.close()
 
 
-def check_enumeration_no_place(be):
-    """What has no place is reported and not written: a capacity one short, offsets that are not the counts' prefix sums."""
-    A = graph_with_corner_rows(10, 200, 3)
+def check_enumeration_no_place(be, n_items=200):
+    """What has no place is reported and not written: a capacity one short, offsets that are not the counts' prefix sums.
+    ``n_items`` past a tile: the fill forms both bits from a total it only knows after the last tile."""
+    A = graph_with_corner_rows(10, n_items, 3)
     g = engine.Graph(A, device=be.device, lib=be.lib)
     users = np.array([4, 0, 7], np.int32)
     ru, rv, rc = enumerate_ref(A, users)

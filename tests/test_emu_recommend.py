@@ -25,6 +25,10 @@ def test_enumeration_reports_what_has_no_place_and_writes_nothing_there():
     SC.check_enumeration_no_place(EmuBackend())
 
 
+def test_enumeration_reports_what_has_no_place_on_a_graph_of_three_tiles():
+    SC.check_enumeration_no_place(EmuBackend(), 40000)
+
+
 def test_enumeration_reports_a_user_id_out_of_range():
     SC.check_enumeration_bad_user(EmuBackend(), (10, -1, 2 ** 31 - 1))
 

@@ -1,4 +1,4 @@
-"""``igmc_candidates_sample_count`` / ``igmc_candidates_sample_fill`` (``igmc_amd/csrc/sampled_candidates.hip``) on the CPU
+"""``igmc_candidates_sample_count`` / ``igmc_candidates_sample_fill`` (``igmc_amd/csrc/candidates.hip``) on the CPU
 emulation of the HIP sources: every segment is the numpy definition of ``tests/sampled_candidates_checks.py`` -- written from
 the text of ``include/igmc_rng.h``, so these tests also hold that restatement to the header's own code.  Cases, references and
 checks run unchanged on the device (``tests/test_gpu_sampled_candidates.py``)."""

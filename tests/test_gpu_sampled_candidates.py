@@ -1,4 +1,4 @@
-"""``k_sampled_candidates<0/1>`` (``igmc_amd/csrc/sampled_candidates.hip``) on a real MI355X through their C entry points,
+"""``k_candidates<0/1, 1>`` (``igmc_amd/csrc/candidates.hip``) on a real MI355X through their C entry points,
 against the numpy definition of ``tests/sampled_candidates_checks.py`` -- the cases, references and checks the emulator test
 runs (test_emu_sampled_candidates.py).  What the single-threaded emulator cannot show is what these are for: 256 threads
 marking the same LDS bitmap words, 64 lanes adding into the same histogram bins and list cursor, ballot placement, and a

@@ -1,5 +1,5 @@
 """Held-out ranking among K SAMPLED negatives on a real MI355X (``rank_eval(..., negatives=K)``, ``CandidateLinks.refill(...,
-negatives=, must=)``, ``igmc_amd/csrc/sampled_candidates.hip``) on the small case of ``tests/test_gpu_rank_eval.py`` (30 x 40,
+negatives=, must=)``, ``igmc_amd/csrc/candidates.hip``) on the small case of ``tests/test_gpu_rank_eval.py`` (30 x 40,
 70 held-out links, no cap): with more negatives than any user has candidates it is the exhaustive evaluation bit for bit; with
 7 the pass's list is the numpy definition of ``tests/sampled_candidates_checks.py``, ranks are the lexsort of that pass's own
 scores and the metrics their float64 restatement; passes do not matter; a ``GraphView`` and ``DGCNN_RS`` are served alike; and

@@ -1,5 +1,5 @@
 """The selection, enumeration and ranking kernels on a real MI355X, on raw keys, ids and graphs made with numpy and uploaded --
-no model, no dataset, no subprocess: ``k_select_*`` (scores.hip), ``k_candidates<0/1>``, ``k_segsel_part`` / ``k_segsel_merge``
+no model, no dataset, no subprocess: ``k_select_*`` (scores.hip), ``k_candidates<0/1, 0>``, ``k_segsel_part`` / ``k_segsel_merge``
 (candidates.hip) and ``k_rank_check / find / count / metrics`` (ranking.hip) through their C entry points, against the numpy
 references of ``tests/selection_checks.py`` -- the cases, references and checks the emulator tests run (test_emu_scores.py,
 test_emu_recommend.py, test_emu_rank_eval.py).  What the single-threaded emulator cannot show is what these are for: the 64-bit
@@ -63,6 +63,10 @@ def test_enumeration_is_the_numpy_complement(be, n_items):
 
 def test_enumeration_reports_what_has_no_place_and_writes_nothing_there(be):
     SC.check_enumeration_no_place(be)
+
+
+def test_enumeration_reports_what_has_no_place_on_a_graph_of_three_tiles(be):
+    SC.check_enumeration_no_place(be, 40000)
 
 
 def test_enumeration_reports_a_user_id_out_of_range(be):
