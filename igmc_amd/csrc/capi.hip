@@ -905,12 +905,14 @@ extern "C" int igmc_model_create(int device, int num_relations, int num_bases, i
   d.fin_stash = nullptr;
   d.datt_part = nullptr;
   d.fold_w = nullptr;
+  d.l3_vec = nullptr;
   if (d.R <= G2_NR * G2_NG_MAX)
   {   // (sums + d att partials in ONE allocation: a data-parallel step exchanges them as one span)
     fail |= M.get(&d.ts_part, (size_t)4 * IGMC_TS_BLOCKS * d.ts_stride) |
             M.get(&d.ts_raw, (size_t)4 * d.ts_stride + (size_t)4 * d.ts_stride / 32 * 4);
     if (!fail) d.datt_part = d.ts_raw + (size_t)4 * d.ts_stride;
     fail |= M.get(&d.fold_w, (size_t)IGMC_FOLD_WORDS);      // hand-off words of the one-launch tail
+    fail |= M.get(&d.l3_vec, Bc * 2 * (G2_NR + 2) * 32);    // layer 3's centre vectors (clustered training steps)
   }
   if (d.R <= 128) fail |= M.get(&d.fin_stash, (size_t)4 * IGMC_STASH_LAYER + 16);     // weights-only stash of k_finalize_ts (both modes)
   d.g2_ex = nullptr;
@@ -1079,6 +1081,12 @@ extern "C" int igmc_model_dense_path(const igmc_model* m, const igmc_batch* b, i
 
 extern "C" int igmc_model_step_form(const igmc_model* m, const igmc_batch* b, int B) {
   return (m && b) ? plan_query(m, b, B).step_form : 0;
+}
+
+// debug aid (tests): non-zero when a training step on (arena, B) hands conv layer 3's weight gradient from the subgraph kernel to
+// its tail as the centre rows' vectors instead of per-workgroup tables (StepPlan::l3_vec: the member that owns the item centre)
+extern "C" int igmc_debug_l3_vectors(const igmc_model* m, const igmc_batch* b, int B) {
+  return (m && b) ? plan_query(m, b, B).l3_vec : 0;
 }
 
 extern "C" int igmc_model_step_geometry(const igmc_model* m, const igmc_batch* b, int B, int32_t* out, int n) {

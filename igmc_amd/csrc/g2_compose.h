@@ -181,6 +181,7 @@ int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan
     a.h[l] = m.h[l];
     a.off_bias[l] = (int)m.off_bias[l];
   }
+  a.l3_vec = (training && cs > 1 && sp.l3_vec) ? m.l3_vec : nullptr;
   a.ts_part = m.ts_part; a.g2_px = m.g2_px; a.g2_fx = m.g2_fx; a.g2_px_stride = m.g2_px_stride; a.g2_w = m.g2_w;
   a.gs_bar = m.gs_bar; a.gs_err = m.gs_err; a.a1 = m.a1; a.dz = m.dz; a.feat = m.feat; a.gfeat = m.gfeat; a.err = m.err;
   a.lmask = m.lmask; a.ctrl = m.ctrl;

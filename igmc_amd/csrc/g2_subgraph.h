@@ -17,7 +17,9 @@ struct G2Args {
   int R, L, D, ts_stride;
   float* h[4];
   float* ts_part;
-  unsigned char* g2_px;        // plane exchange regions [5 exchanges][graphs][2 sides][G2_PX_BYTES] (g2_prims.h)
+  float* l3_vec;               // StepPlan::l3_vec: layer 3's weight gradient leaves as the centre vectors [graphs][2 sides][G2_NR + 2][32]
+                               // (NULL: as a table in every workgroup's slot of ts_part)
+  unsigned char* g2_px;       // plane exchange regions [5 exchanges][graphs][2 sides][G2_PX_BYTES] (g2_prims.h)
   unsigned long long* g2_fx;
   size_t g2_px_stride;         // bytes per exchange
   const float* g2_w;
@@ -161,6 +163,8 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
   const int tslot = (cs > 1) ? g_first + cm * a.stride : (int)blockIdx.x;
   f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f};        // layer-0 table gradient tile (code half, feature half) of this wave
   bool first_graph = true;
+  // layer 3's weight gradient as centre vectors (StepPlan::l3_vec; the launch code passes a.l3_vec to clustered launches only)
+  const bool l3v = ONCE && TRAIN && a.l3_vec != nullptr;
   G2_STAMP(1);
 
   int g = g_first;
@@ -643,17 +647,28 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
             const int sd = tid / 160, mi = tid - sd * 160, i = mi & 31;
             const float* wr = (const float*)sW2 + mi * 32;      // row i of matrix mi >> 5 (bases 0..3, root)
             const float* dv = D3 + sd * 32;
+            // every operand is read into registers in front of the first product: an asm statement is a scheduling barrier to the
+            // compiler, and with the reads left at their products each of the 32 pairs of LDS reads was a round trip of its own
+            // (ds_read x 2, lgkmcnt(0), v_fmac -- 32 times: the 3.6 k cycles of this phase).  The sums keep their order
+            float wv[32], xv[32];
+#pragma unroll
+            for (int o2 = 0; o2 < 32; ++o2) {
+              const int oa = (o2 + i) & 31;
+              wv[o2] = wr[oa];
+              xv[o2] = dv[oa];
+            }
+            G2_SCHED_BARRIER();
             float s0 = 0.f, s1 = 0.f;
 #pragma unroll
             for (int o2 = 0; o2 < 32; o2 += 2) {
-              const int oa = (o2 + i) & 31, ob = (o2 + 1 + i) & 31;
-              DL_FMAC(s0, wr[oa], dv[oa]);
-              DL_FMAC(s1, wr[ob], dv[ob]);
+              DL_FMAC(s0, wv[o2], xv[o2]);
+              DL_FMAC(s1, wv[o2 + 1], xv[o2 + 1]);
             }
             QV[tid] = s0 + s1;
           }
-          if (hf == 0 && lane < 32) {
-            // (d bias_3: the column sums of dPre_3 over a bundle's rows are its centre row, or zero)
+          if (!l3v && hf == 0 && lane < 32) {
+            // (d bias_3: the column sums of dPre_3 over a bundle's rows are its centre row, or zero; vector mode: the tail
+            //  takes dPre_3 of the centres itself)
             sred[(1 * G2_NB + bw) * 32 + lane] = (active && bi == 0) ? D3[side * 32 + lane] : 0.f;
           }
           G2_STAMP(18);
@@ -750,7 +765,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
         } else if (l > 1 && lane < 16) {
           sred[(((l - 1) & 1) * G2_NB + bw) * 32 + 16 * hf + lane] = 0.f;      // idle bundle: exact zeros
         }
-        if (tid < 32) {
+        if (tid < 32 && !(l == 3 && l3v)) {
           // d bias_l = the bundles' column sums of dPre_l in bundle order: under the table product, behind no barrier of its own
           const float* sb = sred + (l & 1) * G2_NB * 32 + tid;
           const float sv = (sb[0] + sb[32]) + (sb[64] + sb[96]);
@@ -762,7 +777,22 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
         //  just written are ordered by the barrier at the end of the layer)
         G2_STAMP(21 + 5 * (3 - l));
         if (l > 1) wload(l - 1, 1);                  // next image: lands under the table product (LDS + matrix work only)
-        if (l == 3) {
+        if (l == 3 && l3v) {
+          // layer 3's weight gradient of the subgraph is T_r[c] (x) dPre_3[c] (r < R), h_2[c] (x) dPre_3[c] (d root) and dPre_3[c]
+          // (d bias) of the two centres: the member that owns a centre leaves those G2_NR + 2 vectors -- 56 sixteen-byte stores,
+          // against a [R + 1][32][32] table from EVERY member -- and the tails (model.hip: l3_vec_sum) form the products where
+          // they add them.  dPre_3 goes as it stands in LDS: its rounding depends on the contraction of the line that formed it.
+          // (cs > 1: the two centres sit in different members; rows R .. G2_NR - 1 are never read and stored as zeros)
+          if (wg_centre && tid < 2 * 64) {
+            const int sd = tid >> 6, e = tid & 63, row = e >> 3, c4 = (e & 7) * 4;
+            if ((sd ? own_v : own_u) && row < G2_NR + 2) {
+              const float* src = row < G2_NR ? TC + (sd * G2_NR + row) * 32 : row == G2_NR ? sfeat + sd * 128 + 64 : D3 + sd * 32;
+              float4 w = *(const float4*)(src + c4);
+              if (row >= R && row < G2_NR) w = make_float4(0.f, 0.f, 0.f, 0.f);
+              *(float4*)(a.l3_vec + (((size_t)g * 2 + sd) * (G2_NR + 2) + row) * 32 + c4) = w;
+            }
+          }
+        } else if (l == 3) {
           // layer-3 partial table of the workgroup [r][in][out] (+ root block): T_r[c] (x) dPre_3[c] and h_2[c] (x) dPre_3[c] of
           // the centres this workgroup owns, users' then items'; exact zeros elsewhere (the tail sums every slot).  Behind the
           // flag raise: the stores sit under the wait for the other side's dPre_2

@@ -228,6 +228,10 @@ struct StepPlan {
   int exchange_inside;       // the step keeps its gradient sources in exchangeable form (StepExchange)
   int tail_fold;             // subgraph kernel, IGMC_TAIL_TS: a single-GPU step with Adam and weight images runs the tail as ONE launch
                              // (k_tail_fin; its stash role rides in the subgraph kernel's launch) -- IGMC_TAIL_FOLD=0: never
+  int l3_vec;                // subgraph kernel, IGMC_TAIL_TS: a clustered training step (cs > 1: every subgraph its own cluster) hands
+                             // layer 3's weight gradient to the tail as the centre vectors (ModelDev::l3_vec), not as tables: 0, or
+                             // the member that owns the item centre (2 cs / G2_NB >= 1; the user centre's is member 0) --
+                             // IGMC_L3_VEC=0: never
   int needs_csr;             // some kernel of the call reads the collated CSR (a lean arena must emit it first)
   int dense_layers;          // the dense-layer kernels take this arena (igmc_model_dense_layers)
   int step_form;             // igmc_model_step_form

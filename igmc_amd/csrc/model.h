@@ -46,6 +46,9 @@ struct ModelDev {
   float* l0_part;     // [IGMC_L0_BLOCKS][(R*L+L+1)*32]
   float* graw;        // [3][32*160+32] + [3][R*4] + l0 rows: reduced partials
   float* ts_part;     // [4][IGMC_TS_BLOCKS][ts_stride] relation-space tables [W_r rows | root rows | bias] per layer (or NULL)
+  float* l3_vec;      // [Bcap][2 sides][G2_NR + 2][32] layer 3's weight gradient of a subgraph as its centre vectors (StepPlan::l3_vec):
+                      // rows r < R: T_r[centre], row G2_NR: h_2[centre], row G2_NR + 1: dPre_3[centre] -- the slot of the side's
+                      // centre member in ts_part[3] would hold their outer products, every other member's zeros (or NULL)
   float* ts_raw;      // [4][ts_stride] their sum over the workgroups
   int ts_stride;      // (R*32 + 33) * 32
   float* fin_stash;   // [4][IGMC_STASH_LAYER] per conv layer: Gram of the bases [0..15], ARR matrix M [16..31], att moments [32..160), att copy [160..160+R*4);

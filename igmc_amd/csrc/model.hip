@@ -1375,12 +1375,79 @@ __device__ __forceinline__ int ts_slot(const TsSlots& s, int q) {
   return c * s.stride + g;
 }
 
+// Layer 3 where the subgraph kernel left centre vectors instead of tables (StepPlan::l3_vec = mv, the member that owns the
+// item centre; vec = ModelDev::l3_vec): partial group pg's sum of one float4 column of the layer's table -- row j (j < R:
+// dW_j, j == R: d root, j > R: the bias row), input row c, outputs c4 .. c4 + 3 -- over the slots q = pg, pg + 16, .. in order,
+// as the table loops of reduce_ts_body / tf_sum_set form it.  Slot q is (member q / ng, subgraph g = q % ng), and its table is
+//   member 0:   T_j[cu] (x) dPre_3[cu] of the user centre (d root: h_2[cu] (x) dPre_3[cu]; bias row: dPre_3[cu]),
+//   member mv:  the item centre's likewise,
+//   any other:  zeros,
+// so the thread takes the subgraphs g = (pg - member * ng) mod 16, + 16, .. < ng of member 0, then those of member mv:
+// ascending q, the table loop's order without its zero addends.
+// WHY THE BITS ARE THE TABLE MODE'S (cs > 1): there an owner's slot holds round(t * d) + 0.f (the other centre's term of the
+// two-term sum is a literal zero; fused or not, the sum rounds once, to round(t * d), and a product of -0.0 becomes +0.0) and
+// every other member's holds +0.0.  The accumulators start at +0.0 and x + y is -0.0 only where both are, so they never
+// become -0.0: adding +0.0 to one, or -0.0 where the table held +0.0, changes no bit of it, and dropping the addend changes
+// none either.  What is left is acc += round(t * d) in the same order -- __fmul_rn, so that the product is rounded before the
+// add here as well (it must not contract into an fma).  The bias row's slot held dPre_3[c] + zeros: the same argument.
+// All loads of a thread are requested before its first add wherever a member has <= 64 subgraphs (<= 4 a thread and side).
+__device__ __forceinline__ float4 l3_vec_sum(const float* __restrict__ vec, const TsSlots& sl, int mv, int R, int j, int c,
+                                             int c4, int pg) {
+  const int ng = sl.ng;
+  const bool bias = j > R;
+  const int trow = j < R ? j : G2_NR;                     // T_j[centre] or h_2[centre]
+  float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  auto request = [&](int side, int i0, float (&t)[4], float4 (&d)[4]) {
+    const int r0 = (pg - (side ? mv : 0) * ng) & 15;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int g = r0 + 16 * (i0 + u), gc = g < ng ? g : ng - 1;      // (past the end: requested and not added, like ts_slot)
+      const float* v = vec + ((size_t)gc * 2 + side) * ((G2_NR + 2) * 32);
+      t[u] = bias ? 1.f : v[trow * 32 + c];
+      d[u] = *(const float4*)(v + (G2_NR + 1) * 32 + c4);
+    }
+  };
+  auto add = [&](int side, int i0, const float (&t)[4], const float4 (&d)[4]) {
+    // (__fmul_rn alone is x * y to the compiler, which fuses it with the add under the default contraction: measured)
+#ifndef IGMC_HIPEMU
+#pragma clang fp contract(off)
+#endif
+    const int r0 = (pg - (side ? mv : 0) * ng) & 15;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (r0 + 16 * (i0 + u) < ng) {
+        if (bias) {
+          s4.x += d[u].x; s4.y += d[u].y; s4.z += d[u].z; s4.w += d[u].w;
+        } else {
+          s4.x += __fmul_rn(t[u], d[u].x); s4.y += __fmul_rn(t[u], d[u].y);
+          s4.z += __fmul_rn(t[u], d[u].z); s4.w += __fmul_rn(t[u], d[u].w);
+        }
+      }
+  };
+  float tu[4], tv[4];
+  float4 du[4], dv[4];
+  if (ng <= 64) {
+    request(0, 0, tu, du);
+    request(1, 0, tv, dv);
+    add(0, 0, tu, du);
+    add(1, 0, tv, dv);
+  } else {
+    for (int side = 0; side < 2; ++side)
+      for (int i0 = 0; 16 * i0 < ng; i0 += 4) {
+        request(side, i0, tu, du);
+        add(side, i0, tu, du);
+      }
+  }
+  return s4;
+}
+
 // relation-space tables of graphstep.hip: ts_raw[l][i] = sum over the workgroups' partials (fixed order);
 // 64 outputs per block, the 4 waves split the partial slices
 // Pold != NULL: wave 0 also forms, per 32 consecutive outputs (always inside one dW_r block: ts_stride and fin*32 are
 // multiples of 32), the partial dot products <dW_r, basis_b> (b = 0..3) with the CURRENT parameters -- d att[r,b] is
 // the sum of the fin partials of its block (k_finalize_ts), so that kernel never reads a basis element it does not own.
-__device__ __forceinline__ void reduce_ts_body(const ModelDev& m, int nparts, int stride, int B, int blk,
+// l3v != 0 (StepPlan::l3_vec): layer 3's tables were not stored -- its sums come from the centre vectors (l3_vec_sum)
+__device__ __forceinline__ void reduce_ts_body(const ModelDev& m, int nparts, int stride, int B, int blk, int l3v,
                                                const float* __restrict__ Pold = nullptr) {
   // 64 outputs a workgroup as 16 float4 columns x 16 partial groups: thread (column o4 = lane & 15, group pg = 4 wave +
   // (lane >> 4)) sums the partial slots pg, pg + 16, .. of its four outputs (<= 14 sixteen-byte loads, all requested before
@@ -1408,7 +1475,12 @@ __device__ __forceinline__ void reduce_ts_body(const ModelDev& m, int nparts, in
     }
   }
   float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (ok4) {
+  if (ok4 && l == 3 && l3v) {
+    // table element i0 = row * 32 + out, rows [R x 32 of dW_r | 32 of d root | bias]
+    const int row = i0 >> 5, R = m.R;
+    s4 = l3_vec_sum(m.l3_vec, ts_slots(nparts, stride, B), l3v, R, row < R * 32 ? row >> 5 : row < R * 32 + 32 ? R : R + 1,
+                    row & 31, i0 & 31, pg);
+  } else if (ok4) {
     const float* p = m.ts_part + (size_t)l * IGMC_TS_BLOCKS * ts + i0;
     const TsSlots sl = ts_slots(nparts, stride, B);
     const int nq = sl.nq;
@@ -1457,7 +1529,7 @@ __device__ __forceinline__ void reduce_ts_body(const ModelDev& m, int nparts, in
 __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_ts(BatchDev b, ModelDev m, const float* __restrict__ P,
                                                           float grad_scale, float mult, float drop_scale,
                                                           float* __restrict__ grad, int nlin, int nparts, int stride,
-                                                          int B, int nstash, const int64_t* ctrl, int bump_seq) {
+                                                          int B, int nstash, const int64_t* ctrl, int bump_seq, int l3v) {
   __builtin_amdgcn_s_setprio(3);      // (step chain: ahead of the extraction chain's waves wherever the two share a SIMD)
   igmc_kernarg_warm<sizeof(BatchDev) + sizeof(ModelDev) + 64>();
   const int nred = (int)gridDim.x - nlin - nstash;
@@ -1465,7 +1537,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_ts(BatchDev b, ModelDev m, 
   if ((int)blockIdx.x < nlin)
     head_bwd_w_body(b, m, P, nullptr, 1, grad_scale, mult, drop_scale, grad, blockIdx.x & 7, blockIdx.x >> 3, B);
   else if ((int)blockIdx.x < nlin + nred)
-    reduce_ts_body(m, nparts, stride, B, blockIdx.x - nlin, nstash ? P : nullptr);
+    reduce_ts_body(m, nparts, stride, B, blockIdx.x - nlin, l3v, nstash ? P : nullptr);
   else
     fin_stash_body(m, P, blockIdx.x - nlin - nred, ctrl);
 }
@@ -2190,9 +2262,10 @@ extern "C" int igmc_debug_fin_clocks(unsigned long long* out) {
 // j == R + 1: the bias row); thread (o4, pg) sums the slots pg, pg + 16, .. of column k0 + o4 in order (14 sixteen-byte loads
 // in flight, all requested before the first add), wave 0 adds the 16 groups in index order through LDS (sred4: 1024 floats).
 // Returns, in wave 0, component (lane & 3) of column k0 + (lane >> 2): element lane of the set's 64 floats.  One barrier;
-// sred4 must not be in use by the workgroup.
+// sred4 must not be in use by the workgroup.  vec != NULL (layer 3 under StepPlan::l3_vec = mv): the same sums from the centre
+// vectors (l3_vec_sum) -- same threads, same slots in the same order, same groups; only the addend is formed here.
 __device__ __forceinline__ float tf_sum_set(const float* __restrict__ pl, const TsSlots& sl, int ts, int R, int fin, int c,
-                                            int k0, int k1, float4* sred4) {
+                                            int k0, int k1, float4* sred4, const float* __restrict__ vec = nullptr, int mv = 0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int o4 = lane & 15, pg = wave * 4 + (lane >> 4);
   const int k = k0 + o4, kc = k < k1 ? k : k1 - 1, j = kc >> 3;
@@ -2200,7 +2273,8 @@ __device__ __forceinline__ float tf_sum_set(const float* __restrict__ pl, const 
   const int i0 = row * 32 + 4 * (kc & 7);
   float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
   const int nq = sl.nq;
-  for (int q0 = pg; q0 < nq; q0 += 16 * 14) {
+  if (vec) s4 = l3_vec_sum(vec, sl, mv, R, j, c, 4 * (kc & 7), pg);
+  else for (int q0 = pg; q0 < nq; q0 += 16 * 14) {
     float4 v[14];
 #pragma unroll
     for (int u = 0; u < 14; ++u) v[u] = *(const float4*)(pl + (size_t)ts_slot(sl, q0 + 16 * u) * ts + i0);
@@ -2244,7 +2318,7 @@ __device__ __forceinline__ void tf_datt_pub(float tot, int r, int R, const float
 
 __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m, const float* P, float grad_scale, float mult,
                                                            float drop_scale, float* grad, float arr_coef, AdamTail at, int nlin,
-                                                           int nparts, int stride, int B, int bump_seq, int mute) {
+                                                           int nparts, int stride, int B, int bump_seq, int mute, int l3v) {
   __builtin_amdgcn_s_setprio(3);      // (step chain: ahead of the extraction chain's waves wherever the two share a SIMD)
   igmc_kernarg_warm<sizeof(BatchDev) + sizeof(ModelDev) + sizeof(AdamTail) + 64>();
   IGMC_DYN_SMEM(smem);
@@ -2287,7 +2361,8 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m,
     TF_STAMP(blk == nprod_r + 1, 49);
     const TsSlots sl = ts_slots(nparts, stride, B);
     const int k0 = brow ? ncol_a : 16 * set, k1 = brow ? ncol_a + 8 : (k0 + 16 < ncol_a ? k0 + 16 : ncol_a);
-    const float tot = tf_sum_set(m.ts_part + (size_t)l * IGMC_TS_BLOCKS * ts, sl, ts, R, fin, c, k0, k1, (float4*)S);
+    const float tot = tf_sum_set(m.ts_part + (size_t)l * IGMC_TS_BLOCKS * ts, sl, ts, R, fin, c, k0, k1, (float4*)S,
+                                 (l == 3 && l3v) ? m.l3_vec : nullptr, l3v);
     TF_STAMP(blk == 0, 42);
     TF_STAMP(blk == nprod_r + 1, 50);
     if (wave == 0) {
@@ -2362,7 +2437,8 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m,
       const int i = tid + u * IGMC_BLOCK;
       if (i < IGMC_STASH_LAYER) s_st[i] = stq[u];
     }
-    const float tot = tf_sum_set(m.ts_part + (size_t)l * IGMC_TS_BLOCKS * ts, sl, ts, R, fin, c, 0, ncol_a < 16 ? ncol_a : 16, sred4);
+    const float tot = tf_sum_set(m.ts_part + (size_t)l * IGMC_TS_BLOCKS * ts, sl, ts, R, fin, c, 0, ncol_a < 16 ? ncol_a : 16, sred4,
+                                 (l == 3 && l3v) ? m.l3_vec : nullptr, l3v);
     if (wave == 0 && (lane >> 2) < ncol_a) rows[lane] = tot;
     TF_STAMP(mb == 0, 2);      // the set is reduced (the partial tables' round trip)
     // ---- this row's share of d att for the relations of set 0
@@ -2704,14 +2780,15 @@ static void launch_reduce(const ModelDev& m, const BatchDev& b, const StepPlan& 
 
 // Sum of the workgroups' relation-space tables (+ nlin workgroups that form d lin1 / d lin2, + the stash of k_finalize_ts)
 static void launch_tail_ts(const ModelDev& m, const BatchDev& b, const float* P, int B, float grad_scale, float mult, float* grad,
-                           int nlin, int nparts, int stride, int nstash, const int64_t* ctrl, int bump_seq, void* stream) {
+                           int nlin, int nparts, int stride, int nstash, const int64_t* ctrl, int bump_seq, int l3v, void* stream) {
   IGMC_PLAUNCH("k_tail_ts", k_tail_ts, nlin + (4 * m.ts_stride + 63) / 64 + nstash, IGMC_BLOCK, 0, stream, b, m, P, grad_scale,
-               mult, 2.f, grad, nlin, nparts, stride, B, nstash, ctrl, bump_seq);
+               mult, 2.f, grad, nlin, nparts, stride, B, nstash, ctrl, bump_seq, l3v);
 }
 
 // ... and the whole tail behind the subgraph kernel as ONE launch (sp.tail_fold; the stash role ran in the launch in front)
 static void launch_tail_fin(const ModelDev& m, const BatchDev& b, const float* P, int B, float grad_scale, float mult, float* grad,
-                            float arr_coef, const AdamTail& at, int nlin, int nparts, int stride, int bump_seq, void* stream) {
+                            float arr_coef, const AdamTail& at, int nlin, int nparts, int stride, int bump_seq, int l3v,
+                            void* stream) {
   int mute = -1;
 #ifdef IGMC_HIPEMU
   // (emulator only -- the timeout test: the publishers of this layer stay silent and its pollers give up; with
@@ -2729,7 +2806,7 @@ static void launch_tail_fin(const ModelDev& m, const BatchDev& b, const float* P
 #endif
   const int nconv = 96 + m.L, nsets = (8 * (m.R + 1) + 15) / 16, nprod = ((nsets - 1) * nconv + 4 + 31) & ~31;
   IGMC_PLAUNCH("k_tail_fin", k_tail_fin, nprod + nconv + nlin + 1, IGMC_BLOCK, (size_t)IGMC_TF_WORDS * sizeof(float), stream, b, m, P,
-               grad_scale, mult, 2.f, grad, arr_coef, at, nlin, nparts, stride, B, bump_seq, mute);
+               grad_scale, mult, 2.f, grad, arr_coef, at, nlin, nparts, stride, B, bump_seq, mute, l3v);
 }
 
 // The reduced gradient sources of a data-parallel step, summed over the ranks: tables + d att partials (one allocation), or the
@@ -2823,7 +2900,7 @@ void igmc_launch_conv_backward(const ModelDev& m, const BatchDev& b, const StepP
   if (sp.dlb) {
     const int gstride = (B + 7) & ~7;
     igmc_launch_dl_bwd(m, b, sp, B, use_flags, stream, nullptr, 1);
-    launch_tail_ts(m, b, P, B, 0.f, 1.f, grad, 0, (sp.nqu + sp.nqv) * gstride, gstride, 4, nullptr, 1, stream);
+    launch_tail_ts(m, b, P, B, 0.f, 1.f, grad, 0, (sp.nqu + sp.nqv) * gstride, gstride, 4, nullptr, 1, 0, stream);
   } else {
     const int l0_mfma = m.R * m.L + m.L + 1 <= 32;       // layer-0 table gradient rides in the MFMA weight-gradient kernel
     launch_layers_bwd(m, b, sp, P, B, use_flags, 0, stream);
@@ -2884,12 +2961,12 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const BatchDev& b, const StepPla
     const int bump_seq = igmc_launch_graph_step2(m, b, sp, Pc, B, 1, use_flags, inj_mask, seed, step, mult, grad_scale, out, stream,
                                                  fold ? 4 : 0, ctrl);
     if (fold) {
-      launch_tail_fin(m, b, Pc, B, grad_scale, mult, grad, ARR * arr_scale, at, 8 * ny, sp.grid, stride, bump_seq, stream);
+      launch_tail_fin(m, b, Pc, B, grad_scale, mult, grad, ARR * arr_scale, at, 8 * ny, sp.grid, stride, bump_seq, sp.l3_vec, stream);
       if (img_emitted) *img_emitted = 1;
       return 0;
     }
     launch_tail_ts(m, b, Pc, B, grad_scale, mult, grad, 8 * ny, sp.grid, (sp.cs > 1) ? ((B + 7) & ~7) : IGMC_TS_BLOCKS,
-                   tables ? 4 : 0, ctrl, bump_seq, stream);
+                   tables ? 4 : 0, ctrl, bump_seq, sp.l3_vec, stream);
   } else {
     launch_conv_fwd(m, b, sp, Pc, B, 1, use_flags, stream);
     if (sp.dlts) {
@@ -2901,7 +2978,7 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const BatchDev& b, const StepPla
       if (sp.dlb) igmc_launch_dl_bwd(m, b, sp, B, use_flags, stream, inside ? &hd : nullptr);
       else launch_layers_bwd(m, b, sp, Pc, B, use_flags, 1, stream);
       const int gstride = (B + 7) & ~7;
-      launch_tail_ts(m, b, Pc, B, grad_scale, mult, grad, 8 * ny, (sp.nqu + sp.nqv) * gstride, gstride, 4, ctrl, sp.dlf ? 1 : 0, stream);
+      launch_tail_ts(m, b, Pc, B, grad_scale, mult, grad, 8 * ny, (sp.nqu + sp.nqv) * gstride, gstride, 4, ctrl, sp.dlf ? 1 : 0, 0, stream);
     } else {
       const int gy = igmc_rows_grid(m.node_cap, 128, 512), hb = (B + 15) / 16, nsl = rows0 <= 32 ? 4 : 3;
       IGMC_PLAUNCH("k_head_train", k_head_train, dim3(hb > gy ? hb : gy, 4), 512, (size_t)32 * (128 + 4) * sizeof(float), stream,

@@ -18,6 +18,7 @@ struct StepHooks {
   int dl_head;         // IGMC_DL_HEAD=0: the loss head as a launch of its own in front of k_dl_bwd
   int fin_mode;        // IGMC_FIN_MODE=0: the hand-off version of the gradient / Adam tail (k_finalize)
   int tail_fold;       // IGMC_TAIL_FOLD=0: the two-launch tail behind the subgraph kernel (k_tail_ts -> k_finalize_ts)
+  int l3_vec;          // IGMC_L3_VEC=0: layer 3's weight gradient leaves the subgraph kernel as tables in every launch form
 };
 static int step_hook(const char* name, int unset) {
   const char* e = getenv(name);
@@ -35,6 +36,7 @@ static StepHooks step_hooks() {
   hk.dl_head = step_hook("IGMC_DL_HEAD", 1);
   hk.fin_mode = step_hook("IGMC_FIN_MODE", 1);
   hk.tail_fold = step_hook("IGMC_TAIL_FOLD", 1);
+  hk.l3_vec = step_hook("IGMC_L3_VEC", 1);
   return hk;
 }
 int igmc_dl_always() { return step_hook("IGMC_DL_ALWAYS", 0) == 1; }
@@ -172,6 +174,12 @@ void igmc_step_plan(const ModelDev& m, const BatchDev& b, int B, int kind, StepP
     // (the four stash workgroups appended to the subgraph kernel's launch take a CU each -- the launch's dynamic LDS -- and are
     //  resident with the rest: a clustered grid is <= 224 on >= 240 CUs (gs_cluster), any other <= IGMC_WG_BLOCKS)
     p->tail_fold = fused && fts && hk.tail_fold != 0 && m.fold_w && m.L <= 32 && 4 * m.R <= IGMC_FOLD_NA;
+    // layer 3's weight gradient as centre vectors: dPre_3 lives on the two centre rows, so a cluster's layer-3 tables are one
+    // outer product a side -- the member that owns the centre leaves its factors, nobody stores a table, and both tails
+    // (k_tail_ts, k_tail_fin) form the products where they add them.  Only where a slot holds ONE such product: a training step
+    // whose subgraphs have a cluster each (cs > 1: the straight-line form, two different centre members).  The looping grid
+    // accumulates several subgraphs in a slot, and at cs == 1 the slot is the sum of both sides' products: tables
+    p->l3_vec = (fused && fts && p->cs > 1 && hk.l3_vec != 0 && m.l3_vec) ? 2 * p->cs / G2_NB : 0;
     p->step_form = 1;
     return;
   }

@@ -362,6 +362,13 @@ class ModelWorkspace(object):
         group-split form, 0 per-layer kernels (igmc_model_step_form)."""
         return int(self.lib.igmc_model_step_form(self.handle, batch.handle, int(B)))
 
+    def l3_vectors(self, batch, B):
+        """Non-zero when a training step on (batch arena, B) hands layer 3's weight gradient to the tail as centre vectors
+        (igmc_debug_l3_vectors): the cluster member that owns the item centre; 0: per-workgroup tables."""
+        fn = self.lib.cdll.igmc_debug_l3_vectors
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int]
+        return int(fn(self.handle, batch.handle, int(B)))
+
     GEOMETRY_KEYS = ('form', 'family', 'wg_per_graph', 'grid', 'nqu', 'nqv', 'groups', 'gsplit', 'tables', 'kp', 'dl_bwd')
     FAMILIES = ('rows', 'subgraph', 'dense_fused', 'dense_layer')
 

@@ -30,7 +30,8 @@ NAMES = {1: 'T0 table staged', 2: 'labels + zero fills', 3: 'relm staged + one-h
 #  forms dPre_l: no phase is left there, and none is printed.  Layer 3 runs on the centre bundles only in the forward and in
 #  closed form in the backward: stamp 19 sits in front of 18 there -- the h_2 rows are requested, then the q vectors formed --,
 #  and a library from before that change shows its own phases under these lines: 18 = dPre3 centre rows + d bias3, 20 = B3 wave
-#  compute (gather, tiles, transform) + d bias2, 22 = B3 table product)
+#  compute (gather, tiles, transform) + d bias2, 22 = B3 table product.  Stamp 22 keeps its label where layer 3 leaves centre
+#  vectors instead of tables (StepPlan::l3_vec): the phase is then the next image's request + 56 stores in a centre member)
 ORDER = [k for k in range(1, 36) if k not in (19, 24, 29)]
 
 

@@ -557,6 +557,11 @@ static inline uint32_t __float_as_uint(float f) {
   memcpy(&u, &f, 4);
   return u;
 }
+// product rounded to f32 before anything is done with it (never one half of a fused multiply-add)
+static inline float __fmul_rn(float a, float b) {
+  volatile float p = a * b;
+  return p;
+}
 static inline float __uint_as_float(uint32_t u) {
   float f;
   memcpy(&f, &u, 4);
