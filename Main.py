@@ -66,7 +66,9 @@ def build_parser():
     p.add_argument('--hop', default=1, metavar='S')
     p.add_argument('--sample-ratio', type=float, default=1.0)
     p.add_argument('--max-nodes-per-hop', default=10000)
-    p.add_argument('--use-features', action='store_true', default=False)
+    p.add_argument('--use-features', action='store_true', default=False,
+                   help='side features of the two target nodes in the MLP head (reference Main.py:94); --recommend, '
+                        '--rank-eval and --explain gather them on the device by node id')
     # edge dropout settings
     p.add_argument('--adj-dropout', type=float, default=0.2)
     p.add_argument('--force-undirected', action='store_true', default=False)
@@ -104,7 +106,9 @@ def build_parser():
     p.add_argument('--new-ratings', default=None, metavar='FILE',
                    help='rating changes applied to the training graph ON THE DEVICE before --recommend / --rank-eval: lines '
                         '"user item rating" (ids as recommendations_*.tsv prints them, "#" comments; rating 0 removes the '
-                        'entry, ids beyond the graph create new users / items)')
+                        'entry, ids beyond the graph create new users / items).  Takes no --use-features: the command line '
+                        'cannot name a new node\'s feature rows (recommend.GraphView(dataset, graph, u_features, v_features) '
+                        'can)')
     p.add_argument('--explain', type=int, default=0, metavar='M',
                    help='write the M neighbours that move each prediction most (leave-one-out attribution on the device) and '
                         'stop; explains the links of --explain-links, or with --recommend N every recommended (user, item); '
@@ -294,8 +298,6 @@ def main(argv=None):
         parser.error('--explain needs the links to explain: --explain-links FILE, or --recommend N for the recommended pairs')
     if args.explain_links and not args.explain > 0:
         parser.error('--explain-links names the links of --explain M: give M')
-    if args.explain > 0 and args.use_features:
-        parser.error('--explain takes no --use-features: leave-one-out variants carry no side features')
     rank, world = parallel.init_from_env()
     torch.manual_seed(args.seed)
     if torch.cuda.is_available():

@@ -47,6 +47,7 @@ SIGNATURES = {
     'igmc_batch_device_ptr': (vp, [vp, i32]),
     'igmc_batch_set_side_features': (i32, [vp, vp, i32]),
     'igmc_batch_bind_side_source': (i32, [vp, vp, i32]),
+    'igmc_batch_bind_side_tables': (i32, [vp, vp, i32, i32, vp, i32, i32]),
     'igmc_batch_set_lean': (i32, [vp, i32]),
     'igmc_batch_assume_size': (i32, [vp, i32]),
     'igmc_batch_want_transposed': (i32, [vp]),
@@ -114,7 +115,7 @@ SIGNATURES = {
 }
 
 BUF = dict(NODE_OFF=0, N_USERS=1, NODE_LABEL=2, NODE_GID=3, NODE_GRAPH=4, ROW_PTR=5, ECR=6, ECODE=7,
-           EFLAG=8, Y=9, TOTALS=10)
+           EFLAG=8, Y=9, TOTALS=10, SIDE=11)
 CTRL = dict(STEP=0, FIRST=1, EPOCH=2, ADAM_T=3, BATCH=4, DONE=5, FIRST_ODD=6, K=7, LR=8, BETA1=9, BETA2=10, EPS=11, WD=12, STEP_SIZE=13,
             INV_SQRT_BC2=14, GROUP=15, GK=16, GQ=17, SYNC_ERR=18, GATE_TIMEOUTS=19, WORDS=24)
 ALLREDUCE_FN = C.CFUNCTYPE(i32, vp, vp, i64, vp)      # igmc_allreduce_fn (igmc_comm_create_host)

@@ -96,6 +96,8 @@ struct igmc_batch {
   const float* side;
   int n_side;
   const float* side_src;    // dataset-wide [n_links, n_side] matrix (igmc_batch_bind_side_source); rows gathered per batch
+  const float *side_u, *side_v;      // per-node tables [side_nu, side_fu] / [side_nv, side_fv] (igmc_batch_bind_side_tables);
+  int side_nu, side_fu, side_nv, side_fv;      // rows of the batch's target nodes gathered per batch; both NULL: none bound
   float* side_buf;          // [graph_cap, n_side] owned by the arena
   int side_buf_cols;
   int lean;                 // igmc_batch_set_lean: extraction stops after the dense blocks (capped arenas)
@@ -487,6 +489,8 @@ extern "C" int igmc_batch_create(const igmc_graph* g, int max_graphs, int hop, i
   b->side = nullptr;
   b->n_side = 0;
   b->side_src = nullptr;
+  b->side_u = b->side_v = nullptr;
+  b->side_nu = b->side_fu = b->side_nv = b->side_fv = 0;
   b->side_buf = nullptr;
   b->side_buf_cols = 0;
   b->lean = 0;
@@ -559,6 +563,16 @@ extern "C" int igmc_batch_want_transposed(igmc_batch* b) {
   return 0;
 }
 
+// Side features of the target nodes travel with the extraction (reference :250-253), behind its launches on the same stream:
+// by link position from a bound source, by node id -- the targets the extraction has just left in the arena's slots -- from
+// bound tables.
+static void gather_side(const igmc_batch* b, const int32_t* d_link_idx, int first, int B, void* stream) {
+  if (b->side_src) igmc_launch_side_gather(b->side_src, b->n_side, d_link_idx, first, B, b->ctrl, b->side_buf, stream);
+  if (b->side_u || b->side_v)
+    igmc_launch_side_gather_nodes(b->d, b->side_u, b->side_nu, b->side_fu, b->side_v, b->side_nv, b->side_fv, B, b->side_buf,
+                                  stream);
+}
+
 extern "C" int igmc_extract_batch(const igmc_graph* g, igmc_batch* b, const int32_t* d_link_u,
                                   const int32_t* d_link_v, const float* d_link_y, const int32_t* d_link_idx,
                                   int first, int B, double sample_ratio, uint64_t seed, uint64_t epoch,
@@ -568,8 +582,7 @@ extern "C" int igmc_extract_batch(const igmc_graph* g, igmc_batch* b, const int3
   if (!d_link_u || !d_link_v || !d_link_y) IGMC_FAIL("null link arrays");
   igmc_launch_extract(g->d, b->d, d_link_u, d_link_v, d_link_y, d_link_idx, first, B, 0, sample_ratio, seed, epoch,
                       b->ctrl, b->lean && b->d.relm, stream);
-  if (b->side_src)      // side features of the target nodes travel with the extraction (reference :250-253)
-    igmc_launch_side_gather(b->side_src, b->n_side, d_link_idx, first, B, b->ctrl, b->side_buf, stream);
+  gather_side(b, d_link_idx, first, B, stream);
   HIPCHECK(hipGetLastError());
   b->last_B = B;
   return 0;
@@ -626,7 +639,7 @@ extern "C" int igmc_extract_batch_cached(const igmc_graph* g, igmc_batch* b, con
   igmc_launch_load_nodes(b->d, d_uoff, d_unodes, d_udist, d_voff, d_vnodes, d_vdist, d_link_y, d_link_idx, first, B, b->ctrl,
                          stream);
   igmc_launch_extract(g->d, b->d, nullptr, nullptr, nullptr, nullptr, 0, B, 1, 1.0, 0, 0, nullptr, b->lean && b->d.relm, stream);
-  if (b->side_src) igmc_launch_side_gather(b->side_src, b->n_side, d_link_idx, first, B, b->ctrl, b->side_buf, stream);
+  gather_side(b, d_link_idx, first, B, stream);
   HIPCHECK(hipGetLastError());
   b->last_B = B;
   return 0;
@@ -682,7 +695,7 @@ extern "C" int igmc_extract_group(const igmc_graph* g, igmc_batch_set* s, int co
   if (B <= 0 || B > b0->d.graph_cap) IGMC_FAIL("B exceeds the batch capacity");
   for (int i = 0; i < count; ++i) {
     const igmc_batch* b = s->arenas[i];
-    if (!b->lean || !b->ctrl || b->ctrl != b0->ctrl || b->side_src)
+    if (!b->lean || !b->ctrl || b->ctrl != b0->ctrl || b->side_src || b->side_u || b->side_v)
       IGMC_FAIL("group extraction needs lean arenas with one control block attached and no side-feature source");
   }
   igmc_launch_extract_set(g->d, s->d_views, b0->d, count, d_link_u, d_link_v, d_link_y, d_link_idx, sel0, B, sample_ratio,
@@ -813,26 +826,21 @@ extern "C" void* igmc_batch_device_ptr(const igmc_batch* b, int which) {
     case IGMC_BUF_EFLAG: return d.eflag;
     case IGMC_BUF_Y: return d.y;
     case IGMC_BUF_TOTALS: return d.totals;
+    case IGMC_BUF_SIDE: return (void*)b->side;
   }
   return nullptr;
 }
 
-extern "C" int igmc_batch_set_side_features(igmc_batch* b, const float* d_feat, int n_side) {
-  if (!b) IGMC_FAIL("null batch");
-  b->side = d_feat;
-  b->n_side = n_side;
+static void side_unbind(igmc_batch* b) {
   b->side_src = nullptr;
-  return 0;
+  b->side_u = b->side_v = nullptr;
+  b->side_nu = b->side_fu = b->side_nv = b->side_fv = 0;
+  b->side = nullptr;
+  b->n_side = 0;
 }
 
-extern "C" int igmc_batch_bind_side_source(igmc_batch* b, const float* d_side_all, int n_side) {
-  if (!b) IGMC_FAIL("null batch");
-  if (!d_side_all || n_side <= 0) {      // unbind
-    b->side_src = nullptr;
-    b->side = nullptr;
-    b->n_side = 0;
-    return 0;
-  }
+// the arena-owned buffer the gathered rows of a batch go to, at least n_side columns wide
+static int side_buf_reserve(igmc_batch* b, int n_side) {
   if (b->side_buf_cols < n_side) {
     // (a wider re-bind carves a new buffer out of the arena's slabs; the old one stays part of them and is released with
     //  the arena -- slabs have no per-buffer free -- so grow geometrically to bound what repeated re-binds can take)
@@ -841,9 +849,49 @@ extern "C" int igmc_batch_bind_side_source(igmc_batch* b, const float* d_side_al
     if (b->mem.get(&b->side_buf, (size_t)b->d.graph_cap * cols)) IGMC_FAIL("hipMalloc failed (side features)");
     b->side_buf_cols = cols;
   }
+  return 0;
+}
+
+extern "C" int igmc_batch_set_side_features(igmc_batch* b, const float* d_feat, int n_side) {
+  if (!b) IGMC_FAIL("null batch");
+  side_unbind(b);
+  b->side = d_feat;
+  b->n_side = n_side;
+  return 0;
+}
+
+extern "C" int igmc_batch_bind_side_source(igmc_batch* b, const float* d_side_all, int n_side) {
+  if (!b) IGMC_FAIL("null batch");
+  if (!d_side_all || n_side <= 0) {      // unbind
+    side_unbind(b);
+    return 0;
+  }
+  if (side_buf_reserve(b, n_side)) return 1;
+  side_unbind(b);
   b->side_src = d_side_all;
   b->side = b->side_buf;
   b->n_side = n_side;
+  return 0;
+}
+
+extern "C" int igmc_batch_bind_side_tables(igmc_batch* b, const float* d_u_feat, int n_u_rows, int fu, const float* d_v_feat,
+                                           int n_v_rows, int fv) {
+  if (!b) IGMC_FAIL("null batch");
+  if (!d_u_feat && !d_v_feat && fu == 0 && fv == 0) {      // unbind
+    side_unbind(b);
+    return 0;
+  }
+  if (fu < 0 || fv < 0 || (int64_t)fu + fv < 1 || n_u_rows < 0 || n_v_rows < 0) IGMC_FAIL("bad side-feature table sizes");
+  if (((int64_t)fu + fv) * b->d.graph_cap >= ((int64_t)1 << 31)) IGMC_FAIL("side-feature rows of a full batch exceed 2^31 floats");
+  if ((fu > 0 && !d_u_feat) || (fv > 0 && !d_v_feat)) IGMC_FAIL("a null side-feature table with a non-zero width");
+  if (side_buf_reserve(b, fu + fv)) return 1;
+  side_unbind(b);
+  b->side_u = fu > 0 ? d_u_feat : nullptr;
+  b->side_nu = n_u_rows; b->side_fu = fu;
+  b->side_v = fv > 0 ? d_v_feat : nullptr;
+  b->side_nv = n_v_rows; b->side_fv = fv;
+  b->side = b->side_buf;
+  b->n_side = fu + fv;
   return 0;
 }
 

@@ -1040,6 +1040,34 @@ void igmc_launch_side_gather(const float* src, int S, const int32_t* link_idx, i
   IGMC_PLAUNCH("k_side_gather", k_side_gather, grid, IGMC_BLOCK, 0, stream, src, S, link_idx, first, B, ctrl, dst);
 }
 
+// The same rows keyed by NODE instead of by link position, for sources whose links are not a dataset's own (candidate lists,
+// leave-one-out variants, views over a changed graph): uf [n_u, fu] and vf [n_v, fv] hold one row per user / item, and the two
+// target ids are read from the arena's own slots -- t_list[g * slot] and t_list[g * slot + cap_u], final once k_extract_nodes
+// (free-running) or k_load_nodes (cached node sets) has run and rewritten by no later stage.  So the launch needs no link
+// arrays, no permutation and no control-block cursor, and is the same under a hipGraph replay.  A target the tables have no
+// row for (a node the graph gained after they were built) reads zeros; rows at or beyond B are not written.
+__global__ __launch_bounds__(IGMC_BLOCK) void k_side_gather_nodes(const int32_t* __restrict__ t_list, int slot, int cap_u,
+                                                                   const float* __restrict__ uf, int n_u, int fu,
+                                                                   const float* __restrict__ vf, int n_v, int fv, int B,
+                                                                   float* __restrict__ dst) {
+  const int S = fu + fv;
+  for (int i = blockIdx.x * IGMC_BLOCK + threadIdx.x; i < B * S; i += gridDim.x * IGMC_BLOCK) {
+    const int g = i / S, f = i - g * S;
+    const bool is_u = f < fu;
+    const int id = t_list[(size_t)g * slot + (is_u ? 0 : cap_u)];
+    const bool have = id >= 0 && id < (is_u ? n_u : n_v);
+    dst[i] = !have ? 0.f : is_u ? uf[(size_t)id * fu + f] : vf[(size_t)id * fv + (f - fu)];
+  }
+}
+
+void igmc_launch_side_gather_nodes(const BatchDev& b, const float* uf, int n_u, int fu, const float* vf, int n_v, int fv,
+                                   int B, float* dst, void* stream) {
+  int grid = (B * (fu + fv) + IGMC_BLOCK - 1) / IGMC_BLOCK;
+  grid = grid < 1 ? 1 : (grid > 256 ? 256 : grid);
+  IGMC_PLAUNCH("k_side_gather_nodes", k_side_gather_nodes, grid, IGMC_BLOCK, 0, stream, b.t_list, b.slot, b.cap_u, uf, n_u, fu,
+               vf, n_v, fv, B, dst);
+}
+
 __global__ __launch_bounds__(IGMC_BLOCK) void k_fill_u8(uint8_t* p, int64_t n, uint8_t v) {
   for (int64_t i = (int64_t)blockIdx.x * IGMC_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * IGMC_BLOCK) p[i] = v;
 }

@@ -194,6 +194,8 @@ struct G2Layout {      // LDS plan of graphstep2.hip, offsets in 4-byte words
 };
 void igmc_launch_side_gather(const float* src, int S, const int32_t* link_idx, int first, int B, const int64_t* ctrl,
                              float* dst, void* stream);
+void igmc_launch_side_gather_nodes(const BatchDev& b, const float* uf, int n_u, int fu, const float* vf, int n_v, int fv,
+                                   int B, float* dst, void* stream);
 int igmc_gs_prepare();
 int igmc_g2_prepare();
 

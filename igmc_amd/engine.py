@@ -211,6 +211,13 @@ class Batch(object):
         device (``igmc_batch_bind_side_source``)."""
         self.lib.call('igmc_batch_bind_side_source', self.handle, _p(ptr), int(n_side))
 
+    def bind_side_tables(self, u_ptr, n_u_rows, fu, v_ptr, n_v_rows, fv):
+        """Per-node side-feature tables ``[n_u_rows, fu]`` / ``[n_v_rows, fv]``: every later ``extract`` / ``extract_cached``
+        gathers the rows of the batch's target nodes on the device, by the ids the extraction left in the arena; ids beyond a
+        table read zeros (``igmc_batch_bind_side_tables``).  All zero / None unbinds."""
+        self.lib.call('igmc_batch_bind_side_tables', self.handle, _p(u_ptr), int(n_u_rows), int(fu), _p(v_ptr), int(n_v_rows),
+                      int(fv))
+
     def dense_layers(self, ws):
         """True when the dense per-layer kernels take the conv layers of this arena with workspace ``ws``."""
         return bool(self.lib.cdll.igmc_model_dense_layers(ws.handle, self.handle, int(self.B or self.max_graphs)))

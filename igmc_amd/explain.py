@@ -61,7 +61,8 @@ class LeaveOneOutLinks(LinkSource):
     The six cache tensors and the per-variant arrays have FIXED ADDRESSES AND CAPACITIES and are refilled in place by every
     pass, so the hipGraph a scoring pass captured is replayed by the later ones.  ``len()`` is the number of variants the
     last pass wrote, ``capacity`` (= ``capacity_variants``) the number they have room for.  ``dataset_or_view``: a dataset or a
-    ``recommend.GraphView``; side features are refused."""
+    ``recommend.GraphView``; with side features, every variant gathers the rows of its two targets -- its base link's -- from
+    the source's per-node tables."""
     dynamic = False
 
     def __init__(self, dataset_or_view, capacity_variants=DEFAULT_VARIANTS, capacity_entries=DEFAULT_ENTRIES):

@@ -60,11 +60,34 @@ class DeviceBatch(object):
     batch = property(lambda self: self._materialise()['batch'])
 
 
+class _DevRows(object):
+    """``[rows, cols]`` float32 values at a device address, for ``torch.as_tensor`` (no copy)."""
+
+    def __init__(self, ptr, rows, cols):
+        self.__cuda_array_interface__ = dict(shape=(int(rows), int(cols)), typestr='<f4', data=(int(ptr), False), version=2)
+
+
 def refuse_side_features(source):
+    """A source that names side features but cannot hand out per-node tables (``node_side()``) is refused: links that are not
+    its own would silently be scored without their feature rows."""
     if getattr(source, '_side', None) is not None or getattr(source, 'u_features', None) is not None or \
             getattr(source, 'v_features', None) is not None:
-        raise NotImplementedError('candidate links carry no side features: recommend over a dataset built without '
-                                  '--use-features (u_features / v_features)')
+        raise NotImplementedError('this source names side features (--use-features: u_features / v_features) but has no '
+                                  'node_side() tables to gather them from by node id: serve from a dataset of '
+                                  'util_functions, or from a view of one')
+
+
+def dense_side_table(features, what, rows=None, cols=None):
+    """``features`` (scipy sparse or array, one row per node) as a dense contiguous float32 host array; ``rows`` / ``cols``:
+    the least row count / the exact column count it must have (``ValueError``)."""
+    f = features.toarray() if hasattr(features, 'toarray') else np.asarray(features)
+    if f.ndim != 2:
+        raise ValueError('%s: one feature row per node' % what)
+    if rows is not None and f.shape[0] < rows:
+        raise ValueError('%s: %d rows, at least %d expected' % (what, f.shape[0], rows))
+    if cols is not None and f.shape[1] != cols:
+        raise ValueError('%s: %d columns, %d expected' % (what, f.shape[1], cols))
+    return np.ascontiguousarray(f, dtype=np.float32)
 
 
 class LinkSource(object):
@@ -77,8 +100,10 @@ class LinkSource(object):
     STORAGE, device tensors a subclass allocates ONCE (captured launches hold their addresses): ``link_y`` float32, one label
     per position, always; ``link_u`` / ``link_v`` int32 where the subgraphs are extracted from the graph; where they are
     rebuilt from stored node sets instead, ``_cache_t`` -- the six tensors ``uoff voff unodes vnodes udist vdist`` -- and
-    ``_cache``, their device pointers (``None``: no cache); ``_side`` float32 ``[capacity, n_side_features]``, the target
-    nodes' feature rows per position (``None``: no side features).
+    ``_cache``, their device pointers (``None``: no cache); side features of the target nodes: ``_side`` float32 ``[capacity,
+    n_side_features]``, their rows per position (a dataset's own links; where set, batches gather from it), else
+    ``_side_tables`` = ``(U [n_u, fu], V [n_v, fv])`` float32, one row per node, gathered by the ids of a batch's targets (links
+    that are nobody's own: candidate lists, leave-one-out variants, views); both ``None``: no side features.
 
     ``capacity`` is the number of positions ``link_y`` holds: what everything that keeps a buffer per position
     (``ScoreGraph``'s scores and labels, ``StepGraph``'s permutation) is sized by.  ``len()`` is the number of links held NOW; a
@@ -86,7 +111,7 @@ class LinkSource(object):
     dynamic = True
     link_u = link_v = None
     _cache = _cache_t = None
-    _side, n_side_features = None, 0
+    _side, _side_tables, n_side_features = None, None, 0
 
     def _configure(self, graph, device, h, sample_ratio, seed, max_nodes_per_hop):
         self.graph, self.lib, self.device = graph, graph.lib, device
@@ -95,12 +120,25 @@ class LinkSource(object):
         self._arenas = {}
 
     def _configure_from(self, source, graph=None):
-        """The settings of ``source`` (a dataset, or a view of one over another graph), over ``graph`` where given.  A source
-        with side features is refused: links that are not its own have no feature rows."""
-        refuse_side_features(source)
+        """The settings of ``source`` (a dataset, or a view of one over another graph), over ``graph`` where given, and its
+        per-node side-feature tables where it has them (``node_side()``: the SAME tensors, so every source derived from a
+        dataset gathers from one copy).  A source that names side features without such tables is refused."""
+        tables = source.node_side() if hasattr(source, 'node_side') else None
+        if tables is None:
+            refuse_side_features(source)
         self.source = source
         self._configure(source.graph if graph is None else graph, source.device, source.h, source.sample_ratio, source.seed,
                         source.max_nodes_per_hop)
+        self._take_side_tables(tables)
+
+    def _take_side_tables(self, tables):
+        self._side_tables = tables
+        self.n_side_features = 0 if tables is None else tables[0].shape[1] + tables[1].shape[1]
+
+    def node_side(self):
+        """``(U [n_u, fu], V [n_v, fv])``: the per-node side-feature tables this source serves with -- dense float32 device
+        tensors allocated once (captured launches hold their addresses) --, or None."""
+        return self._side_tables
 
     def __len__(self):
         return self.capacity
@@ -117,16 +155,19 @@ class LinkSource(object):
     def group_extractable(self):
         """A group's batches can go into their arenas in one launch per stage (``engine.BatchSet``: ``link_u`` / ``link_v``,
         nothing else to gather)."""
-        return self._cache is None and self._side is None
+        return self._cache is None and self._side is None and self._side_tables is None
 
     def arena(self, max_graphs, slot=0):
         key = (int(max_graphs), slot)
         if key not in self._arenas:
             a = engine.Batch(self.graph, int(max_graphs), self.h, self.max_nodes_per_hop)
+            # the target nodes' feature rows are gathered by the extraction launch itself (device-side, also under hipGraph
+            # replay of the training step): by link position from a dataset's own matrix, by target id from node tables
             if self._side is not None:
-                # the target nodes' feature rows are gathered by the extraction launch itself (device-side, also
-                # under hipGraph replay of the training step)
                 a.bind_side_source(self._side.data_ptr(), self.n_side_features)
+            elif self._side_tables is not None:
+                U, V = self._side_tables
+                a.bind_side_tables(U.data_ptr(), U.shape[0], U.shape[1], V.data_ptr(), V.shape[0], V.shape[1])
             self._arenas[key] = a
         return self._arenas[key]
 
@@ -148,6 +189,10 @@ class LinkSource(object):
         db = DeviceBatch(self, arena, B, positions, first)
         if self._side is not None:        # view of the rows the extraction launch gathered (for inspection / get())
             db.side = self._side.index_select(0, db.link_pos)
+        elif self._side_tables is not None:        # a copy of the arena's own gathered rows, taken behind the gather on `stream`
+            with torch.cuda.stream(torch.cuda.current_stream() if stream is None else torch.cuda.ExternalStream(int(stream))):
+                db.side = torch.as_tensor(_DevRows(arena.device_ptr('SIDE'), B, self.n_side_features),
+                                          device=self.link_y.device).clone()
         return db
 
 

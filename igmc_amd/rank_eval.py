@@ -155,8 +155,8 @@ def rank_eval(model, dataset, heldout, ks=(5, 10, 20), batch_size=50, exclude_se
     default ranks among every candidate.
 
     ``stats`` receives ``users``, ``candidates``, ``passes``, ``queries`` and ``not_candidates`` -- and ``negatives`` and
-    ``draw`` where ``negatives`` is given.  Side-feature datasets raise ``NotImplementedError`` (``CandidateLinks``).  Works
-    for ``DGCNN_RS`` too, and over a ``recommend.GraphView``."""
+    ``draw`` where ``negatives`` is given.  Works for ``DGCNN_RS`` too, over a ``recommend.GraphView``, and over a dataset
+    with side features (gathered per candidate from its ``node_side()`` tables)."""
     if not isinstance(heldout, HeldOut):
         heldout = HeldOut.from_links(heldout)
     ks = [int(k) for k in ks]

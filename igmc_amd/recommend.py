@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import engine
-from .links import LinkSource, kept
+from .links import LinkSource, dense_side_table, kept
 from .train_eval import score_links
 
 DEFAULT_CAPACITY = 1 << 22      # candidates of one pass where the caller names no ``users_per_pass``: 4 Mi links are 48 MB of
@@ -63,16 +63,29 @@ class GraphView(LinkSource):
     """The extraction settings of ``dataset`` over ANOTHER rating graph -- normally ``dataset.graph.updated(...)``, the
     graph after new ratings (``engine.Graph.updated``: built on the device) --, shaped like a dataset as far as
     :class:`CandidateLinks` reads one: ``graph``, ``device``, ``h``, ``sample_ratio``, ``seed``, ``max_nodes_per_hop``, a
-    ``link_y`` on the dataset's device (empty: a view has no links of its own) and no side features.  :func:`recommend`,
+    ``link_y`` on the dataset's device (empty: a view has no links of its own) and ``node_side()``.  :func:`recommend`,
     :func:`candidate_passes`, :func:`score_candidates` and ``rank_eval.rank_eval`` take it as they take a dataset; users and
-    items the graph gained are scored from their enclosing subgraphs like any other.  A dataset with side features is
-    refused: new users have no feature rows."""
+    items the graph gained are scored from their enclosing subgraphs like any other.
+
+    SIDE FEATURES (a dataset built with ``u_features`` / ``v_features``).  Without further arguments the view serves with the
+    dataset's own per-node tables, and a user or item the graph GAINED has no row there: its features read as ZEROS.  Give
+    ``u_features`` and ``v_features`` (both; scipy sparse or arrays) to name them: one row per node, at least as many rows as
+    the dataset's tables and exactly their column counts (``ValueError`` otherwise); the view then builds tables of its own,
+    once.  Rows beyond the arrays given read zeros as well.  Over a dataset without side features the arguments are an
+    error."""
 
     u_features = v_features = None
 
-    def __init__(self, dataset, graph):
+    def __init__(self, dataset, graph, u_features=None, v_features=None):
         self._configure_from(dataset, graph)
         self.link_y = torch.zeros(0, dtype=torch.float32, device=dataset.link_y.device)
+        if u_features is not None or v_features is not None:
+            if u_features is None or v_features is None or self._side_tables is None:
+                raise ValueError('u_features and v_features come together, over a dataset built with side features')
+            U, V = self._side_tables
+            self._take_side_tables(tuple(
+                torch.from_numpy(dense_side_table(f, what, old.shape[0], old.shape[1])).to(self.link_y.device)
+                for f, what, old in ((u_features, 'u_features', U), (v_features, 'v_features', V))))
 
 
 class CandidateLinks(LinkSource):

@@ -25,7 +25,7 @@ import scipy.sparse as ssp
 import torch
 
 from . import engine
-from .links import DeviceBatch, LinkSource          # noqa: F401  (DeviceBatch: importable from here as before)
+from .links import DeviceBatch, LinkSource, dense_side_table          # noqa: F401  (DeviceBatch: importable from here as before)
 
 
 class Data(object):
@@ -195,6 +195,20 @@ class _EngineDataset(LinkSource):
             side = np.asarray(ssp.hstack([uf, vf]).todense(), dtype=np.float32)
             self._side = torch.from_numpy(np.ascontiguousarray(side)).to(dev)
             self.n_side_features = side.shape[1]
+
+    def node_side(self):
+        """The side features by NODE, for sources whose links are not this dataset's own (``links.LinkSource``: candidate
+        lists, leave-one-out variants, views): ``(U [n_users, fu], V [n_items, fv])``, dense float32 device tensors built
+        from ``u_features`` / ``v_features`` on first use and kept -- one copy at fixed addresses for every source derived
+        from this dataset --, or None for a dataset without features.  The dataset's own batches keep their per-position
+        matrix ``_side``."""
+        if self._side is None:
+            return None
+        if self._side_tables is None:
+            dev = self.link_y.device
+            self._side_tables = tuple(torch.from_numpy(dense_side_table(f, what)).to(dev) for f, what in
+                                      ((self.u_features, 'u_features'), (self.v_features, 'v_features')))
+        return self._side_tables
 
     # ---- reference surface
     def get(self, idx):

@@ -97,7 +97,7 @@ int igmc_extract_batch_cached(const igmc_graph* g, igmc_batch* b,
  * into the arenas of `set` with the kernels of igmc_extract_batch launched ONCE over all of them, followed -- drop_p > 0 --
  * by their edge dropout (igmc_batch_edge_dropout with step = the batch's selector).  Every arena of the set must belong to
  * `g`, share one geometry, carry dense induced blocks, be lean (igmc_batch_set_lean), have the same control block attached
- * and no side-feature source; anything else is an error (callers then extract arena by arena). */
+ * and no side-feature source or tables; anything else is an error (callers then extract arena by arena). */
 typedef struct igmc_batch_set igmc_batch_set;
 int igmc_batch_set_create(igmc_batch* const* batches, int count, igmc_batch_set** out);
 void igmc_batch_set_destroy(igmc_batch_set* s);
@@ -127,10 +127,12 @@ int igmc_batch_get_info(const igmc_batch* b, igmc_batch_info* out, void* stream)
 int igmc_batch_download(const igmc_batch* b, int32_t* node_off, int32_t* n_users, uint8_t* node_label,
                         int32_t* node_gid, int32_t* node_graph, int32_t* row_ptr, int32_t* col,
                         uint8_t* erel, uint8_t* elab, uint8_t* eflag, float* y, void* stream);
-/* Device pointers of the collated batch (for zero-copy views): index by IGMC_BUF_*. */
+/* Device pointers of the collated batch (for zero-copy views): index by IGMC_BUF_*.  IGMC_BUF_SIDE: the [B, n_side] fp32 side
+ * features the next forward reads (the arena's gathered rows, or the pointer handed to igmc_batch_set_side_features; NULL:
+ * none). */
 enum { IGMC_BUF_NODE_OFF = 0, IGMC_BUF_N_USERS, IGMC_BUF_NODE_LABEL, IGMC_BUF_NODE_GID,
        IGMC_BUF_NODE_GRAPH, IGMC_BUF_ROW_PTR, IGMC_BUF_ECR, IGMC_BUF_ECODE,
-       IGMC_BUF_EFLAG, IGMC_BUF_Y, IGMC_BUF_TOTALS, IGMC_BUF_COUNT };
+       IGMC_BUF_EFLAG, IGMC_BUF_Y, IGMC_BUF_TOTALS, IGMC_BUF_SIDE, IGMC_BUF_COUNT };
 void* igmc_batch_device_ptr(const igmc_batch* b, int which);
 /* Optional side features of the two target nodes (reference util_functions.py:250-253,
  * models.py:208-209): d_feat[B, n_side] fp32, borrowed for the next forward. */
@@ -141,6 +143,19 @@ int igmc_batch_set_side_features(igmc_batch* b, const float* d_feat, int n_side)
  * links (same d_link_idx / first / control-block indexing as the extraction) into an arena-owned buffer that the
  * model then reads -- nothing happens on the host per step, so the step stays hipGraph-capturable.  NULL unbinds. */
 int igmc_batch_bind_side_source(igmc_batch* b, const float* d_side_all, int n_side);
+/* The same, keyed by NODE (no reference counterpart: the reference indexes u_features / v_features by the target ids on the
+ * host, util_functions.py:250-253): d_u_feat[n_u_rows, fu] and d_v_feat[n_v_rows, fv], fp32 row-major, borrowed, hold one row
+ * per user / item.  Every following igmc_extract_batch / igmc_extract_batch_cached on this arena writes, behind its own launches
+ * on the same stream, row g < B of the arena-owned buffer = [d_u_feat[tu] | d_v_feat[tv]] with tu / tv the target user / item
+ * the extraction left in slot g -- no link array, permutation or control-block cursor is read, so the launch is the same for
+ * free-running extraction, cached node sets and a hipGraph replay, and serves links that are no dataset's own (candidate
+ * lists, leave-one-out variants).  A target id at or beyond its table's row count reads zeros (a node the graph gained after
+ * the tables were built); nothing is read outside the tables or written at or beyond row B.  fu, fv >= 0, fu + fv >= 1
+ * (n_side becomes fu + fv); a NULL table with a non-zero width is an error; both NULL with zero widths unbinds.  Tables, a
+ * side source and igmc_batch_set_side_features replace one another: the last call holds.  igmc_extract_group refuses an
+ * arena with tables as it refuses one with a source. */
+int igmc_batch_bind_side_tables(igmc_batch* b, const float* d_u_feat, int n_u_rows, int fu, const float* d_v_feat, int n_v_rows,
+                                int fv);
 /* Lean extraction (arenas with a per-hop cap only; ignored otherwise): igmc_extract_batch stops after the node sets,
  * labels, ratings and the dense induced blocks -- everything the matrix-core subgraph kernel reads -- and the collated
  * CSR (reference construct_pyg_graph + Batch.from_data_list, util_functions.py:280-297) is emitted on demand by the
