@@ -103,6 +103,14 @@ def build_parser():
                         'the device; the user\'s other held-out items stay in the list) instead of among all of them')
     p.add_argument('--rank-draw', type=int, default=0, metavar='D',
                    help='--rank-negatives: which draw of the negatives (default 0); another D gives another sample')
+    p.add_argument('--shortlist', type=int, default=None, metavar='M',
+                   help='--recommend / --rank-eval / --explain of the recommended pairs: score only every user\'s M unseen items '
+                        'with the most co-rating votes ("people who liked what you liked also liked", counted on the device) '
+                        'instead of all of them; --rank-eval counts a held-out item the shortlist cut as a miss and also writes '
+                        'the shortlist\'s own recall.  A user without ratings gets its M lowest unseen item ids.  Not with '
+                        '--rank-negatives')
+    p.add_argument('--shortlist-min-rating', type=float, default=None, metavar='X',
+                   help='--shortlist: only ratings >= X count, as what a user liked and as a vote (default: every rating)')
     p.add_argument('--new-ratings', default=None, metavar='FILE',
                    help='rating changes applied to the training graph ON THE DEVICE before --recommend / --rank-eval: lines '
                         '"user item rating" (ids as recommendations_*.tsv prints them, "#" comments; rating 0 removes the '
@@ -156,6 +164,34 @@ def recommend_users(spec, n_users):
         return np.asarray([int(line) for line in f if line.strip()], dtype=np.int32)
 
 
+def shortlist_flag_error(shortlist, min_rating, rank_negatives, serving):
+    """The argument error of ``--shortlist`` / ``--shortlist-min-rating`` in this combination of flags, or None."""
+    if shortlist is None:
+        return '--shortlist-min-rating names the ratings that count for --shortlist M: give M' if min_rating is not None else None
+    if not 1 <= shortlist < 2 ** 31:
+        return '--shortlist takes M in [1, 2^31)'
+    if rank_negatives is not None:
+        return '--shortlist and --rank-negatives exclude one another: sampled negatives are an evaluation protocol, a ' \
+               'shortlist is a retrieval stage'
+    if not serving:
+        return '--shortlist shortens the candidate lists of --recommend N / --rank-eval K[,K...]: give one of them'
+    return None
+
+
+def shortlist_min_rel(class_values, min_rating):
+    """The relation index both thresholds of ``--shortlist`` take: that of the smallest ``class_values`` entry >=
+    ``--shortlist-min-rating`` (their number where there is none: no rating counts); 0 without the flag."""
+    if min_rating is None:
+        return 0
+    return int((np.asarray(class_values, np.float64) < float(min_rating)).sum())
+
+
+def shortlist_kwargs(args):
+    if args.shortlist is None:
+        return {}
+    return dict(shortlist=args.shortlist, seed_min_rel=args.shortlist_min_rel, vote_min_rel=args.shortlist_min_rel)
+
+
 def write_recommendations(model, train_graphs, args):
     """``--recommend N``: ``<res_dir>/recommendations_<data_name>.tsv`` with lines ``user\trank\titem\tscore`` (ranks
     from 1, best first; a user with fewer than N unseen items has fewer lines)."""
@@ -166,7 +202,7 @@ def write_recommendations(model, train_graphs, args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     items, scores, counts = recommend(model, train_graphs, users=users, n=args.recommend, batch_size=args.batch_size,
-                                      stats=stats)
+                                      stats=stats, **shortlist_kwargs(args))
     items, scores, counts = items.cpu().numpy(), scores.cpu().numpy(), counts.cpu().numpy()      # (synchronises)
     dt = time.perf_counter() - t0
     ids = np.arange(train_graphs.graph.n_users) if users is None else users
@@ -176,7 +212,8 @@ def write_recommendations(model, train_graphs, args):
             for r in range(int(c)):
                 f.write('%d\t%d\t%d\t%.6f\n' % (u, r + 1, row[r], srow[r]))
     print('Recommended for {} users: {} candidates scored in {} pass(es), {:.0f} candidates/s; wrote {}'.format(
-        stats['users'], stats['candidates'], stats['passes'], stats['candidates'] / max(dt, 1e-9), path))
+        stats['users'], stats['candidates'], stats['passes'], stats['candidates'] / max(dt, 1e-9), path) +
+        ('' if args.shortlist is None else ' (shortlist {})'.format(args.shortlist)))
     # (--explain without --explain-links: the recommended pairs, in the file's order)
     args.recommended_pairs = (np.repeat(np.asarray(ids, np.int32), counts),
                               np.concatenate([row[:int(c)] for row, c in zip(items, counts)] or [np.zeros(0, np.int32)]))
@@ -233,9 +270,12 @@ def rank_eval_ks(spec):
 def write_ranking(model, train_graphs, heldout_graphs, args):
     """``--rank-eval``: ``<res_dir>/ranking_<data_name>.tsv`` with lines ``metric\tvalue`` -- the ranking metrics of the held-out
     links among every user's unseen items of the training graph (``igmc_amd/rank_eval.py``); with ``--rank-negatives K`` among
-    K sampled ones, and two more lines ``negatives\tK`` and ``draw\tD``."""
+    K sampled ones, and two more lines ``negatives\tK`` and ``draw\tD``; with ``--shortlist M`` among the user's M unseen items
+    with the most co-rating votes, held-out items the shortlist cut counted as misses, and three more lines ``shortlist\tM``,
+    ``cut_by_shortlist\tn`` and ``shortlist_recall\tx`` (the share of the relevant held-out candidate links the shortlist
+    keeps: ``rank_eval.shortlist_recall``, micro)."""
     import time
-    from igmc_amd.rank_eval import HeldOut, metric_names, rank_eval
+    from igmc_amd.rank_eval import HeldOut, metric_names, rank_eval, shortlist_recall
     ks = rank_eval_ks(args.rank_eval)
     users = recommend_users(args.recommend_users, train_graphs.graph.n_users)
     heldout = HeldOut.from_links(heldout_graphs, min_rating=args.rank_min_rating)
@@ -243,9 +283,14 @@ def write_ranking(model, train_graphs, heldout_graphs, args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     sampled = {} if args.rank_negatives is None else dict(negatives=args.rank_negatives, draw=args.rank_draw)
+    short = shortlist_kwargs(args)
     res = rank_eval(model, train_graphs, heldout, ks=ks, batch_size=args.batch_size, users=users, stats=stats,
-                    **sampled)      # (synchronises)
+                    **sampled, **short)      # (synchronises)
     dt = time.perf_counter() - t0
+    recall = None
+    if short:
+        recall = shortlist_recall(train_graphs, heldout, ms=(args.shortlist,), users=users, seed_min_rel=short['seed_min_rel'],
+                                  vote_min_rel=short['vote_min_rel'])[args.shortlist]['micro']
     names = metric_names(ks)
     path = os.path.join(args.res_dir, 'ranking_{}.tsv'.format(args.data_name))
     with open(path, 'w') as f:
@@ -253,10 +298,15 @@ def write_ranking(model, train_graphs, heldout_graphs, args):
             f.write('%s\t%.6f\n' % (k, res[k]))
         if sampled:
             f.write('negatives\t%d\ndraw\t%d\n' % (args.rank_negatives, args.rank_draw))
+        if short:
+            f.write('shortlist\t%d\ncut_by_shortlist\t%d\nshortlist_recall\t%.6f\n' % (args.shortlist, stats['cut_by_shortlist'],
+                                                                                       recall))
     print('Ranked {} held-out links of {} users ({} not among the candidates; means over {} users) among {} candidates in '
           '{} pass(es), {:.0f} candidates/s: {}; wrote {}'.format(
               stats['queries'], stats['users'], stats['not_candidates'], res['users_evaluated'], stats['candidates'],
-              stats['passes'], stats['candidates'] / max(dt, 1e-9), ', '.join('%s %.4f' % (k, res[k]) for k in names), path))
+              stats['passes'], stats['candidates'] / max(dt, 1e-9), ', '.join('%s %.4f' % (k, res[k]) for k in names), path) +
+          ('' if not short else ' (shortlist {}: {} held-out candidates cut and counted as misses, shortlist recall {:.4f})'.format(
+              args.shortlist, stats['cut_by_shortlist'], recall)))
     return path
 
 
@@ -292,6 +342,9 @@ def main(argv=None):
         parser.error('--rank-draw names the draw of --rank-negatives K: give K')
     if args.rank_draw < 0:
         parser.error('--rank-draw takes D >= 0')
+    bad = shortlist_flag_error(args.shortlist, args.shortlist_min_rating, args.rank_negatives, args.recommend > 0 or args.rank_eval)
+    if bad:
+        parser.error(bad)
     if args.explain < 0 or args.explain > 64:
         parser.error('--explain takes M in [1, 64]')
     if args.explain > 0 and not args.explain_links and not args.recommend > 0:
@@ -352,6 +405,7 @@ def main(argv=None):
     if rank == 0:
         print('All ratings are:')
         print(class_values)
+    args.shortlist_min_rel = shortlist_min_rel(class_values, args.shortlist_min_rating)
     if args.use_features:
         if u_features is None or v_features is None:
             raise ValueError('--use-features: dataset %s has no side features here' % args.data_name)

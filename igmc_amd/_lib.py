@@ -81,6 +81,10 @@ SIGNATURES = {
     'igmc_candidates_sample_fill': (i32, [vp, vp, i32, vp, i32, vp, vp, i64, i64, u64, u64, vp, vp, vp, vp, i64, vp, vp]),
     'igmc_select_segments_scratch_bytes': (i64, [i32, i32, i32]),
     'igmc_select_segments': (i32, [vp, vp, i32, i32, vp, vp, vp, vp, i64, i32, vp]),
+    'igmc_shortlist_scratch_bytes': (i64, [vp, i32, i32]),
+    'igmc_shortlist_plan_info': (i32, [vp, i32, i32, vp]),
+    'igmc_shortlist_fill': (i32, [vp, vp, i32, vp, i32, i32, i32, i64, vp, vp, vp, vp, i64, vp, vp, i64, i32, vp]),
+    'igmc_shortlist_places': (i32, [vp, vp, i32, vp, i32, i32, i32, vp, vp, i64, vp, vp, vp, vp, i64, i32, vp]),
     'igmc_rank_segments': (i32, [vp, vp, i64, vp, i32, vp, vp, i64, vp, vp, vp, i32, vp]),
     'igmc_rank_metrics': (i32, [vp, vp, vp, i64, i32, vp, i32, vp, vp, vp, i32, vp]),
     'igmc_loo_count': (i32, [vp, i32, vp, vp, vp, vp]),

@@ -1,0 +1,74 @@
+// cand_tile.h -- THE definition of a user's candidates C (items in range, not in the user's row where exclude_seen, item_ok),
+// as LDS ballots over a tile of items: shared by candidates.hip (the exhaustive and the sampled lists) and shortlist.hip (the
+// co-rating shortlist), so that the three kinds of segment can never disagree about what a candidate is.
+#pragma once
+#include "launch.h"
+
+#define CAND_TILE_WORDS IGMC_BLOCK                 // 64-item words of a bitmap tile: one per thread of the scan
+#define CAND_TILE (CAND_TILE_WORDS * 64)
+static_assert(CAND_TILE == IGMC_CAND_TILE_ITEMS, "launch.h names the tile");
+
+// LDS of one workgroup: the must bitmap, the forced ballots, the histogram and the parked keys exist in the SAMPLED
+// instantiations alone (members in this order: the sampled fill's register count depends on it)
+template <bool SAMPLED>
+struct CandLds;
+template <>
+struct CandLds<false> {
+  uint32_t row[2 * CAND_TILE_WORDS];               // items of the tile the user rated
+  unsigned long long pool[CAND_TILE_WORDS];        // C of the tile
+  int woff[CAND_TILE_WORDS];
+  int smi[16];
+};
+template <>
+struct CandLds<true> {
+  uint32_t row[2 * CAND_TILE_WORDS];
+  uint32_t must[2 * CAND_TILE_WORDS];              // must items of the tile
+  unsigned long long pool[CAND_TILE_WORDS];        // N of the tile; the emission overwrites it with the words it writes
+  unsigned long long forc[CAND_TILE_WORDS];        // M n C of the tile
+  int woff[CAND_TILE_WORDS];
+  int hist[IGMC_BLOCK];
+  uint32_t ckey[IGMC_BLOCK];                       // parked keys of the deciding byte
+  int smi[16];
+};
+
+// pool (and forc) of the tile at tile0 (nw words).  report: a must item outside [0, n_items) raises bit 3 (first walk only)
+template <bool SAMPLED>
+__device__ __forceinline__ void cand_build_tile(const CandArgs& a, CandLds<SAMPLED>& s, int lo, int hi, int64_t mo, int64_t me,
+                                                int tile0, int nw, bool report) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nwave = IGMC_BLOCK >> 6;
+  s.row[2 * t] = s.row[2 * t + 1] = 0u;
+  if constexpr (SAMPLED) s.must[2 * t] = s.must[2 * t + 1] = 0u;
+  __syncthreads();
+  for (int p = lo + t; p < hi; p += IGMC_BLOCK) {
+    const int v = a.g.u_idx[p] - tile0;
+    if (v >= 0 && v < CAND_TILE) atomicOr(&s.row[v >> 5], 1u << (v & 31));
+  }
+  if constexpr (SAMPLED) {
+    for (int64_t p = mo + t; p < me; p += IGMC_BLOCK) {
+      const int id = a.must_item[p];
+      if (id < 0 || id >= a.g.n_items) {        // ignored and reported
+        if (report) atomicOr(a.err, 8);
+        continue;
+      }
+      const int v = id - tile0;
+      if (v >= 0 && v < CAND_TILE) atomicOr(&s.must[v >> 5], 1u << (v & 31));
+    }
+  }
+  __syncthreads();
+  for (int w = wave; w < nw; w += nwave) {
+    const int v = tile0 + w * 64 + lane;
+    const int h = 2 * w + (lane >> 5), bit = lane & 31;
+    const bool cand = v < a.g.n_items && !((s.row[h] >> bit) & 1u) && (!a.item_ok || a.item_ok[v] != 0);
+    const unsigned long long c = __ballot(cand);
+    if constexpr (SAMPLED) {
+      const unsigned long long m = __ballot(cand && ((s.must[h] >> bit) & 1u));
+      if (lane == 0) {
+        s.pool[w] = c & ~m;
+        s.forc[w] = m;
+      }
+    } else {
+      if (lane == 0) s.pool[w] = c;
+    }
+  }
+  __syncthreads();
+}

@@ -119,6 +119,45 @@ void igmc_launch_candidates(const CandArgs& a, int fill, int sampled, void* stre
 int igmc_segsel_default_split(int ns);
 void igmc_launch_select_segments(const float* keys, const int64_t* seg_off, int ns, int num, int k, void* scratch,
                                  int32_t* idx_out, float* key_out, int32_t* count, void* stream);
+// shortlist.hip: the co-rating shortlist of a set of users (igmc_hip.h states the definition) -- the segments themselves, or
+// the places of given items in the full vote order
+#define IGMC_SHORT_TILE_ITEMS IGMC_CAND_TILE_ITEMS      // items of the LDS vote table (uint32 each, 64 KB): every bundled dataset
+                                                        // and ml_10m (10 677 items) in one tile; wider graphs keep their votes in
+                                                        // the workgroup's scratch row
+#define IGMC_SHORT_LDS_BYTES (160 * 1024)               // LDS of one workgroup at most (gfx950: 160 KB a CU): w sits in LDS
+                                                        // where it fits beside the fixed part and the vote table, else in scratch
+#define IGMC_SHORT_MAX_GRID 512                         // workgroups (and scratch rows) where the caller names no grid: 2 a CU
+struct ShortArgs {
+  GraphDev g;
+  const int32_t* users;
+  int nq;
+  const uint8_t* item_ok;
+  int exclude_seen;
+  int seed_min_rel, vote_min_rel;
+  int64_t m;                    // fill
+  const int64_t* off;
+  int32_t* link_u;
+  int32_t* link_v;
+  uint32_t* votes_out;          // may be null
+  int64_t capacity;
+  const int64_t* q_off;         // places
+  const int32_t* q_id;
+  int64_t n_query;
+  int32_t* q_place;
+  uint32_t* q_votes;            // may be null
+  int32_t* err;
+  uint32_t* scratch;            // [grid] rows of row_words: w (n_users words, where not in LDS), then the votes (n_items words,
+  int64_t row_words;            // where the graph is wider than the LDS vote table)
+};
+struct ShortPlan {
+  int grid, w_lds, v_lds;       // workgroups; w / the vote table in LDS
+  int lds_bytes;                // dynamic LDS of the launch
+  int64_t row_words, scratch_bytes;
+  int w_lds_max_users;          // the most users whose w fits LDS for this graph's item count
+};
+void igmc_shortlist_plan(int n_users, int n_items, int nq, int grid, ShortPlan* p);
+int igmc_shortlist_prepare();
+void igmc_launch_shortlist(const ShortArgs& a, const ShortPlan& p, int places, void* stream);
 // ranking.hip: the position and the 0-based place (the order of igmc_launch_select_segments) of given ids in their segments,
 // and the per-segment sums of the ranking metrics over those places
 #define IGMC_RANK_MAX_KS 8              // cut-offs K of one metrics launch at most

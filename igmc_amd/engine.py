@@ -527,6 +527,80 @@ def candidates_fill(graph, users, mask, exclude_seen, offsets, link_u, link_v, e
     graph.lib.call(name + '_fill', *(args + out + (link_u.numel(), _p(err.data_ptr()), _p(st))))
 
 
+def _shortlist_scratch(graph, nq, grid, dev):
+    """The graph's shortlist scratch (kept on the ``Graph`` and grown on demand) as ``(pointer, bytes)``; ``(None, 0)`` where
+    both tables of a workgroup fit its LDS."""
+    import torch
+    nbytes = graph.lib.igmc_shortlist_scratch_bytes(graph.handle, int(nq), int(grid))
+    if nbytes < 0:
+        raise RuntimeError('igmc_shortlist_scratch_bytes failed: %s' % graph.lib.cdll.igmc_last_error().decode())
+    if nbytes == 0:
+        return None, 0
+    have = getattr(graph, '_shortlist_scratch', None)
+    if have is None or have.numel() * 4 < nbytes or have.device != dev:
+        have = graph._shortlist_scratch = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    return _p(have.data_ptr()), nbytes
+
+
+def _shortlist_head(graph, users, mask, exclude_seen, seed_min_rel, vote_min_rel):
+    if min(int(seed_min_rel), int(vote_min_rel)) < 0:
+        raise ValueError('seed_min_rel and vote_min_rel must be at least 0')
+    return (graph.handle, _p(users.data_ptr()), users.numel(), _p(None if mask is None else mask.data_ptr()),
+            int(bool(exclude_seen)), int(seed_min_rel), int(vote_min_rel))
+
+
+def shortlist_fill(graph, users, mask, exclude_seen, m, offsets, link_u, link_v, err, votes=None, seed_min_rel=0,
+                   vote_min_rel=0, grid=0, stream=None):
+    """Every user's ``min(m, candidates)`` candidates with the most co-rating votes, item ascending, written at ``offsets``
+    (device int64 ``[nq + 1]``: the prefix sums of :func:`candidates_count` clamped to ``m``) into the device int32 buffers
+    ``link_u`` / ``link_v`` and -- ``votes``: device int32 / uint32 of the same length, or None -- their vote counts
+    (``igmc_shortlist_fill``; ``include/igmc_hip.h`` states the definition; no reference counterpart).  A user without a
+    seeding entry gets its ``m`` lowest candidate ids.  ``err`` collects the error bits of :func:`candidates_fill` and is
+    left to the caller."""
+    import torch
+    if not 1 <= int(m) <= 2 ** 31 - 1:
+        raise ValueError('shortlist size must be in [1, 2^31)')
+    head = _shortlist_head(graph, users, mask, exclude_seen, seed_min_rel, vote_min_rel)
+    sp, sb = _shortlist_scratch(graph, users.numel(), grid, users.device)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    graph.lib.call('igmc_shortlist_fill', *(head + (int(m), _p(offsets.data_ptr()), _p(link_u.data_ptr()), _p(link_v.data_ptr()),
+                                                    _p(None if votes is None else votes.data_ptr()), link_u.numel(),
+                                                    _p(err.data_ptr()), sp, sb, int(grid), _p(st))))
+
+
+def shortlist_places(graph, users, mask, exclude_seen, q_off, q_id, seed_min_rel=0, vote_min_rel=0, err=None, grid=0,
+                     stream=None):
+    """Where the items ``q_id`` (device int32; request ``q`` owns ``q_id[q_off[q]:q_off[q + 1]]``, ``q_off`` device int64
+    ``[nq + 1]``) stand in the FULL vote order of their users (``igmc_shortlist_places``).  Returns device tensors ``(place
+    int32, votes int32)``: the number of candidates before the item (votes descending, item id ascending) or -1 where it is no
+    candidate, and its vote count (below 2^31 by the entry point's own limit).  "In the shortlist of size m" is ``0 <= place <
+    m``.  ``err``: as in :func:`rank_segments` (bit 0: inconsistent ``q_off``; bit 1: a user id out of range)."""
+    import torch
+    _dev_vector(q_off, torch.int64, 'q_off')
+    _dev_vector(q_id, torch.int32, 'q_id')
+    if q_off.numel() != users.numel() + 1:
+        raise ValueError('one query range per requested user')
+    nquery = q_id.numel()
+    place = torch.full((nquery,), -1, dtype=torch.int32, device=users.device)
+    votes = torch.zeros(nquery, dtype=torch.int32, device=users.device)
+    if nquery == 0:
+        return place, votes
+    own = err is None
+    if own:
+        err = torch.zeros(1, dtype=torch.int32, device=users.device)
+    head = _shortlist_head(graph, users, mask, exclude_seen, seed_min_rel, vote_min_rel)
+    sp, sb = _shortlist_scratch(graph, users.numel(), grid, users.device)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    graph.lib.call('igmc_shortlist_places', *(head + (_p(q_off.data_ptr()), _p(q_id.data_ptr()), nquery, _p(place.data_ptr()),
+                                                      _p(votes.data_ptr()), _p(err.data_ptr()), sp, sb, int(grid), _p(st))))
+    if own:
+        e = int(err.item())
+        if e:
+            raise RuntimeError('igmc_shortlist_places: %s (err=%d)' % (
+                '; '.join(w for b, w in ((1, RANK_ERRORS[0][1]), (2, 'a user id outside [0, n_users)')) if e & b), e))
+    return place, votes
+
+
 RANK_ERRORS = ((1,'query offsets that are not 0 = q_off[0] <= ... <= q_off[ns] = the number of queries'),
                (2, 'a segment outside the keys'))
 

@@ -39,12 +39,23 @@ exactly as they do in the exhaustive evaluation, so ``negatives`` >= every user'
 exhaustive result bit for bit; ranking each positive against the negatives alone is not offered.  ``not_candidates`` is what
 it is in the exhaustive run.  SAMPLER POSITIONS carries over, and positions in a sampled list differ from those in the full
 list: under a binding per-hop cap the sampled and the exhaustive score of the same pair may differ.
+
+SHORTLISTS (``shortlist=M``; ``recommend``'s module docstring): only every user's M candidates with the most co-rating votes are
+scored, as ``recommend(shortlist=M)`` scores them.  A held-out link that IS a candidate but is cut by the shortlist is a MISS: it
+counts in n_rel, has no hit at any K, adds nothing to the DCG (the ideal DCG does count it) and its reciprocal rank is 0 -- it
+carries the rank ``MISS_RANK``, beyond every K.  A link that is no candidate keeps the treatment above.  The two are told apart
+by ``igmc_shortlist_places`` in the same pass (the link's place in the full vote order: ``place >= M`` is a cut), not by a second
+enumeration.  M >= every user's candidate count reproduces the exhaustive result bit for bit.  :func:`shortlist_recall` judges the
+shortlist by itself, without the model: the share of relevant held-out candidate links with ``place < M``.
 """
 import numpy as np
 import torch
 
 from . import engine
-from .recommend import _dev_int32, candidate_passes
+from .recommend import _check_shortlist, _dev_int32, _item_mask, candidate_passes
+
+MISS_RANK = 2 ** 31 - 1      # the rank of a held-out candidate link that a shortlist cut: at or beyond every K (a K is below 2^31),
+                             # above every real rank (a list holds fewer than 2^31 - 1 entries)
 
 
 class HeldOut(object):
@@ -123,7 +134,8 @@ def metric_names(ks):
 
 def reduce_metrics(cnt, dcg, ks):
     """The means of the module docstring from the per-user sums of ``igmc_rank_metrics``: a float64 device vector in the
-    order of :func:`metric_names`, with the number of users it was taken over behind it.  NaN where no user counts."""
+    order of :func:`metric_names`, with the number of users it was taken over behind it.  NaN where no user counts.  A first
+    rank of ``MISS_RANK`` (every relevant link of the user was cut by a shortlist) has the reciprocal rank 0."""
     nk = len(ks)
     keep = cnt[:, 0] > 0
     n = keep.sum().to(torch.float64)
@@ -133,12 +145,14 @@ def reduce_metrics(cnt, dcg, ks):
     for j, k in enumerate(ks):
         out += [(hits[:, j] > 0).to(torch.float64).sum() / n, (hits[:, j] / n_rel).sum() / n, (hits[:, j] / float(k)).sum() / n,
                 (dcg[keep, j] / dcg[keep, nk + j]).sum() / n]
-    out.append((1.0 / (cnt[keep, 1].to(torch.float64) + 1.0)).sum() / n)
+    first = cnt[keep, 1]
+    rr = 1.0 / (first.to(torch.float64) + 1.0)
+    out.append(torch.where(first == MISS_RANK, torch.zeros_like(rr), rr).sum() / n)
     return torch.stack(out + [n])
 
 
 def rank_eval(model, dataset, heldout, ks=(5, 10, 20), batch_size=50, exclude_seen=True, item_mask=None, users=None,
-              users_per_pass=None, stats=None, negatives=None, draw=0):
+              users_per_pass=None, stats=None, negatives=None, draw=0, shortlist=None, seed_min_rel=0, vote_min_rel=0):
     """Ranking metrics of ``heldout`` (a :class:`HeldOut`, or a dataset: :meth:`HeldOut.from_links`) over the rating graph
     and with the extraction settings of ``dataset`` (normally the training set), for the held-out users -- or those of
     them that are in ``users`` --: for every pass of ``recommend`` (same candidates, same scores, same ``users_per_pass``)
@@ -149,33 +163,47 @@ def rank_eval(model, dataset, heldout, ks=(5, 10, 20), batch_size=50, exclude_se
     were taken over) and ``per_user``: device tensors ``users`` (int32 ``[m]``), ``offsets`` (int64 ``[m + 1]``: the user's
     links), ``items`` / ``relevant`` of the links, ``cnt`` (int32 ``[m, 2 + nk]``) / ``dcg`` (float64 ``[m, 2 * nk]``) as
     ``engine.rank_metrics`` returns them, and per link ``rank`` and ``pos``, its position in ITS PASS's candidate list
-    (both -1 for a link that is no candidate), ``index`` (its place in ``heldout``; None = the same place).
+    (both -1 for a link that is no candidate), ``index`` (its place in ``heldout``; None = the same place).  With
+    ``shortlist``: also ``place``, the link's place in its user's full vote order (-1: no candidate), and a link the shortlist
+    cut has ``pos`` -1 and ``rank`` ``MISS_RANK``.
 
     ``negatives=K``: among ``K`` sampled negatives per user, drawn under ``draw`` (module docstring: SAMPLED NEGATIVES); the
-    default ranks among every candidate.
+    default ranks among every candidate.  ``shortlist=M`` (not together with ``negatives``): among the user's M candidates with
+    the most co-rating votes under ``seed_min_rel`` / ``vote_min_rel``, links the shortlist cut counted as misses (module
+    docstring: SHORTLISTS; a user without a seeding entry is shortlisted its M lowest candidate ids).
 
     ``stats`` receives ``users``, ``candidates``, ``passes``, ``queries`` and ``not_candidates`` -- and ``negatives`` and
-    ``draw`` where ``negatives`` is given.  Works for ``DGCNN_RS`` too, over a ``recommend.GraphView``, and over a dataset
+    ``draw`` where ``negatives`` is given, ``shortlist`` and ``cut_by_shortlist`` where ``shortlist`` is.  Works for ``DGCNN_RS`` too, over a ``recommend.GraphView``, and over a dataset
     with side features (gathered per candidate from its ``node_side()`` tables)."""
     if not isinstance(heldout, HeldOut):
         heldout = HeldOut.from_links(heldout)
     ks = [int(k) for k in ks]
     if not 1 <= len(ks) <= 8 or min(ks) < 1:
         raise ValueError('ks: 1 to 8 cut-offs K >= 1')
+    _check_shortlist(shortlist, negatives)
     sel_users, q_off, items, relevant, index = _select(heldout, users)
     if sel_users.numel() < 1:
         raise ValueError('none of the users has a held-out link')
     dev = items.device
     bounds = q_off.tolist()                 # (per user, once: the passes' slices of the query list)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    pos, rank, total, passes = [], [], 0, 0
+    pos, rank, place, total, passes = [], [], [], 0, 0
     sampled = {} if negatives is None else dict(negatives=int(negatives), must=(q_off, items), draw=int(draw))
+    if shortlist is not None:
+        sampled = dict(shortlist=int(shortlist), seed_min_rel=seed_min_rel, vote_min_rel=vote_min_rel)
+        mask = _item_mask(dataset.graph, item_mask, dev)
+        serr = torch.zeros(1, dtype=torch.int32, device=dev)
     for q0, cands, R in candidate_passes(model, dataset, sel_users, batch_size, exclude_seen, item_mask, users_per_pass,
                                          **sampled):
         m = cands.users.numel()
         a, b = bounds[q0], bounds[q0 + m]
-        p, r = engine.rank_segments(R, cands.link_v[:len(cands)], cands.offsets, (q_off[q0:q0 + m + 1] - a).contiguous(),
-                                    items[a:b], err=err, lib=cands.lib)
+        mine = (q_off[q0:q0 + m + 1] - a).contiguous()
+        p, r = engine.rank_segments(R, cands.link_v[:len(cands)], cands.offsets, mine, items[a:b], err=err, lib=cands.lib)
+        if shortlist is not None:          # a candidate the shortlist cut is a miss, not a link without a rank
+            pl, _ = engine.shortlist_places(cands.graph, cands.users, mask, exclude_seen, mine, items[a:b].contiguous(),
+                                            seed_min_rel, vote_min_rel, err=serr)
+            r = torch.where((p < 0) & (pl >= 0), torch.full_like(r, MISS_RANK), r)
+            place.append(pl)
         pos.append(p)
         rank.append(r)
         total += len(cands)
@@ -183,16 +211,79 @@ def rank_eval(model, dataset, heldout, ks=(5, 10, 20), batch_size=50, exclude_se
     pos, rank = torch.cat(pos), torch.cat(rank)
     cnt, dcg = engine.rank_metrics(rank, q_off, ks, relevant, err=err, lib=dataset.graph.lib)
     means = reduce_metrics(cnt, dcg, ks)
+    cut = 0
+    if shortlist is not None:
+        place = torch.cat(place)
+        cut, bad = torch.stack([((pos < 0) & (place >= 0)).sum(), serr[0].to(torch.int64)]).tolist()
+        if bad:
+            raise RuntimeError('rank_eval: igmc_shortlist_places reported err=%d' % bad)
     host = torch.cat([means, (pos < 0).sum().to(torch.float64).view(1), err.to(torch.float64)]).tolist()
     if int(host[-1]):
         engine._raise_rank_errors(err, 'rank_eval')
     if stats is not None:
         stats.update(users=sel_users.numel(), candidates=total, passes=passes, queries=items.numel(),
-                     not_candidates=int(host[-2]))
+                     not_candidates=int(host[-2]) - cut)
         if negatives is not None:
             stats.update(negatives=int(negatives), draw=int(draw))
+        if shortlist is not None:
+            stats.update(shortlist=int(shortlist), cut_by_shortlist=cut)
     out = dict(zip(metric_names(ks), host[:-3]))
     out['users_evaluated'] = int(host[-3])
     out['per_user'] = dict(users=sel_users, offsets=q_off, items=items, relevant=relevant, cnt=cnt, dcg=dcg, rank=rank,
                            pos=pos, index=index)
+    if shortlist is not None:
+        out['per_user']['place'] = place
     return out
+
+
+def shortlist_recall(dataset, heldout, ms=(50, 100, 200, 500), users=None, exclude_seen=True, item_mask=None,
+                     users_per_pass=65536, seed_min_rel=0, vote_min_rel=0, stats=None):
+    """How much of ``heldout`` a co-rating shortlist of each size M of ``ms`` keeps -- no model, no scoring: the number a user
+    needs to choose M.  Over the rating graph of ``dataset`` (a dataset or a ``recommend.GraphView``), for the held-out users
+    -- or those of them in ``users`` --, ``igmc_shortlist_places`` gives every held-out link its place in its user's full
+    vote order (one call per pass of ``users_per_pass`` users; the reductions run on the device, one host read at the end).
+    Over the RELEVANT held-out links that are candidates (``place >= 0``; the others are left out, as ``rank_eval`` leaves
+    them out), per M: ``micro`` = the share of links with ``place < M``, ``macro`` = the mean over the users that have such a
+    link of the user's own share.  Returns ``{M: {'micro': x, 'macro': y}}`` (NaN where no link counts); ``stats`` receives
+    ``users``, ``queries``, ``links`` (those that count), ``users_counted``, ``not_candidates`` and ``passes``.  A user
+    without a seeding entry is shortlisted its M lowest candidate ids, so its links count like any other."""
+    if not isinstance(heldout, HeldOut):
+        heldout = HeldOut.from_links(heldout)
+    ms = [int(m) for m in ms]
+    if not ms or min(ms) < 1 or max(ms) > 2 ** 31 - 1:
+        raise ValueError('ms: shortlist sizes in [1, 2^31)')
+    sel_users, q_off, items, relevant, _ = _select(heldout, users)
+    if sel_users.numel() < 1:
+        raise ValueError('none of the users has a held-out link')
+    dev = items.device
+    g = dataset.graph
+    mask = _item_mask(g, item_mask, dev)
+    bounds = q_off.tolist()
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    upp = max(1, int(users_per_pass))
+    place, passes = [], 0
+    for q0 in range(0, sel_users.numel(), upp):
+        m = min(upp, sel_users.numel() - q0)
+        a, b = bounds[q0], bounds[q0 + m]
+        place.append(engine.shortlist_places(g, sel_users[q0:q0 + m].contiguous(), mask, exclude_seen,
+                                             (q_off[q0:q0 + m + 1] - a).contiguous(), items[a:b].contiguous(), seed_min_rel,
+                                             vote_min_rel, err=err)[0])
+        passes += 1
+    place = torch.cat(place)
+    counts = (place >= 0) if relevant is None else ((place >= 0) & (relevant != 0))
+    owner = torch.repeat_interleave(torch.arange(sel_users.numel(), device=dev), q_off[1:] - q_off[:-1])
+    per_user = torch.zeros(sel_users.numel(), dtype=torch.float64, device=dev).index_add_(0, owner, counts.to(torch.float64))
+    have = per_user > 0
+    n, nu = counts.sum().to(torch.float64), have.sum().to(torch.float64)
+    out = []
+    for m in ms:
+        hit = (counts & (place < m)).to(torch.float64)
+        mine = torch.zeros_like(per_user).index_add_(0, owner, hit)
+        out += [hit.sum() / n, (mine[have] / per_user[have]).sum() / nu]
+    host = torch.stack(out + [n, nu, (place < 0).sum().to(torch.float64), err[0].to(torch.float64)]).tolist()
+    if int(host[-1]):
+        raise RuntimeError('shortlist_recall: igmc_shortlist_places reported err=%d' % int(host[-1]))
+    if stats is not None:
+        stats.update(users=sel_users.numel(), queries=items.numel(), links=int(host[-4]), users_counted=int(host[-3]),
+                     not_candidates=int(host[-2]), passes=passes)
+    return {m: dict(micro=host[2 * i], macro=host[2 * i + 1]) for i, m in enumerate(ms)}

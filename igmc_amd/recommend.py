@@ -29,6 +29,15 @@ A user with fewer than K other candidates gets them all.  SAMPLER POSITIONS appl
 sampled list is not its position in the full list: under a binding per-hop cap the sampled and the exhaustive score of the
 same pair may differ.
 
+SHORTLISTS (``shortlist=M``; ``igmc_amd/csrc/shortlist.hip``).  A retrieval stage in front of the scoring pass: per user only the
+``min(M, candidates)`` candidates with the most CO-RATING VOTES are listed and scored -- votes[j] = the sum, over the other users
+u', of (the items u and u' both rated at relation >= ``seed_min_rel``) x [u' rated j at relation >= ``vote_min_rel``]; order:
+votes descending, item id ascending (``include/igmc_hip.h`` states the definition).  ``igmc_candidates_count`` clamped to M gives
+the offsets, ``igmc_shortlist_fill`` writes the segments, item ascending like every other list.  Items nobody voted for fill a
+short list by ascending id, and A USER WITHOUT A SEEDING ENTRY (no rating at all, or none at or above ``seed_min_rel``) GETS ITS M
+LOWEST CANDIDATE IDS: the votes say nothing about such a user -- and neither does the model, whose subgraph for it is empty.
+M >= every user's candidate count reproduces the exhaustive lists byte for byte.  SAMPLER POSITIONS applies unchanged.
+
 ``link_y`` of a candidate list is zeros: the squared-error sums a scoring pass accumulates over candidates are MEANINGLESS and
 are dropped here.
 """
@@ -95,7 +104,9 @@ class CandidateLinks(LinkSource):
     The link buffers hold ``capacity`` entries at fixed addresses; ``len()`` is the number of links the last
     :meth:`refill` / :meth:`set_pairs` wrote.  After :meth:`refill`, ``users`` (int32 ``[nq]``) and ``offsets`` (int64
     ``[nq + 1]``) describe the per-user segments; after :meth:`set_pairs` they are ``None``.  After a refill with
-    ``negatives``, ``forced`` (uint8 ``[len()]``) is 1 where the link is a must item and 0 where it was drawn; else ``None``."""
+    ``negatives``, ``forced`` (uint8 ``[len()]``) is 1 where the link is a must item and 0 where it was drawn; else ``None``.
+    After a refill with ``shortlist``, ``votes`` (int32 ``[len()]``: the counts are below 2^31) holds every link's co-rating
+    votes; else ``None``."""
     dynamic = True          # subgraphs are extracted on the fly, under the sampling key of the pass
 
     def __init__(self, dataset, capacity):
@@ -109,23 +120,29 @@ class CandidateLinks(LinkSource):
         self.link_y = torch.zeros(capacity, dtype=torch.float32, device=dev)
         self.n = 0
         self.users, self.offsets, self.forced, self._forced = None, None, None, None
+        self.votes, self._votes = None, None
 
     # ---- constructors
     @classmethod
-    def for_users(cls, dataset, users, exclude_seen=True, item_mask=None, capacity=None, negatives=None, must=None, draw=0):
+    def for_users(cls, dataset, users, exclude_seen=True, item_mask=None, capacity=None, negatives=None, must=None, draw=0,
+                  shortlist=None, seed_min_rel=0, vote_min_rel=0):
         """The candidates of ``users`` (ids, host or device; duplicates allowed, each gets its own segment): every item --
         of ``item_mask`` (bool / uint8 ``[n_items]``) where given -- that the user has no entry for in the dataset's rating
         graph (``exclude_seen``), users in the order given, item id ascending.  ``capacity``: entries of the link buffers
-        (default: what these users need).  ``negatives`` / ``must`` / ``draw``: see :meth:`refill`."""
+        (default: what these users need).  ``negatives`` / ``must`` / ``draw`` / ``shortlist`` / ``seed_min_rel`` /
+        ``vote_min_rel``: see :meth:`refill`."""
+        _check_shortlist(shortlist, negatives)
         dev = dataset.link_y.device
         users = _dev_int32(users, dev, 'users')
         mask = _item_mask(dataset.graph, item_mask, dev)
         if capacity is None:
             counts, _ = engine.candidates_count(dataset.graph, users, mask, exclude_seen, negatives,
                                                 _must(must, users, dev, negatives))
+            if shortlist is not None:
+                counts = counts.clamp(max=int(shortlist))
             capacity = max(1, int(counts.sum().item()))
         self = cls(dataset, capacity)
-        self.refill(users, exclude_seen, mask, negatives, must, draw)
+        self.refill(users, exclude_seen, mask, negatives, must, draw, shortlist, seed_min_rel, vote_min_rel)
         return self
 
     @classmethod
@@ -136,13 +153,19 @@ class CandidateLinks(LinkSource):
         return self
 
     # ---- refilling in place
-    def refill(self, users, exclude_seen=True, item_mask=None, negatives=None, must=None, draw=0):
+    def refill(self, users, exclude_seen=True, item_mask=None, negatives=None, must=None, draw=0, shortlist=None,
+               seed_min_rel=0, vote_min_rel=0):
         """Enumerate the candidates of ``users`` into the link buffers (two launches, one host read: the total).
 
         ``negatives=K``: every user's ``K`` sampled candidates only (module docstring: SAMPLED NEGATIVES) under the source's
         ``seed`` and ``draw``, plus the user's must items -- ``must = (offsets int64 [nq + 1], items int32)``, device tensors:
         request ``q`` must list ``items[offsets[q]:offsets[q + 1]]`` --; ``forced`` then tells the two apart.
-        ``negatives=None``: ``igmc_candidates_count`` / ``_fill``, every candidate."""
+        ``negatives=None``: ``igmc_candidates_count`` / ``_fill``, every candidate.
+
+        ``shortlist=M`` (not together with ``negatives``: ``ValueError``): every user's ``min(M, candidates)`` candidates with
+        the most co-rating votes under the relation thresholds ``seed_min_rel`` / ``vote_min_rel`` (module docstring:
+        SHORTLISTS; a user without a seeding entry gets its M lowest candidate ids); ``votes`` then holds the links' votes."""
+        _check_shortlist(shortlist, negatives)
         dev = self.link_y.device
         users = _dev_int32(users, dev, 'users')
         if users.numel() < 1:
@@ -150,6 +173,8 @@ class CandidateLinks(LinkSource):
         mask = _item_mask(self.graph, item_mask, dev)
         must = _must(must, users, dev, negatives)
         counts, err = engine.candidates_count(self.graph, users, mask, exclude_seen, negatives, must)
+        if shortlist is not None:
+            counts = counts.clamp(max=int(shortlist))
         offsets = torch.zeros(users.numel() + 1, dtype=torch.int64, device=dev)
         torch.cumsum(counts, 0, out=offsets[1:])
         total = int(offsets[-1].item())
@@ -157,13 +182,20 @@ class CandidateLinks(LinkSource):
             raise ValueError('%d candidates do not fit the link buffers (capacity %d)' % (total, self.capacity))
         if negatives is not None and self._forced is None:
             self._forced = torch.zeros(self.capacity, dtype=torch.uint8, device=dev)
-        engine.candidates_fill(self.graph, users, mask, exclude_seen, offsets, self.link_u, self.link_v, err, negatives, must,
-                               self.seed, draw, self._forced)
+        if shortlist is not None:
+            if self._votes is None:
+                self._votes = torch.zeros(self.capacity, dtype=torch.int32, device=dev)
+            engine.shortlist_fill(self.graph, users, mask, exclude_seen, int(shortlist), offsets, self.link_u, self.link_v, err,
+                                  self._votes, seed_min_rel, vote_min_rel)
+        else:
+            engine.candidates_fill(self.graph, users, mask, exclude_seen, offsets, self.link_u, self.link_v, err, negatives,
+                                   must, self.seed, draw, self._forced)
         e = int(err.item())
         if e:
             raise RuntimeError('candidate enumeration: %s (err=%d)' % ('; '.join(w for b, w in _ERRORS if e & b), e))
         self.n, self.users, self.offsets = total, users, offsets
         self.forced = None if negatives is None else self._forced[:total]
+        self.votes = None if shortlist is None else self._votes[:total]
         return self
 
     def set_pairs(self, u, v):
@@ -180,7 +212,7 @@ class CandidateLinks(LinkSource):
                                                                                          self.graph.n_items))
         self.link_u[:u.numel()].copy_(u)
         self.link_v[:v.numel()].copy_(v)
-        self.n, self.users, self.offsets, self.forced = u.numel(), None, None, None
+        self.n, self.users, self.offsets, self.forced, self.votes = u.numel(), None, None, None, None
         return self
 
     def __len__(self):
@@ -194,6 +226,16 @@ def _item_mask(graph, item_mask, dev):
     if m.dim() != 1 or m.numel() != graph.n_items:
         raise ValueError('item_mask: one entry per item (%d)' % graph.n_items)
     return (m != 0).to(device=dev, dtype=torch.uint8).contiguous()
+
+
+def _check_shortlist(shortlist, negatives):
+    if shortlist is None:
+        return
+    if negatives is not None:
+        raise ValueError('shortlist and negatives exclude one another: a sampled list is an evaluation protocol, a shortlist '
+                         'a retrieval stage')
+    if not 1 <= int(shortlist) <= _INT32_MAX:
+        raise ValueError('shortlist must be in [1, 2^31)')
 
 
 def _must(must, users, dev, negatives):
@@ -242,7 +284,7 @@ def top_n(cands, scores, n, geometry=0):
 def pass_plan(graph, n_users_requested, item_mask=None, users_per_pass=None, per_user=None):
     """``(users_per_pass, capacity)`` of :func:`recommend`: by default the largest number of users whose WORST-CASE candidate
     count (every item, or every item of the mask; with sampled negatives at most ``per_user`` = negatives + the longest must
-    list) stays within ``DEFAULT_CAPACITY`` -- at least one user, at most those requested --; positions stay below 2^31 in
+    list, with a shortlist ``per_user`` = its size) stays within ``DEFAULT_CAPACITY`` -- at least one user, at most those requested --; positions stay below 2^31 in
     every case."""
     worst = max(1, graph.n_items if item_mask is None else int((torch.as_tensor(item_mask) != 0).sum().item()))
     if per_user is not None:
@@ -257,7 +299,7 @@ def pass_plan(graph, n_users_requested, item_mask=None, users_per_pass=None, per
 
 
 def candidate_passes(model, dataset, users=None, batch_size=50, exclude_seen=True, item_mask=None, users_per_pass=None,
-                     negatives=None, must=None, draw=0):
+                     negatives=None, must=None, draw=0, shortlist=None, seed_min_rel=0, vote_min_rel=0):
     """The pass loop of :func:`recommend` and of ``rank_eval.rank_eval``: ``users`` (default: every user of the rating graph)
     in passes of ``users_per_pass`` (:func:`pass_plan`); a generator of ``(q0, cands, scores)`` -- the index of the pass's
     first user in ``users``, the ONE :class:`CandidateLinks` every pass refills (kept as ``dataset._recommend_links`` and
@@ -265,8 +307,10 @@ def candidate_passes(model, dataset, users=None, batch_size=50, exclude_seen=Tru
     (:func:`score_candidates`).  ``cands`` is refilled by the next pass: take what you need from it before asking for it.
     ``negatives`` / ``must`` / ``draw``: sampled lists (:meth:`CandidateLinks.refill`); ``must`` covers all of ``users`` and
     every pass gets its slice (one host read of the offsets), and the passes are planned for ``negatives`` + the longest must
-    list per user instead of every item."""
+    list per user instead of every item.  ``shortlist`` / ``seed_min_rel`` / ``vote_min_rel``: co-rating shortlists
+    (module docstring: SHORTLISTS); the passes are planned for ``min(shortlist, items)`` per user."""
     from . import train_eval
+    _check_shortlist(shortlist, negatives)
     if model.flat_parameters().device.type != train_eval.device.type:
         model.to(train_eval.device)
     dev = dataset.link_y.device
@@ -281,6 +325,8 @@ def candidate_passes(model, dataset, users=None, batch_size=50, exclude_seen=Tru
     if negatives is not None:
         bounds = None if must is None else must[0].tolist()
         per_user = int(negatives) + (max(b - a for a, b in zip(bounds[:-1], bounds[1:])) if bounds else 0)
+    if shortlist is not None:
+        per_user = int(shortlist)
     upp, capacity = pass_plan(g, nq, mask, users_per_pass, per_user)
     cands = kept(dataset, '_recommend_links', lambda c: c.capacity >= capacity, lambda: CandidateLinks(dataset, capacity))
     for q0 in range(0, nq, upp):
@@ -288,12 +334,12 @@ def candidate_passes(model, dataset, users=None, batch_size=50, exclude_seen=Tru
         if bounds is not None:
             m = min(upp, nq - q0)
             mine = ((must[0][q0:q0 + m + 1] - bounds[q0]).contiguous(), must[1][bounds[q0]:bounds[q0 + m]])
-        cands.refill(users[q0:q0 + upp], exclude_seen, mask, negatives, mine, draw)
+        cands.refill(users[q0:q0 + upp], exclude_seen, mask, negatives, mine, draw, shortlist, seed_min_rel, vote_min_rel)
         yield q0, cands, score_candidates(model, cands, batch_size)
 
 
 def recommend(model, dataset, users=None, n=10, batch_size=50, exclude_seen=True, item_mask=None, users_per_pass=None,
-              stats=None):
+              stats=None, shortlist=None, seed_min_rel=0, vote_min_rel=0):
     """Ranked top-``n`` items for ``users`` (default: every user of the rating graph) over the rating graph and with the
     extraction settings of ``dataset`` (normally the training set): ``(items int32 [nq, n], scores float32 [nq, n], counts
     int32 [nq])``, device tensors, rows in the order of ``users``, -1 / 0 behind a user's count.
@@ -305,9 +351,12 @@ def recommend(model, dataset, users=None, n=10, batch_size=50, exclude_seen=True
     candidate crosses to the host: one total per pass does.  Works for ``DGCNN_RS`` too (``score_links``' eager path).
 
     Where a per-hop cap binds, scores depend on ``users_per_pass`` (see the module docstring: SAMPLER POSITIONS).
-    ``stats``: a dict that receives ``users``, ``candidates`` and ``passes``."""
+    ``shortlist=M``: only every user's M candidates with the most co-rating votes are scored (module docstring: SHORTLISTS; a
+    user without a seeding entry gets its M lowest candidate ids); M >= every candidate count is the exhaustive result.
+    ``stats``: a dict that receives ``users``, ``candidates`` and ``passes`` -- and ``shortlist`` where one is given."""
     items, scores, counts, total, nq = [], [], [], 0, 0
-    for _, cands, R in candidate_passes(model, dataset, users, batch_size, exclude_seen, item_mask, users_per_pass):
+    for _, cands, R in candidate_passes(model, dataset, users, batch_size, exclude_seen, item_mask, users_per_pass,
+                                        shortlist=shortlist, seed_min_rel=seed_min_rel, vote_min_rel=vote_min_rel):
         total += len(cands)
         nq += cands.users.numel()
         i, s, c = top_n(cands, R, n)
@@ -316,4 +365,6 @@ def recommend(model, dataset, users=None, n=10, batch_size=50, exclude_seen=True
         counts.append(c)
     if stats is not None:
         stats.update(users=nq, candidates=total, passes=len(items))
+        if shortlist is not None:
+            stats.update(shortlist=int(shortlist))
     return torch.cat(items, 0), torch.cat(scores, 0), torch.cat(counts, 0)

@@ -471,6 +471,70 @@ int64_t igmc_select_segments_scratch_bytes(int ns, int num, int geometry);
 int igmc_select_segments(const float* d_keys, const int64_t* d_seg_off, int ns, int num, int32_t* d_idx_out, float* d_key_out,
                          int32_t* d_count, void* d_scratch, int64_t scratch_bytes, int geometry, void* stream);
 
+/* ---- Co-rating shortlists: a retrieval stage in front of the scoring pass (no reference counterpart: the reference has no
+ * recommendation path; by hand this is row u of (L L^T) L as scipy sparse products and one np.lexsort per user).
+ *
+ * RELATIONS.  rel(u, v) is the 0-based relation index of the entry (u, v): the graph's u_rel / v_rel arrays hold exactly it,
+ * i.e. h_rating - 1 of igmc_graph_create (h_rating is rating label + 1, 1..R; the arrays hold the label, 0..R-1), and it
+ * rises with the rating value as the loaders order class_values.
+ *
+ * THE DEFINITION.  Two thresholds seed_min_rel = s >= 0 and vote_min_rel = t >= 0 give the binary matrices
+ * L_s[u, v] = [the graph has an entry (u, v) and rel(u, v) >= s] and L_t alike; with s = t = 0 every rating counts, with a
+ * threshold above every relation the matrix is empty.  For request q, user u = d_users[q]:
+ *   w[u']    = #{ i : L_s[u, i] and L_s[u', i] } for u' != u, and w[u] = 0: the items both like.  The user itself never votes.
+ *   votes[j] = sum over u' of w[u'] * L_t[u', j]: row u of (L_s L_s^T with its diagonal zeroed) L_t, exact unsigned integers,
+ *              defined for EVERY item j, candidates or not.
+ *   C        = the candidates of igmc_candidates_fill under the same d_item_ok / exclude_seen.
+ *   THE VOTE ORDER over C: votes descending, then item id ascending -- np.lexsort((item, -votes)) over the items of C.
+ *   The shortlist of q = the first min(m, |C|) items of C in the vote order, 1 <= m < 2^31; its segment is WRITTEN ITEM
+ *   ASCENDING, like every candidate segment (igmc_rank_segments binary-searches it).
+ * Items without a vote are ordinary members of C: they fill a short list by ascending id, and a user with no seeding entry
+ * (an empty row, or no rating at or above s) gets the m lowest candidate ids.
+ * LIMIT.  votes[j] <= max_deg_u * max_deg_v (igmc_graph_info); both entry points refuse -- non-zero return, igmc_last_error,
+ * nothing launched -- a graph whose product reaches 2^31.
+ *
+ * igmc_shortlist_fill writes d_link_u[p] = u, d_link_v[p] = item (int32) and, where d_votes is given, d_votes[p] = votes[item]
+ * (uint32) for the p of [d_offsets[q], d_offsets[q + 1]).  There is no count entry: the segment's length is min(m, the count
+ * of igmc_candidates_count); the caller clamps those counts and forms d_offsets (int64[nq + 1], offsets[0] = 0, their
+ * inclusive prefix sums behind it).  capacity = entries of d_link_u / d_link_v / d_votes, in [1, 2^31): nothing is written
+ * at or past it.  d_err[0] (int32, zeroed by the caller, read after the launch), the bits of igmc_candidates_fill:
+ *   bit 0 = a segment reaches past capacity (its links there are missing);
+ *   bit 1 = a user id outside [0, n_users): its segment is empty and no row is read;
+ *   bit 2 = the offsets are not the prefix sums of the clamped counts.
+ * igmc_shortlist_places answers, for queries grouped by request -- request q owns the queries [d_q_off[q], d_q_off[q + 1]) of
+ * d_q_id (int32[n_query], any order, duplicates allowed; d_q_off int64[nq + 1], d_q_off[0] = 0, d_q_off[nq] = n_query,
+ * 0 <= n_query < 2^31: the convention of igmc_rank_segments) --, where each queried item stands in the FULL vote order of its
+ * user:
+ *   d_q_place[k] = the number of items of C before it in the vote order (int32), or -1 when it is not in C (an item the user
+ *                  has rated under exclude_seen, one d_item_ok leaves out, an id outside [0, n_items), a user id out of range);
+ *   d_q_votes[k] = votes[d_q_id[k]] (uint32; may be NULL), in C or not; 0 for an id outside [0, n_items) and for a user id out
+ *                  of range.
+ * "Item j is in the shortlist of size m" is 0 <= place < m.  d_err[0]: bit 0 = d_q_off is not 0 = q_off[0] <= q_off[1] <= ...
+ * <= q_off[nq] = n_query: the queries cannot be told apart and EVERY query gets -1 / 0; bit 1 = a user id outside
+ * [0, n_users).  Nothing is read outside the n_query queries or written outside d_q_place / d_q_votes, whatever d_q_off holds.
+ *
+ * Both: one workgroup per request, `grid` workgroups in all (0 = chosen: min(nq, 512); at most 65536; more than nq are not
+ * launched), each working through the requests q, q + grid, ...  The outputs are a function of the inputs alone -- every sum
+ * is an integer sum -- and do not depend on grid.  d_scratch: igmc_shortlist_scratch_bytes(g, nq, grid) bytes (-1 on bad
+ * arguments; 0 where both tables of a workgroup fit its LDS, d_scratch may then be NULL), 4-byte aligned, owned by the caller,
+ * its contents before and after the call meaningless: a row per workgroup for w (uint32[n_users], where it does not fit LDS)
+ * and the votes (uint32[n_items], for graphs of more than 16384 items).  Nothing is allocated; _fill is one launch, _places
+ * two, capturable.  Refusals: a null argument, nq < 1, m outside [1, 2^31), a negative threshold, capacity outside [1, 2^31),
+ * grid outside [0, 65536], scratch too small or misaligned, the LIMIT above.
+ * igmc_shortlist_plan_info: what a launch over (g, nq, grid) looks like -- [0] workgroups, [1] LDS bytes of a workgroup,
+ * [2] 1 = w in LDS, [3] 1 = the votes in LDS, [4] igmc_shortlist_scratch_bytes, [5] the largest n_users whose w fits LDS at
+ * this graph's item count. */
+int64_t igmc_shortlist_scratch_bytes(const igmc_graph* g, int nq, int grid);
+int igmc_shortlist_plan_info(const igmc_graph* g, int nq, int grid, int64_t out6[6]);
+int igmc_shortlist_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok /* may be NULL */,
+                        int exclude_seen, int seed_min_rel, int vote_min_rel, int64_t m, const int64_t* d_offsets,
+                        int32_t* d_link_u, int32_t* d_link_v, uint32_t* d_votes /* may be NULL */, int64_t capacity,
+                        int32_t* d_err, void* d_scratch, int64_t scratch_bytes, int grid, void* stream);
+int igmc_shortlist_places(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok /* may be NULL */,
+                          int exclude_seen, int seed_min_rel, int vote_min_rel, const int64_t* d_q_off, const int32_t* d_q_id,
+                          int64_t n_query, int32_t* d_q_place, uint32_t* d_q_votes /* may be NULL */, int32_t* d_err,
+                          void* d_scratch, int64_t scratch_bytes, int grid, void* stream);
+
 /* ---- Where given ids stand in their segments, and the ranking metrics' per-segment sums (no reference counterpart: the
  * reference judges rating regression only, by the test RMSE; by hand this is every candidate score pulled to the host and one
  * `np.lexsort` per user).
