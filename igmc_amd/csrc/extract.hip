@@ -114,7 +114,9 @@ __device__ uint32_t radix_select(const uint32_t* bm, int W, int k, uint64_t salt
 // bits: (1) histogram of the keys' top byte -> the byte b that holds the k-th smallest key and how many (r) of its keys are
 // wanted; (2) keep every key below b outright and park the keys OF b (cnt / 256 of them on average) in a short list, whose
 // r smallest are then found by counting -- each parked key against the others -- and set again.  A list that would not
-// fit (more than 256 keys in one byte of a hash: not seen; tests force it) goes through radix_select's four passes instead;
+// fit (more than 256 keys in one byte of a hash: never on the bundled datasets, whose fringes stay far below 65 536
+// candidates; beyond that a byte holds cnt / 256 > 256 keys on average -- the raters of a popular item on an ml_25m-sized
+// graph -- and tests/extract_wide_checks.py draws from 70 000 and 90 000) goes through radix_select's four passes instead;
 // the kept set is the same either way: the k smallest keys, which never tie (igmc_rng.h).
 __device__ void sample_fringe(uint32_t* bm, int W, int cnt, int k, uint64_t salt, int* hist, int* sm) {
   if (k >= cnt) return;
