@@ -124,6 +124,17 @@ def build_parser():
     p.add_argument('--explain-links', default=None, metavar='FILE',
                    help='--explain: the links to explain, lines "user item" (ids as recommendations_*.tsv prints them, "#" '
                         'comments)')
+    p.add_argument('--pair-epochs', type=int, default=None, metavar='E',
+                   help='after training (or after loading model_checkpoint{epochs}.pth under --no-train) and before any serving '
+                        'stage, fine-tune E epochs for RANKING on the training links: every link against an unseen item of its '
+                        'user drawn on the device, so that the observed one scores higher; appends to pair_log.txt, saves '
+                        'pair_checkpoint{E}.pth, and the serving stages of the same command use the tuned weights')
+    p.add_argument('--pair-checkpoint', type=int, default=None, metavar='E',
+                   help='serving stages load pair_checkpoint{E}.pth instead of model_checkpoint{epochs}.pth (no fine-tuning)')
+    p.add_argument('--pair-lr', type=float, default=None, metavar='LR', help='--pair-epochs: learning rate (default 0.1 x --lr)')
+    p.add_argument('--pair-mse-weight', type=float, default=None, metavar='A',
+                   help='--pair-epochs: weight of the positives\' squared error beside the pair term (default 1.0: the scores '
+                        'stay ratings; 0 = the plain pairwise objective)')
     p.add_argument('--rank-min-rating', type=float, default=None, metavar='X',
                    help='--rank-eval: only held-out links rated >= X are relevant (default: all of them)')
     p.add_argument('--ensemble', action='store_true', default=False)
@@ -176,6 +187,42 @@ def shortlist_flag_error(shortlist, min_rating, rank_negatives, serving):
     if not serving:
         return '--shortlist shortens the candidate lists of --recommend N / --rank-eval K[,K...]: give one of them'
     return None
+
+
+def pair_flag_error(pair_epochs, pair_checkpoint, pair_lr, pair_mse_weight, dgcnn_rs, world):
+    """The argument error of ``--pair-epochs`` / ``--pair-checkpoint`` / ``--pair-lr`` / ``--pair-mse-weight`` in this combination
+    of flags (``world``: the number of ranks of the job), or None."""
+    if pair_epochs is None:
+        if pair_lr is not None:
+            return '--pair-lr names the learning rate of --pair-epochs E: give E'
+        if pair_mse_weight is not None:
+            return '--pair-mse-weight names the squared-error weight of --pair-epochs E: give E'
+        if pair_checkpoint is not None and pair_checkpoint < 1:
+            return '--pair-checkpoint takes E >= 1'
+        return None
+    if pair_epochs < 1:
+        return '--pair-epochs takes E >= 1'
+    if pair_checkpoint is not None:
+        return '--pair-epochs and --pair-checkpoint exclude one another: fine-tune, or serve what a fine-tuning saved'
+    if dgcnn_rs:
+        return '--pair-epochs fine-tunes IGMC: not with --dgcnn-rs'
+    if world > 1:
+        return '--pair-epochs runs on one rank (this job has %d)' % world
+    if pair_lr is not None and not pair_lr > 0:
+        return '--pair-lr takes LR > 0'
+    if pair_mse_weight is not None and not pair_mse_weight >= 0:
+        return '--pair-mse-weight takes A >= 0'
+    return None
+
+
+def pair_checkpoint_path(res_dir, E):
+    """Where ``--pair-epochs E`` saves and ``--pair-checkpoint E`` loads: a state dict like ``model_checkpoint{N}.pth``."""
+    return os.path.join(res_dir, 'pair_checkpoint{}.pth'.format(E))
+
+
+def pair_log_line(info):
+    return 'Pair epoch {}, pair loss {:.6f}, mse {:.6f}, pair acc {:.6f}\n'.format(info['epoch'], info['pair_loss'], info['mse'],
+                                                                                  info['pair_acc'])
 
 
 def shortlist_min_rel(class_values, min_rating):
@@ -351,6 +398,10 @@ def main(argv=None):
         parser.error('--explain needs the links to explain: --explain-links FILE, or --recommend N for the recommended pairs')
     if args.explain_links and not args.explain > 0:
         parser.error('--explain-links names the links of --explain M: give M')
+    bad = pair_flag_error(args.pair_epochs, args.pair_checkpoint, args.pair_lr, args.pair_mse_weight, args.dgcnn_rs,
+                          int(os.environ.get('WORLD_SIZE', '1')))
+    if bad:
+        parser.error(bad)
     rank, world = parallel.init_from_env()
     torch.manual_seed(args.seed)
     if torch.cuda.is_available():
@@ -480,6 +531,28 @@ def main(argv=None):
                                      res_dir=args.res_dir)
     # only rank 0 writes checkpoints (inside `logger`): nobody may look for them before it is done
     parallel.barrier()
+
+    if args.pair_epochs:
+        # no reference counterpart: E epochs of pairwise fine-tuning on the training links (igmc_amd/pair_train.py); what
+        # follows -- the serving stages, the final test -- loads the tuned weights
+        from igmc_amd.pair_train import train_pairs
+        if args.no_train:
+            model.load_state_dict(torch.load(args.model_pos, map_location='cpu'))
+
+        def pair_logger(info):
+            with open(os.path.join(args.res_dir, 'pair_log.txt'), 'a') as f:
+                f.write(pair_log_line(info))
+
+        train_pairs(model, train_graphs, args.pair_epochs, args.batch_size,
+                    0.1 * args.lr if args.pair_lr is None else args.pair_lr,
+                    mse_weight=1.0 if args.pair_mse_weight is None else args.pair_mse_weight, ARR=args.ARR, logger=pair_logger)
+        args.model_pos = pair_checkpoint_path(args.res_dir, args.pair_epochs)
+        torch.save(model.state_dict(), args.model_pos)
+        print('Saved pair-tuned model states to {}'.format(os.path.basename(args.model_pos)))
+    elif args.pair_checkpoint is not None:
+        args.model_pos = pair_checkpoint_path(args.res_dir, args.pair_checkpoint)
+        if rank == 0:
+            print('Serving from {}'.format(os.path.basename(args.model_pos)))
 
     if args.recommend > 0 or args.rank_eval or args.explain > 0:
         # no reference counterpart: the checkpoint's N best unseen items per user over adj_train, with the training set's

@@ -7,6 +7,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -1382,6 +1383,50 @@ extern "C" int igmc_candidates_sample_fill(const igmc_graph* g, const int32_t* d
   a.forced = d_forced;
   igmc_launch_candidates(a, 1, 1, stream);
   HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// ------------------------------------------------------------------ pair training (pairs.hip)
+extern "C" int igmc_pair_negatives(const igmc_graph* g, const int32_t* d_pos_u, const int32_t* d_pos_v, int64_t n,
+                                   const uint8_t* d_item_ok, uint64_t seed, uint64_t epoch, int32_t* d_link_u,
+                                   int32_t* d_link_v, float* d_link_y, int32_t* d_err, void* stream) {
+  if (!g || !d_pos_u || !d_pos_v || !d_link_u || !d_link_v || !d_link_y || !d_err) IGMC_FAIL("null argument");
+  if (n < 1 || n >= ((int64_t)1 << 30)) IGMC_FAIL("n must be in [1, 2^30): the 2 n link positions are int32");
+  int tries = IGMC_PAIR_TRIES;
+  if (const char* e = getenv("IGMC_PAIR_TRIES")) tries = atoi(e);      // (test hook: the cyclic scan after few tries, or none)
+  tries = tries < 0 ? 0 : tries > (1 << 20) ? (1 << 20) : tries;
+  const PairArgs a = {g->d, d_pos_u, d_pos_v, n, d_item_ok, seed, epoch, tries, d_link_u, d_link_v, d_link_y, d_err};
+  igmc_launch_pair_negatives(a, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int igmc_pair_loss(const float* d_out, const float* d_y, int B, float mse_weight, float* d_gout, double* d_stats,
+                              void* stream) {
+  if (!d_out || !d_y || !d_gout || !d_stats) IGMC_FAIL("null argument");
+  if (B < 2 || (B & 1)) IGMC_FAIL("a pair batch holds an even number of links, at least two");
+  igmc_launch_pair_loss(d_out, d_y, B, mse_weight, d_gout, d_stats, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int igmc_pair_loss_grad(igmc_model* m, const float* d_params, const igmc_batch* b, int use_edge_flags,
+                                   const uint8_t* d_lin_mask, uint64_t seed, uint64_t step, float multiply_by, float ARR,
+                                   float mse_weight, float* d_out, float* d_gout, float* d_grad, double* d_stats,
+                                   void* stream) {
+  std::string why;
+  if (check_call(m, b, d_params && d_out && d_gout && d_grad && d_stats, &why)) IGMC_FAIL(why);
+  if (b->last_B & 1) IGMC_FAIL("a pair batch holds an even number of links: positives in the even slots, their negatives behind them");
+  const int B = b->last_B;
+  const StepPlan sp = begin_call(m, b, IGMC_CALL_CONV, stream);
+  ImgScope img(m, d_params);
+  igmc_launch_forward(m->d, b->d, sp, d_params, B, 1, use_edge_flags, d_lin_mask, seed, step, multiply_by, d_out, stream);
+  igmc_launch_pair_loss(d_out, b->d.y, B, mse_weight, d_gout, d_stats, stream);
+  igmc_launch_backward(m->d, b->d, sp, d_params, B, use_edge_flags, d_gout, 0, 0.f, multiply_by, 2.f, ARR, d_grad, stream);
+  igmc_launch_pair_arr(m->d.arr_part, ARR, d_stats, stream);
+  img.done_unchanged();
+  HIPCHECK(hipGetLastError());
+  end_call(m, b, 1, use_edge_flags);
   return 0;
 }
 static int segsel_split(int ns, int num, int geometry) {

@@ -119,6 +119,25 @@ void igmc_launch_candidates(const CandArgs& a, int fill, int sampled, void* stre
 int igmc_segsel_default_split(int ns);
 void igmc_launch_select_segments(const float* keys, const int64_t* seg_off, int ns, int num, int k, void* scratch,
                                  int32_t* idx_out, float* key_out, int32_t* count, void* stream);
+// pairs.hip: pair training -- one negative per positive link and epoch drawn into a link list of (positive, negative) slots, and
+// the pair loss of a batch of such slots with its gradient w.r.t. the outputs
+#define IGMC_PAIR_TRIES 256             // hashed candidates tried before the cyclic scan decides (IGMC_PAIR_TRIES: test hook)
+struct PairArgs {
+  GraphDev g;
+  const int32_t* pos_u;
+  const int32_t* pos_v;
+  int64_t n;
+  const uint8_t* item_ok;       // may be null
+  uint64_t seed, epoch;
+  int tries;
+  int32_t* link_u;              // [2n] each
+  int32_t* link_v;
+  float* link_y;
+  int32_t* err;
+};
+void igmc_launch_pair_negatives(const PairArgs& a, void* stream);
+void igmc_launch_pair_loss(const float* out, const float* y, int B, float mse_weight, float* gout, double* stats, void* stream);
+void igmc_launch_pair_arr(const float* arr_part, float ARR, double* stats, void* stream);
 // shortlist.hip: the co-rating shortlist of a set of users (igmc_hip.h states the definition) -- the segments themselves, or
 // the places of given items in the full vote order
 #define IGMC_SHORT_TILE_ITEMS IGMC_CAND_TILE_ITEMS      // items of the LDS vote table (uint32 each, 64 KB): every bundled dataset

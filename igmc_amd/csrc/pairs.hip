@@ -1,0 +1,143 @@
+// pairs.hip -- pair training (no reference counterpart: the reference trains on observed links with MSE alone; by hand a ranking
+// objective there is a host loop drawing an unseen item per link and an autograd loss over the two scores).
+//
+// THE NEGATIVE of positive k = (u, i) of a pair list (igmc_hip.h states it for callers): with c_t = igmc_pair_candidate(
+// igmc_pair_salt(seed, epoch, k), t, n_items), the c_t of the smallest t < T that is not in the user's row and passes item_ok;
+// where none of the T tries qualifies, the first qualifying item of c_0, c_0 + 1, .., n_items - 1, 0, .., c_0 - 1; where no
+// item qualifies the pair is void.  Keyed by the positive's position in the list: no shuffle or batch size changes a draw.
+//
+// k_pair_negatives  one WAVE per positive (grid-stride), no workgroup barrier: lane t holds try 64 r + t of round r; the user's
+//                   row -- sorted by (relation, item), so not searchable by id -- goes through a 64-entry LDS stage of the wave,
+//                   chunk after chunk, and every lane compares its candidate with the 64 staged entries (LDS broadcast reads,
+//                   four entries a read); the first qualifying lane is a ballot + ffs.  A row has no size limit and there is
+//                   no second path.  The cyclic scan takes 64 consecutive items a step against the same row walk.
+// k_pair_loss       one workgroup over a batch whose even slots are positives and odd slots their negatives: every pair in
+//                   float64, the sums by a strided loop and a fixed LDS tree -- the same bits on every run.
+// Plain vector stores only (error word: a vector atomic OR, reached on errors only).
+#include "launch.h"
+
+#define PAIR_GRID_MAX 2048      // workgroups of the sampler at most: four positives each, the rest by the grid stride
+
+__global__ __launch_bounds__(IGMC_BLOCK) void k_pair_negatives(PairArgs a) {
+  __shared__ __attribute__((aligned(16))) int32_t stage[IGMC_BLOCK / 64][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = IGMC_BLOCK >> 6;
+  int32_t* st = stage[wave];
+  const uint32_t n_items = (uint32_t)a.g.n_items;
+  for (int64_t k = (int64_t)blockIdx.x * nwave + wave; k < a.n; k += (int64_t)gridDim.x * nwave) {
+    const int u = a.pos_u[k], i = a.pos_v[k];
+    if (u < 0 || u >= a.g.n_users || i < 0 || i >= a.g.n_items) {      // (uniform over the wave) no row is read: a void pair
+      if (lane == 0) {
+        a.link_u[2 * k] = a.link_u[2 * k + 1] = u;
+        a.link_v[2 * k] = a.link_v[2 * k + 1] = i;
+        a.link_y[2 * k + 1] = 0.f;
+        atomicOr(a.err, 1);
+      }
+      continue;
+    }
+    const int lo = a.g.u_ptr[u], hi = a.g.u_ptr[u + 1];
+    // live lanes whose item is not in the row; every lane of the wave walks the row (the stage is the wave's)
+    auto unseen = [&](int c, bool live) -> bool {
+      if (__ballot(live) == 0ull) return false;
+      bool seen = false;
+      for (int base = lo; base < hi; base += 64) {
+        st[lane] = lane < hi - base ? a.g.u_idx[base + lane] : -1;
+        IGMC_WAVE_SYNC();
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const int4 e = ((const int4*)st)[q];
+          seen |= (e.x == c) | (e.y == c) | (e.z == c) | (e.w == c);
+        }
+        IGMC_WAVE_SYNC();      // (the next chunk overwrites the stage)
+      }
+      return live && !seen;
+    };
+    const uint64_t salt = igmc_pair_salt(a.seed, a.epoch, (uint64_t)k);
+    int j = -1;
+    for (int t0 = 0; t0 < a.tries && j < 0; t0 += 64) {
+      const int t = t0 + lane;
+      const uint32_t c = igmc_pair_candidate(salt, (uint64_t)t, n_items);
+      const bool live = t < a.tries && (!a.item_ok || a.item_ok[c] != 0);
+      const unsigned long long m = __ballot(unseen((int)c, live));
+      if (m) j = __shfl((int)c, __ffsll((long long)m) - 1, 64);
+    }
+    if (j < 0) {      // the cyclic order from c_0: 64 consecutive items a step
+      const uint32_t c0 = igmc_pair_candidate(salt, 0, n_items);
+      for (uint32_t o0 = 0; o0 < n_items && j < 0; o0 += 64) {
+        const uint32_t o = o0 + lane;
+        uint32_t c = c0 + o;
+        if (c >= n_items) c -= n_items;
+        const bool live = o < n_items && (!a.item_ok || a.item_ok[c] != 0);
+        const unsigned long long m = __ballot(unseen((int)c, live));
+        if (m) j = __shfl((int)c, __ffsll((long long)m) - 1, 64);
+      }
+    }
+    if (lane == 0) {
+      a.link_u[2 * k] = a.link_u[2 * k + 1] = u;
+      a.link_v[2 * k] = i;
+      a.link_v[2 * k + 1] = j >= 0 ? j : i;      // (a void pair: every slot stays an extractable link)
+      a.link_y[2 * k + 1] = j >= 0 ? 1.f : 0.f;
+      if (j < 0) atomicOr(a.err, 2);
+    }
+  }
+}
+
+// stats[0] = sum_ok softplus(-d), [1] = sum_ok (s_pos - y)^2, [2] = #{ok: d > 0}, [3] = P_ok;  gout: igmc_hip.h
+__global__ __launch_bounds__(IGMC_BLOCK) void k_pair_loss(const float* __restrict__ out, const float* __restrict__ y, int P,
+                                                          double A, float* __restrict__ gout, double* __restrict__ stats) {
+  __shared__ double sm[4][IGMC_BLOCK];
+  const int t = threadIdx.x;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int p = t; p < P; p += IGMC_BLOCK) {
+    if (y[2 * p + 1] != 0.f) {
+      const double sp = (double)out[2 * p], d = sp - (double)out[2 * p + 1], e = sp - (double)y[2 * p];
+      acc[0] += fmax(-d, 0.0) + log1p(exp(-fabs(d)));
+      acc[1] += e * e;
+      acc[2] += d > 0.0 ? 1.0 : 0.0;
+      acc[3] += 1.0;
+    }
+  }
+  for (int q = 0; q < 4; ++q) sm[q][t] = acc[q];
+  __syncthreads();
+  for (int h = IGMC_BLOCK / 2; h >= 1; h >>= 1) {
+    if (t < h)
+      for (int q = 0; q < 4; ++q) sm[q][t] += sm[q][t + h];
+    __syncthreads();
+  }
+  const double p_ok = sm[3][0];
+  if (t < 4) stats[t] = sm[t][0];
+  for (int p = t; p < P; p += IGMC_BLOCK) {
+    float gp = 0.f, gn = 0.f;
+    if (y[2 * p + 1] != 0.f) {
+      const double sp = (double)out[2 * p], d = sp - (double)out[2 * p + 1], e = sp - (double)y[2 * p];
+      const double sg = 1.0 / (1.0 + exp(d));
+      gp = (float)((-sg + 2.0 * A * e) / p_ok);
+      gn = (float)(sg / p_ok);
+    }
+    gout[2 * p] = gp;
+    gout[2 * p + 1] = gn;
+  }
+}
+
+// stats[4] = the ARR term of the step, from the per-layer sums the gradient kernel left (as k_loss forms it)
+__global__ void k_pair_arr(const float* __restrict__ arr_part, float ARR, double* __restrict__ stats) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const float reg = arr_part[0] + arr_part[1] + arr_part[2] + arr_part[3];
+    stats[4] = (double)(ARR * reg);
+  }
+}
+
+// ------------------------------------------------------------------ host
+void igmc_launch_pair_negatives(const PairArgs& a, void* stream) {
+  const int nwave = IGMC_BLOCK >> 6;
+  const int64_t blocks = (a.n + nwave - 1) / nwave;
+  IGMC_PLAUNCH("k_pair_negatives", k_pair_negatives, (int)(blocks < 1 ? 1 : blocks > PAIR_GRID_MAX ? PAIR_GRID_MAX : blocks),
+               IGMC_BLOCK, 0, stream, a);
+}
+
+void igmc_launch_pair_loss(const float* out, const float* y, int B, float mse_weight, float* gout, double* stats, void* stream) {
+  IGMC_PLAUNCH("k_pair_loss", k_pair_loss, 1, IGMC_BLOCK, 0, stream, out, y, B / 2, (double)mse_weight, gout, stats);
+}
+
+void igmc_launch_pair_arr(const float* arr_part, float ARR, double* stats, void* stream) {
+  IGMC_PLAUNCH("k_pair_arr", k_pair_arr, 1, 64, 0, stream, arr_part, ARR, stats);
+}

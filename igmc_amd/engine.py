@@ -360,6 +360,14 @@ class ModelWorkspace(object):
                       _p(lin_mask), int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), float(multiply_by),
                       float(ARR), float(grad_scale), float(arr_scale), _p(out), _p(grad), _p(loss), _p(stream))
 
+    def pair_loss_grad(self, params, batch, out, gout, grad, stats, use_edge_flags=False, lin_mask=None, seed=0, step=0,
+                       multiply_by=1.0, ARR=0.0, mse_weight=1.0, stream=None):
+        """One pair step's loss and gradient on a batch of (positive, negative) slots (``igmc_pair_loss_grad``): ``out`` /
+        ``gout`` float32 ``[B]``, ``grad`` the flat gradient, ``stats`` float64 ``[5]``."""
+        self.lib.call('igmc_pair_loss_grad', self.handle, _p(params), batch.handle, int(bool(use_edge_flags)), _p(lin_mask),
+                      int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), float(multiply_by), float(ARR), float(mse_weight),
+                      _p(out), _p(gout), _p(grad), _p(stats), _p(stream))
+
     def dense_path(self, batch, B):
         """True when forward / loss_grad / train_step on (batch arena, B) take the matrix-core subgraph kernel."""
         return bool(self.lib.igmc_model_dense_path(self.handle, batch.handle, int(B)))
@@ -525,6 +533,14 @@ def candidates_fill(graph, users, mask, exclude_seen, offsets, link_u, link_v, e
         args += (int(seed), int(draw))
         out += (_p(None if forced is None else forced.data_ptr()),)
     graph.lib.call(name + '_fill', *(args + out + (link_u.numel(), _p(err.data_ptr()), _p(st))))
+
+
+def pair_negatives(graph, pos_u, pos_v, n, mask, seed, epoch, link_u, link_v, link_y, err, stream=None):
+    """One negative per positive ``(pos_u[k], pos_v[k])``, ``k < n``, drawn under ``(seed, epoch, k)`` into the ``2 n`` slots of
+    ``link_u`` / ``link_v`` / ``link_y`` (``igmc_pair_negatives``; no reference counterpart).  Every argument but the scalars
+    is a device address (or None for ``mask``); ``err`` collects the error bits and is left to the caller."""
+    graph.lib.call('igmc_pair_negatives', graph.handle, _p(pos_u), _p(pos_v), int(n), _p(mask), int(seed) & (2 ** 64 - 1),
+                   int(epoch) & (2 ** 64 - 1), _p(link_u), _p(link_v), _p(link_y), _p(err), _p(stream))
 
 
 def _shortlist_scratch(graph, nq, grid, dev):

@@ -239,6 +239,29 @@ class IGMC(nn.Module):
         with torch.no_grad():
             return _IGMCFunction.forward(_NoCtx(), self, data, bool(self.training), *params)
 
+    def pair_loss_grad(self, data, ARR=0.0, mse_weight=1.0, lin_mask=None, stats=None, out=None, gout=None):
+        """One pair step's loss and gradient (``igmc_pair_loss_grad``; no reference counterpart) on a batch of a
+        ``pair_train.PairLinks`` source -- positives in the even slots, their negatives behind them --: softplus of the score
+        difference + ``mse_weight`` x the positives' squared error, over the valid pairs, + ARR over ``self.convs``; the gradient
+        lands in ``flat_grad()`` so that ``FlatAdam.step()`` applies.  Returns the 5-double device tensor ``stats`` [sum of pair
+        terms, sum of squared errors, ordered pairs, valid pairs, ARR term]."""
+        if data.num_graphs % 2:
+            raise ValueError('a pair batch holds an even number of links, got %d' % data.num_graphs)
+        ws = self._workspace(data)
+        st = torch.cuda.current_stream().cuda_stream
+        dev = self._flat.device
+        stats = stats if stats is not None else torch.zeros(5, dtype=torch.float64, device=dev)
+        out = out if out is not None else torch.empty(data.num_graphs, dtype=torch.float32, device=dev)
+        gout = gout if gout is not None else torch.empty(data.num_graphs, dtype=torch.float32, device=dev)
+        use_flags = self.adj_dropout > 0
+        self._step += 1
+        if use_flags:
+            data.arena.edge_dropout(self.adj_dropout, self.force_undirected, self.seed, self._step, st)
+        ws.pair_loss_grad(self._flat.data_ptr(), data.arena, out.data_ptr(), gout.data_ptr(), self.flat_grad().data_ptr(),
+                          stats.data_ptr(), use_edge_flags=use_flags, lin_mask=lin_mask, seed=self.seed, step=self._step,
+                          multiply_by=float(self.multiply_by), ARR=float(ARR), mse_weight=float(mse_weight), stream=st)
+        return stats
+
     def __repr__(self):
         return self.__class__.__name__
 
@@ -390,6 +413,9 @@ class DGCNN_RS(IGMC):
         out = torch.empty(data.num_graphs, dtype=torch.float32, device=self._flat.device)
         self.forward_into(data, out, training=bool(self.training))
         return out
+
+    def pair_loss_grad(self, *a, **k):
+        raise NotImplementedError('pair training is built for IGMC (centre-node readout), not for the sort-pool family')
 
     def fused_loss_grad(self, data, ARR=0.0, grad_scale=None, arr_scale=1.0, lin_mask=None, loss=None, out=None):
         """One step's loss and gradient (reference ``train_eval.py:158-175``): MSE + ARR over ``self.convs``; the

@@ -1,0 +1,179 @@
+"""Pair training: fine-tune a rating regressor for RANKING (no reference counterpart: the reference trains on observed links
+with MSE and never sees an unobserved (user, item) pair).
+
+Every training link (u, i) is paired, anew every epoch, with an item j the user has not rated, drawn on the device
+(``igmc_pair_negatives``), and the step's objective is that the observed link scores higher:
+
+    softplus(-(s(u, i) - s(u, j)))  +  mse_weight * (s(u, i) - rating)^2,   mean over the valid pairs,  + ARR
+
+``mse_weight = 1`` (the default) keeps the tuned model's scores ratings -- ``recommendations_*.tsv`` prints them and ``--explain``
+reports deltas in rating units --, ``mse_weight = 0`` is the plain BPR objective.  A step is eager: extraction, edge dropout,
+``igmc_pair_loss_grad`` (training forward, pair loss, backward of the generic sequence), ``FlatAdam.step``; nothing is read back
+inside an epoch.  The fused step of ``train_eval.train`` is not involved: its loss head forms ``out - y`` inside the launch that
+runs the backward, and a pair's gradient needs the partner's score first.
+
+* :class:`PairLinks`   the link list of (positive, negative) slots over a dataset's rating graph
+* :func:`train_pairs`  the loop
+* :func:`eval_pairs`   mean pair term / pair accuracy of a drawn list in evaluation mode
+"""
+import time
+
+import numpy as np
+import torch
+
+from . import engine, parallel
+from .links import LinkSource
+
+_INT32_MAX = 2 ** 31 - 1
+_M64 = (1 << 64) - 1
+
+
+class PairLinks(LinkSource):
+    """``2 n`` link positions over the rating graph of ``dataset``: position ``2 k`` is positive ``k`` with its rating as the
+    label, position ``2 k + 1`` its negative of the current draw (:meth:`redraw`) with the label 1, or 0 where the pair is
+    void -- the user has no unseen item; the slot then repeats the positive so that it stays extractable.
+
+    The positives are the dataset's own links, or ``(u, v, y)`` (host or device arrays: user ids, item ids, rating values).
+    Storage is allocated once.  Subgraphs are always extracted from the graph, under the sampling key of the epoch where the
+    dataset is dynamic -- a negative has no cached node sets --, and side features are gathered by node id from the
+    dataset's ``node_side()`` tables."""
+
+    def __init__(self, dataset, u=None, v=None, y=None):
+        self._configure_from(dataset)
+        self.dynamic = bool(getattr(dataset, 'dynamic', True))
+        dev = dataset.link_y.device
+        if u is None:
+            u, v, y = dataset.link_u[:len(dataset)], dataset.link_v[:len(dataset)], dataset.link_y[:len(dataset)]
+        to = lambda x, dt: torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).to(device=dev, dtype=dt).contiguous()
+        self.pos_u, self.pos_v, y = to(u, torch.int32), to(v, torch.int32), to(y, torch.float32)
+        n = self.pos_u.numel()
+        if not (self.pos_v.numel() == n and y.numel() == n and self.pos_u.dim() == 1):
+            raise ValueError('u, v and y: 1-D arrays of one length')
+        if not 1 <= n <= _INT32_MAX // 2:
+            raise ValueError('between 1 and 2^30 - 1 positives: the 2 n link positions are int32')
+        bad = (self.pos_u < 0) | (self.pos_u >= self.graph.n_users) | (self.pos_v < 0) | (self.pos_v >= self.graph.n_items)
+        if bool(bad.any().item()):
+            raise ValueError('a positive outside the rating graph (%d users x %d items)' % (self.graph.n_users,
+                                                                                            self.graph.n_items))
+        self.n_pairs = n
+        self.link_u = self.pos_u.repeat_interleave(2).contiguous()      # (valid links before the first draw: every pair void)
+        self.link_v = self.pos_v.repeat_interleave(2).contiguous()
+        self.link_y = torch.zeros(2 * n, dtype=torch.float32, device=dev)
+        self.link_y[0::2] = y
+        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.epoch = None
+
+    def redraw(self, epoch, item_mask=None, stream=None):
+        """The negatives of ``epoch`` into the odd positions (one launch, nothing read back): a function of (seed, epoch,
+        position of the positive) -- the same epoch twice gives the same bytes.  ``item_mask`` (bool / uint8 ``[n_items]``):
+        the items a negative may be.  ``err`` collects bit 1 where a pair is void."""
+        mask = None
+        if item_mask is not None:
+            mask = torch.as_tensor(np.asarray(item_mask) if not torch.is_tensor(item_mask) else item_mask)
+            if mask.dim() != 1 or mask.numel() != self.graph.n_items:
+                raise ValueError('item_mask: one entry per item (%d)' % self.graph.n_items)
+            mask = (mask != 0).to(device=self.link_y.device, dtype=torch.uint8).contiguous()
+        st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+        engine.pair_negatives(self.graph, self.pos_u.data_ptr(), self.pos_v.data_ptr(), self.n_pairs,
+                              None if mask is None else mask.data_ptr(), self.seed, int(epoch), self.link_u.data_ptr(),
+                              self.link_v.data_ptr(), self.link_y.data_ptr(), self.err.data_ptr(), st)
+        self._mask = mask          # (kept until the next draw: the launch reads it)
+        self.epoch = int(epoch)
+        return self
+
+    def epoch_positions(self, epoch):
+        """A permutation of the PAIRS under (seed, epoch), expanded to ``[2 p, 2 p + 1]``: device int32 ``[2 n]``; the two slots
+        of a pair stay adjacent, so every even-sized batch cut at an even offset holds whole pairs."""
+        gen = torch.Generator()
+        gen.manual_seed((self.seed * 0x9E3779B97F4A7C15 + int(epoch) * 7919 + 0x50414952) & (_M64 >> 1))
+        p = torch.randperm(self.n_pairs, generator=gen)
+        pos = torch.stack([2 * p, 2 * p + 1], 1).reshape(-1)
+        return pos.to(device=self.link_y.device, dtype=torch.int32)
+
+
+def _as_pairs(dataset):
+    return dataset if isinstance(dataset, PairLinks) else PairLinks(dataset)
+
+
+def _refuse(model):
+    from .models import DGCNN_RS, IGMC
+    if parallel.world_size() > 1:
+        raise RuntimeError('pair training runs on one rank: data-parallel pair steps are not built (world size %d)'
+                           % parallel.world_size())
+    if isinstance(model, DGCNN_RS) or not isinstance(model, IGMC):
+        raise NotImplementedError('pair training is built for IGMC (centre-node readout), not for %s' % type(model).__name__)
+
+
+def train_pairs(model, dataset, epochs, batch_size, lr, mse_weight=1.0, ARR=0.001, logger=None):
+    """Fine-tune ``model`` for ``epochs`` epochs on the pairs of ``dataset`` (a dataset: its own links are the positives; or a
+    :class:`PairLinks`).  ``batch_size`` counts subgraphs and is rounded down to even.  Per epoch: one draw of the negatives,
+    then eager steps with no host synchronisation; the statistics accumulate on the device and are read once.  Prints and
+    returns per epoch ``dict(epoch, pair_loss, mse, pair_acc, pairs, void, steps, seconds)``: the mean pair term, the positives'
+    mean squared error and ordered / valid pairs -- all over the epoch's valid pairs, under dropout, as the steps saw them --,
+    and the epoch's steps and wall-clock time.
+    ``logger(info)`` is called with each."""
+    from .train_eval import FlatAdam, _check_workspaces
+    _refuse(model)
+    B = int(batch_size) // 2 * 2
+    if B < 2:
+        raise ValueError('batch_size must be at least 2: a step holds whole pairs')
+    if int(epochs) < 1:
+        raise ValueError('epochs must be at least 1')
+    pairs = _as_pairs(dataset)
+    dev = pairs.link_y.device
+    model.to(dev).train()
+    opt = FlatAdam(model, lr=lr)
+    step_stats = torch.zeros(5, dtype=torch.float64, device=dev)
+    total = torch.zeros(5, dtype=torch.float64, device=dev)
+    out, gout = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev)
+    n = 2 * pairs.n_pairs
+    history = []
+    torch.cuda.synchronize()
+    for epoch in range(1, int(epochs) + 1):
+        t0 = time.perf_counter()
+        pairs.err.zero_()
+        pairs.redraw(epoch)
+        perm = pairs.epoch_positions(epoch)
+        total.zero_()
+        for first in range(0, n, B):
+            data = pairs.extract(perm, first, min(B, n - first), epoch=epoch, max_graphs=B)
+            model.pair_loss_grad(data, ARR=ARR, mse_weight=mse_weight, stats=step_stats, out=out, gout=gout)
+            total += step_stats
+            opt.step()
+        t, err = total.cpu().numpy(), int(pairs.err.item())      # (the epoch's one read)
+        _check_workspaces(model)
+        ok = max(t[3], 1.0)
+        info = dict(epoch=epoch, pair_loss=float(t[0] / ok), mse=float(t[1] / ok), pair_acc=float(t[2] / ok), pairs=int(t[3]),
+                    void=pairs.n_pairs - int(t[3]), steps=(n + B - 1) // B, seconds=time.perf_counter() - t0)
+        if err & 1:
+            raise RuntimeError('pair sampler: a positive outside the rating graph (err=%d)' % err)
+        print('Pair epoch {}, pair loss {:.6f}, mse {:.6f}, pair acc {:.6f}'.format(epoch, info['pair_loss'], info['mse'],
+                                                                                    info['pair_acc']))
+        history.append(info)
+        if logger is not None:
+            logger(info)
+    steps, seconds = sum(h['steps'] for h in history), sum(h['seconds'] for h in history)
+    print('Pair training: {} steps of {} subgraphs in {:.3f} s, {:.1f} steps/s'.format(steps, B, seconds, steps / max(seconds, 1e-9)))
+    return history
+
+
+def eval_pairs(model, pairs, batch_size=50):
+    """``(mean pair term, pair accuracy)`` of the list as drawn (:meth:`PairLinks.redraw`), scored in evaluation mode -- no
+    dropout -- in the list's own order; over the valid pairs.  The scores come from the model's forward; the two means over a
+    list's worth of numbers are formed in float64."""
+    _refuse(model)
+    B = int(batch_size) // 2 * 2
+    was_training = model.training
+    model.eval()
+    n = 2 * pairs.n_pairs
+    scores = torch.empty(n, dtype=torch.float32, device=pairs.link_y.device)
+    with torch.no_grad():
+        for first in range(0, n, B):
+            data = pairs.extract(None, first, min(B, n - first), epoch=pairs.epoch or 0, max_graphs=B)
+            scores[first:first + data.num_graphs] = model(data)
+    model.train(was_training)
+    s = scores.double()
+    d, ok = s[0::2] - s[1::2], pairs.link_y[1::2] != 0
+    k = max(int(ok.sum().item()), 1)
+    term = torch.nn.functional.softplus(-d)[ok].sum().item() / k
+    return term, float((d[ok] > 0).sum().item()) / k

@@ -471,6 +471,48 @@ int64_t igmc_select_segments_scratch_bytes(int ns, int num, int geometry);
 int igmc_select_segments(const float* d_keys, const int64_t* d_seg_off, int ns, int num, int32_t* d_idx_out, float* d_key_out,
                          int32_t* d_count, void* d_scratch, int64_t scratch_bytes, int geometry, void* stream);
 
+/* ---- Pair training: a ranking objective on top of a regression checkpoint (no reference counterpart: the reference trains on
+ * observed links with MSE alone; by hand this is a host loop drawing an unseen item for every training link plus an autograd
+ * loss over the two scores).
+ *
+ * igmc_pair_negatives draws ONE negative per positive link and epoch.  d_pos_u / d_pos_v (int32[n], 1 <= n < 2^30) are the
+ * positives; for positive k = (u, i), with c_t = try t of igmc_rng.h's igmc_pair_candidate under the salt igmc_pair_salt of (seed,
+ * epoch, k), an item id in [0, n_items):
+ *   the negative j = c_t of the smallest t < T = 256 with no entry (u, c_t) in the graph and d_item_ok[c_t] != 0 (uint8[n_items];
+ *   NULL = every item); if none of the T tries qualifies, the first qualifying item of the cyclic order c_0, c_0 + 1, ..,
+ *   n_items - 1, 0, .., c_0 - 1; if no item qualifies the pair is VOID.
+ * The key is the positive's position k in the list: a link's negative depends neither on a shuffle nor on a batch size.  Left of
+ * the try list j is uniform over the qualifying items up to the multiply-shift's bias (n_items / 2^32); the cyclic scan is
+ * deterministic and reached with probability (share of non-qualifying items)^T.
+ * Written, all arrays [2 n]: d_link_u[2k] = d_link_u[2k+1] = u; d_link_v[2k] = i; d_link_v[2k+1] = j, or i for a void pair (every
+ * slot stays an extractable link); d_link_y[2k+1] = 1.0f, or 0.0f for a void pair -- the negative's label slot carries the
+ * pair's validity; d_link_y[2k] is NOT written: the caller keeps the positive's rating there.
+ * d_err[0] (int32, zeroed by the caller, read after the launch): bit 0 = a user or item id of a positive outside the graph --
+ * that pair is void (ids written as given, label 0) and no row is read; bit 1 = at least one pair void for lack of an unseen
+ * item.  One wave per positive over a grid-stride loop; one launch, nothing allocated, capturable.
+ *
+ * igmc_pair_loss_grad is one pair step's loss and gradient on an extracted batch whose EVEN slots are positives and whose ODD
+ * slots are their negatives (an odd batch size is refused): exactly igmc_model_forward(training = 1), the pair loss kernel,
+ * the backward of igmc_model_backward with the ARR coefficient -- for every arena those calls serve.  With s = d_out, y_p =
+ * the arena's label of slot 2p, ok_p = (label of slot 2p+1 != 0), d_p = s[2p] - s[2p+1], P_ok = #ok, A = mse_weight:
+ *   pair term  l_p = softplus(-d_p) = max(-d_p, 0) + log1p(exp(-|d_p|))                                     (ok_p only)
+ *   loss       L   = (sum_ok l_p + A * sum_ok (s[2p] - y_p)^2) / max(P_ok, 1) + ARR * sum_l sum_r ||W_l[r+1] - W_l[r]||^2
+ *   d_gout[2p] = (-1 / (1 + exp(d_p)) + 2 A (s[2p] - y_p)) / P_ok    d_gout[2p+1] = (1 / (1 + exp(d_p))) / P_ok    (0, 0: void)
+ *   d_stats (double[5]) = sum_ok l_p, sum_ok (s[2p] - y_p)^2, #{ok: d_p > 0}, P_ok, the ARR term (coefficient included)
+ * every pair evaluated in float64, d_gout its float32 rounding, the sums in a fixed order: the same bits on every run.  A = 0
+ * is the plain BPR objective; A = 1 keeps the scores ratings.  d_grad (flat, the layout of the parameters) is overwritten
+ * with dL/dparams; d_out[B], d_gout[B] and d_stats are overwritten.  Asynchronous on `stream`.
+ * igmc_pair_loss is the middle launch alone, on scores and labels the caller holds (d_out / d_y float[B], B even and >= 2):
+ * d_gout[0..B) and d_stats[0..4) as above; d_stats[4] is not written. */
+int igmc_pair_negatives(const igmc_graph* g, const int32_t* d_pos_u, const int32_t* d_pos_v, int64_t n,
+                        const uint8_t* d_item_ok /* may be NULL */, uint64_t seed, uint64_t epoch, int32_t* d_link_u,
+                        int32_t* d_link_v, float* d_link_y, int32_t* d_err, void* stream);
+int igmc_pair_loss(const float* d_out, const float* d_y, int B, float mse_weight /* A */, float* d_gout, double* d_stats,
+                   void* stream);
+int igmc_pair_loss_grad(igmc_model* m, const float* d_params, const igmc_batch* b, int use_edge_flags,
+                        const uint8_t* d_lin_mask, uint64_t seed, uint64_t step, float multiply_by, float ARR,
+                        float mse_weight /* A */, float* d_out, float* d_gout, float* d_grad, double* d_stats, void* stream);
+
 /* ---- Co-rating shortlists: a retrieval stage in front of the scoring pass (no reference counterpart: the reference has no
  * recommendation path; by hand this is row u of (L L^T) L as scipy sparse products and one np.lexsort per user).
  *

@@ -55,6 +55,21 @@ IGMC_HD uint64_t igmc_negative_salt(uint64_t seed, uint64_t draw, uint64_t user)
   return s;
 }
 
+/* salt for the negative of one (dataset seed, epoch, positive link) of pair training: `pos` is the positive's position in the
+ * pair list, not its place in a batch, so a link's negative does not depend on the shuffle or on the batch size */
+IGMC_HD uint64_t igmc_pair_salt(uint64_t seed, uint64_t epoch, uint64_t pos) {
+  uint64_t s = igmc_splitmix64(seed ^ 0x50414952ull);
+  s = igmc_splitmix64(s ^ epoch);
+  s = igmc_splitmix64(s ^ pos);
+  return s;
+}
+
+/* try t of a pair's negative: an item id in [0, n_items) by multiply-shift of 32 hashed bits -- no division; an item is hit by
+ * floor or ceil of 2^32 / n_items of the 2^32 words, so the bias of any item's probability is at most n_items / 2^32 relative */
+IGMC_HD uint32_t igmc_pair_candidate(uint64_t salt, uint64_t t, uint32_t n_items) {
+  return (uint32_t)(((igmc_splitmix64(salt ^ t) >> 32) * (uint64_t)n_items) >> 32);
+}
+
 /* bijective in `id` for fixed salt */
 IGMC_HD uint32_t igmc_sample_key(uint64_t salt, uint32_t id) {
   return igmc_fmix32(igmc_fmix32(id + (uint32_t)salt) ^ (uint32_t)(salt >> 32));
