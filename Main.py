@@ -135,6 +135,16 @@ def build_parser():
     p.add_argument('--pair-mse-weight', type=float, default=None, metavar='A',
                    help='--pair-epochs: weight of the positives\' squared error beside the pair term (default 1.0: the scores '
                         'stay ratings; 0 = the plain pairwise objective)')
+    p.add_argument('--pair-shortlist', type=int, default=None, metavar='M',
+                   help='--pair-epochs: HARD negatives -- a share of every epoch\'s pairs takes its negative from the user\'s M '
+                        'unseen items with the most co-rating votes over the training graph (the list --shortlist M serves '
+                        'from; built once on the device) instead of from the whole catalogue; the pair log then tells the two '
+                        'kinds apart.  Independent of --shortlist, which shortens the serving stages\' lists')
+    p.add_argument('--pair-hard-share', type=float, default=None, metavar='P',
+                   help='--pair-shortlist: the share of pairs whose negative is asked of the shortlist, in [0, 1] (default 0.5: '
+                        'a first value, not a tuned one)')
+    p.add_argument('--pair-shortlist-min-rating', type=float, default=None, metavar='X',
+                   help='--pair-shortlist: only ratings >= X count, as what a user liked and as a vote (default: every rating)')
     p.add_argument('--rank-min-rating', type=float, default=None, metavar='X',
                    help='--rank-eval: only held-out links rated >= X are relevant (default: all of them)')
     p.add_argument('--ensemble', action='store_true', default=False)
@@ -220,9 +230,35 @@ def pair_checkpoint_path(res_dir, E):
     return os.path.join(res_dir, 'pair_checkpoint{}.pth'.format(E))
 
 
+def pair_shortlist_flag_error(pair_epochs, pair_shortlist, pair_hard_share, pair_shortlist_min_rating):
+    """The argument error of ``--pair-shortlist`` / ``--pair-hard-share`` / ``--pair-shortlist-min-rating`` in this combination
+    of flags, or None."""
+    if pair_epochs is None:
+        for value, flag in ((pair_shortlist, '--pair-shortlist'), (pair_hard_share, '--pair-hard-share'),
+                            (pair_shortlist_min_rating, '--pair-shortlist-min-rating')):
+            if value is not None:
+                return '%s shapes the negatives of --pair-epochs E: give E' % flag
+        return None
+    if pair_shortlist is None:
+        if pair_hard_share is not None:
+            return '--pair-hard-share names the share of negatives drawn from --pair-shortlist M: give M'
+        if pair_shortlist_min_rating is not None:
+            return '--pair-shortlist-min-rating names the ratings that count for --pair-shortlist M: give M'
+        return None
+    if not 1 <= pair_shortlist < 2 ** 31:
+        return '--pair-shortlist takes M in [1, 2^31)'
+    if pair_hard_share is not None and not 0 <= pair_hard_share <= 1:
+        return '--pair-hard-share takes P in [0, 1]'
+    return None
+
+
 def pair_log_line(info):
-    return 'Pair epoch {}, pair loss {:.6f}, mse {:.6f}, pair acc {:.6f}\n'.format(info['epoch'], info['pair_loss'], info['mse'],
-                                                                                  info['pair_acc'])
+    line = 'Pair epoch {}, pair loss {:.6f}, mse {:.6f}, pair acc {:.6f}'.format(info['epoch'], info['pair_loss'], info['mse'],
+                                                                                info['pair_acc'])
+    if 'hard_pairs' in info:          # (--pair-shortlist: the share of valid pairs with a shortlist negative, accuracy per kind)
+        line += ', hard {:.6f}, pair acc hard {:.6f}, uniform {:.6f}'.format(info['hard_pairs'] / max(info['pairs'], 1),
+                                                                             info['pair_acc_hard'], info['pair_acc_uniform'])
+    return line + '\n'
 
 
 def shortlist_min_rel(class_values, min_rating):
@@ -402,6 +438,9 @@ def main(argv=None):
                           int(os.environ.get('WORLD_SIZE', '1')))
     if bad:
         parser.error(bad)
+    bad = pair_shortlist_flag_error(args.pair_epochs, args.pair_shortlist, args.pair_hard_share, args.pair_shortlist_min_rating)
+    if bad:
+        parser.error(bad)
     rank, world = parallel.init_from_env()
     torch.manual_seed(args.seed)
     if torch.cuda.is_available():
@@ -543,9 +582,15 @@ def main(argv=None):
             with open(os.path.join(args.res_dir, 'pair_log.txt'), 'a') as f:
                 f.write(pair_log_line(info))
 
+        hard = {}
+        if args.pair_shortlist is not None:          # (the table is over train_graphs' rating graph: before --new-ratings)
+            min_rel = shortlist_min_rel(class_values, args.pair_shortlist_min_rating)
+            hard = dict(shortlist=args.pair_shortlist, hard_share=0.5 if args.pair_hard_share is None else args.pair_hard_share,
+                        seed_min_rel=min_rel, vote_min_rel=min_rel)
         train_pairs(model, train_graphs, args.pair_epochs, args.batch_size,
                     0.1 * args.lr if args.pair_lr is None else args.pair_lr,
-                    mse_weight=1.0 if args.pair_mse_weight is None else args.pair_mse_weight, ARR=args.ARR, logger=pair_logger)
+                    mse_weight=1.0 if args.pair_mse_weight is None else args.pair_mse_weight, ARR=args.ARR, logger=pair_logger,
+                    **hard)
         args.model_pos = pair_checkpoint_path(args.res_dir, args.pair_epochs)
         torch.save(model.state_dict(), args.model_pos)
         print('Saved pair-tuned model states to {}'.format(os.path.basename(args.model_pos)))

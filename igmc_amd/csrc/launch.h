@@ -134,8 +134,14 @@ struct PairArgs {
   int32_t* link_v;
   float* link_y;
   int32_t* err;
+  const int64_t* sl_off;        // igmc_pair_negatives_shortlist alone: the per-user table, its entries, floor(share * 2^32)
+  const int32_t* sl_item;
+  int64_t sl_total;
+  uint64_t hard_thr;
 };
 void igmc_launch_pair_negatives(const PairArgs& a, void* stream);
+void igmc_launch_pair_negatives_shortlist(const PairArgs& a, void* stream);
+void igmc_launch_pair_kind_stats(const float* out, const float* y, int B, double* stats6, void* stream);
 void igmc_launch_pair_loss(const float* out, const float* y, int B, float mse_weight, float* gout, double* stats, void* stream);
 void igmc_launch_pair_arr(const float* arr_part, float ARR, double* stats, void* stream);
 // shortlist.hip: the co-rating shortlist of a set of users (igmc_hip.h states the definition) -- the segments themselves, or

@@ -11,13 +11,20 @@
 //                   chunk after chunk, and every lane compares its candidate with the 64 staged entries (LDS broadcast reads,
 //                   four entries a read); the first qualifying lane is a ballot + ffs.  A row has no size limit and there is
 //                   no second path.  The cyclic scan takes 64 consecutive items a step against the same row walk.
+//                   <HARD> (igmc_pair_negatives_shortlist) puts one question in front of the tries: where 32 hashed bits of the
+//                   salt decide so, ONE entry of the user's shortlist segment -- decision and pick uniform over the wave -- goes
+//                   through the same row walk as the only live candidate (lane 0); if it qualifies it is the negative (label
+//                   2), else the tries run as they always do.  <false> is the kernel igmc_pair_negatives has always launched.
 // k_pair_loss       one workgroup over a batch whose even slots are positives and odd slots their negatives: every pair in
 //                   float64, the sums by a strided loop and a fixed LDS tree -- the same bits on every run.
+// k_pair_kind_stats one workgroup over the same batch: count, ordered pairs and pair term per kind of negative (label 1 / 2), the
+//                   sums as k_pair_loss forms them.
 // Plain vector stores only (error word: a vector atomic OR, reached on errors only).
 #include "launch.h"
 
 #define PAIR_GRID_MAX 2048      // workgroups of the sampler at most: four positives each, the rest by the grid stride
 
+template <bool HARD>
 __global__ __launch_bounds__(IGMC_BLOCK) void k_pair_negatives(PairArgs a) {
   __shared__ __attribute__((aligned(16))) int32_t stage[IGMC_BLOCK / 64][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = IGMC_BLOCK >> 6;
@@ -53,6 +60,24 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_pair_negatives(PairArgs a) {
     };
     const uint64_t salt = igmc_pair_salt(a.seed, a.epoch, (uint64_t)k);
     int j = -1;
+    bool hard = false;
+    if constexpr (HARD) {
+      if (igmc_pair_hard(salt, a.hard_thr)) {      // (uniform over the wave: u and the salt are)
+        const int64_t sa = a.sl_off[u], sb = a.sl_off[u + 1];
+        if (sa < 0 || sb < sa || sb > a.sl_total) {      // not a segment of the table: nothing is read from it
+          if (lane == 0) atomicOr(a.err, 8);
+        } else if (sb > sa) {
+          const int c = a.sl_item[sa + (int64_t)igmc_pair_pick(salt, (uint32_t)(sb - sa))];
+          const bool live = lane == 0 && c >= 0 && c < a.g.n_items && (!a.item_ok || a.item_ok[c] != 0);
+          if (__ballot(unseen(c, live))) {
+            j = c;
+            hard = true;
+          } else if (lane == 0) {
+            atomicOr(a.err, 4);      // a stale table: the uniform draw decides
+          }
+        }
+      }
+    }
     for (int t0 = 0; t0 < a.tries && j < 0; t0 += 64) {
       const int t = t0 + lane;
       const uint32_t c = igmc_pair_candidate(salt, (uint64_t)t, n_items);
@@ -75,7 +100,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_pair_negatives(PairArgs a) {
       a.link_u[2 * k] = a.link_u[2 * k + 1] = u;
       a.link_v[2 * k] = i;
       a.link_v[2 * k + 1] = j >= 0 ? j : i;      // (a void pair: every slot stays an extractable link)
-      a.link_y[2 * k + 1] = j >= 0 ? 1.f : 0.f;
+      a.link_y[2 * k + 1] = j >= 0 ? (hard ? 2.f : 1.f) : 0.f;
       if (j < 0) atomicOr(a.err, 2);
     }
   }
@@ -118,6 +143,32 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_pair_loss(const float* __restric
   }
 }
 
+// stats6[0..3) = count, #{d > 0}, sum softplus(-d) over the pairs whose negative's label is 1; [3..6) the same for label 2
+__global__ __launch_bounds__(IGMC_BLOCK) void k_pair_kind_stats(const float* __restrict__ out, const float* __restrict__ y, int P,
+                                                                double* __restrict__ stats6) {
+  __shared__ double sm[6][IGMC_BLOCK];
+  const int t = threadIdx.x;
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int p = t; p < P; p += IGMC_BLOCK) {
+    const float l = y[2 * p + 1];
+    if (l == 1.f || l == 2.f) {
+      const int o = l == 2.f ? 3 : 0;
+      const double d = (double)out[2 * p] - (double)out[2 * p + 1];
+      acc[o] += 1.0;
+      acc[o + 1] += d > 0.0 ? 1.0 : 0.0;
+      acc[o + 2] += fmax(-d, 0.0) + log1p(exp(-fabs(d)));
+    }
+  }
+  for (int q = 0; q < 6; ++q) sm[q][t] = acc[q];
+  __syncthreads();
+  for (int h = IGMC_BLOCK / 2; h >= 1; h >>= 1) {
+    if (t < h)
+      for (int q = 0; q < 6; ++q) sm[q][t] += sm[q][t + h];
+    __syncthreads();
+  }
+  if (t < 6) stats6[t] = sm[t][0];
+}
+
 // stats[4] = the ARR term of the step, from the per-layer sums the gradient kernel left (as k_loss forms it)
 __global__ void k_pair_arr(const float* __restrict__ arr_part, float ARR, double* __restrict__ stats) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -127,11 +178,22 @@ __global__ void k_pair_arr(const float* __restrict__ arr_part, float ARR, double
 }
 
 // ------------------------------------------------------------------ host
-void igmc_launch_pair_negatives(const PairArgs& a, void* stream) {
+static int pair_grid(int64_t n) {
   const int nwave = IGMC_BLOCK >> 6;
-  const int64_t blocks = (a.n + nwave - 1) / nwave;
-  IGMC_PLAUNCH("k_pair_negatives", k_pair_negatives, (int)(blocks < 1 ? 1 : blocks > PAIR_GRID_MAX ? PAIR_GRID_MAX : blocks),
-               IGMC_BLOCK, 0, stream, a);
+  const int64_t blocks = (n + nwave - 1) / nwave;
+  return (int)(blocks < 1 ? 1 : blocks > PAIR_GRID_MAX ? PAIR_GRID_MAX : blocks);
+}
+
+void igmc_launch_pair_negatives(const PairArgs& a, void* stream) {
+  IGMC_PLAUNCH("k_pair_negatives", k_pair_negatives<false>, pair_grid(a.n), IGMC_BLOCK, 0, stream, a);
+}
+
+void igmc_launch_pair_negatives_shortlist(const PairArgs& a, void* stream) {
+  IGMC_PLAUNCH("k_pair_negatives_shortlist", k_pair_negatives<true>, pair_grid(a.n), IGMC_BLOCK, 0, stream, a);
+}
+
+void igmc_launch_pair_kind_stats(const float* out, const float* y, int B, double* stats6, void* stream) {
+  IGMC_PLAUNCH("k_pair_kind_stats", k_pair_kind_stats, 1, IGMC_BLOCK, 0, stream, out, y, B / 2, stats6);
 }
 
 void igmc_launch_pair_loss(const float* out, const float* y, int B, float mse_weight, float* gout, double* stats, void* stream) {

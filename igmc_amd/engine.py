@@ -543,6 +543,23 @@ def pair_negatives(graph, pos_u, pos_v, n, mask, seed, epoch, link_u, link_v, li
                    int(epoch) & (2 ** 64 - 1), _p(link_u), _p(link_v), _p(link_y), _p(err), _p(stream))
 
 
+def pair_negatives_shortlist(graph, pos_u, pos_v, n, mask, seed, epoch, sl_off, sl_item, sl_total, hard_share, link_u, link_v,
+                             link_y, err, stream=None):
+    """:func:`pair_negatives` with a share ``hard_share`` of the negatives asked of a per-user table (``sl_off`` int64
+    ``[n_users + 1]``, ``sl_item`` int32 ``[sl_total]``: every user's co-rating shortlist) -- ``igmc_pair_negatives_shortlist``;
+    such a negative's label is 2.  ``err`` gains bit 2 (a picked item did not qualify: a stale table) and bit 3 (offsets that
+    are no segment of the table)."""
+    graph.lib.call('igmc_pair_negatives_shortlist', graph.handle, _p(pos_u), _p(pos_v), int(n), _p(mask),
+                   int(seed) & (2 ** 64 - 1), int(epoch) & (2 ** 64 - 1), _p(sl_off), _p(sl_item), int(sl_total), float(hard_share),
+                   _p(link_u), _p(link_v), _p(link_y), _p(err), _p(stream))
+
+
+def pair_kind_stats(lib, out, y, B, stats6, stream=None):
+    """Count, ordered pairs and pair-term sum of a pair batch's uniform (label 1) and shortlist (label 2) negatives into the
+    device float64 ``[6]`` at ``stats6`` (``igmc_pair_kind_stats``); every argument but ``B`` is a device address."""
+    lib.call('igmc_pair_kind_stats', _p(out), _p(y), int(B), _p(stats6), _p(stream))
+
+
 def _shortlist_scratch(graph, nq, grid, dev):
     """The graph's shortlist scratch (kept on the ``Graph`` and grown on demand) as ``(pointer, bytes)``; ``(None, 0)`` where
     both tables of a workgroup fit its LDS."""

@@ -503,10 +503,44 @@ int igmc_select_segments(const float* d_keys, const int64_t* d_seg_off, int ns, 
  * is the plain BPR objective; A = 1 keeps the scores ratings.  d_grad (flat, the layout of the parameters) is overwritten
  * with dL/dparams; d_out[B], d_gout[B] and d_stats are overwritten.  Asynchronous on `stream`.
  * igmc_pair_loss is the middle launch alone, on scores and labels the caller holds (d_out / d_y float[B], B even and >= 2):
- * d_gout[0..B) and d_stats[0..4) as above; d_stats[4] is not written. */
+ * d_gout[0..B) and d_stats[0..4) as above; d_stats[4] is not written.
+ *
+ * igmc_pair_negatives_shortlist is igmc_pair_negatives with a share of HARD negatives: items of a per-user table, meant to be
+ * every user's co-rating shortlist (below) -- the unseen items the serving path would put in front of the ranker.  The table is
+ * indexed by USER ID: user u owns d_sl_item[d_sl_off[u] .. d_sl_off[u + 1]) (d_sl_off int64[n_users + 1], d_sl_item int32,
+ * sl_total entries, 0 <= sl_total < 2^31) -- the layout igmc_shortlist_fill leaves for d_users = 0 .. n_users - 1.  With
+ * thr = (uint64) floor(hard_share * 2^32), 0 <= hard_share <= 1, for positive k = (u, i) with both ids inside the graph, salt =
+ * the igmc_pair_salt of (seed, epoch, k) and H = igmc_splitmix64, in igmc_rng.h's words:
+ *   HARD-DECIDED  iff igmc_pair_hard: (H(salt ^ IGMC_PAIR_KEY_HARD) >> 32) < thr.  Share 0 never decides hard, share 1 always
+ *                 does.
+ *   SEGMENT       of a hard-decided pair: [a, b) = [d_sl_off[u], d_sl_off[u + 1]).  Usable iff 0 <= a <= b <= sl_total; else
+ *                 d_err bit 3, its length counts as 0 and nothing is read from it.  If b > a: x = igmc_pair_pick =
+ *                 ((H(salt ^ IGMC_PAIR_KEY_PICK) >> 32) * (b - a)) >> 32 and j = d_sl_item[a + x].
+ *   QUALIFYING    j qualifies iff 0 <= j < n_items, d_item_ok[j] != 0 (or d_item_ok is NULL) and the graph has no entry (u, j).
+ *                 Then j is the negative and d_link_y[2k+1] = 2.0f.  ONE pick, no retry: over a clean segment the pick is
+ *                 uniform up to the multiply-shift's bias ((b - a) / 2^32).
+ *   STALE TABLE   j does not qualify: d_err bit 2 ("the table does not belong to this graph or mask"), and the uniform draw
+ *                 decides.  An empty segment goes on to the uniform draw silently.
+ *   UNIFORM DRAW  not hard-decided, or no qualifying pick: EXACTLY the negative of igmc_pair_negatives for this (seed, epoch, k,
+ *                 mask) -- label 1.0f, or void (label 0, bit 1).  Ids out of range: bit 0, neither row nor segment is read.
+ * Both keys are >= 2^20, so neither word is a try's.  A negative is never an item the user has rated, whatever the table
+ * holds.  With hard_share == 0, or d_sl_off == NULL (allowed only with hard_share == 0; d_sl_item is then not read either),
+ * every output byte and the error word are igmc_pair_negatives'.  Refused: what igmc_pair_negatives refuses, a share outside
+ * [0, 1] or NaN, a NULL d_sl_off or d_sl_item with a share above 0, sl_total outside [0, 2^31).  One wave per positive, the
+ * decision and the pick uniform over it; the pick goes through the same row walk as a try, one live lane.
+ *
+ * igmc_pair_kind_stats tells a step's pairs apart by the kind of their negative (d_out / d_y float[B] as for igmc_pair_loss,
+ * B even and >= 2): d_stats6 (double[6]) = for the pairs with d_y[2p+1] == 1.0f their count, #{d_p > 0} and sum softplus(-d_p);
+ * then the same three for d_y[2p+1] == 2.0f.  Void pairs (and any other label) are counted nowhere.  One workgroup, float64,
+ * the sums in the fixed order of igmc_pair_loss: the same bits on every run. */
 int igmc_pair_negatives(const igmc_graph* g, const int32_t* d_pos_u, const int32_t* d_pos_v, int64_t n,
                         const uint8_t* d_item_ok /* may be NULL */, uint64_t seed, uint64_t epoch, int32_t* d_link_u,
                         int32_t* d_link_v, float* d_link_y, int32_t* d_err, void* stream);
+int igmc_pair_negatives_shortlist(const igmc_graph* g, const int32_t* d_pos_u, const int32_t* d_pos_v, int64_t n,
+                                  const uint8_t* d_item_ok /* may be NULL */, uint64_t seed, uint64_t epoch,
+                                  const int64_t* d_sl_off, const int32_t* d_sl_item, int64_t sl_total, double hard_share,
+                                  int32_t* d_link_u, int32_t* d_link_v, float* d_link_y, int32_t* d_err, void* stream);
+int igmc_pair_kind_stats(const float* d_out, const float* d_y, int B, double* d_stats6, void* stream);
 int igmc_pair_loss(const float* d_out, const float* d_y, int B, float mse_weight /* A */, float* d_gout, double* d_stats,
                    void* stream);
 int igmc_pair_loss_grad(igmc_model* m, const float* d_params, const igmc_batch* b, int use_edge_flags,

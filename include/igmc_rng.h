@@ -70,6 +70,22 @@ IGMC_HD uint32_t igmc_pair_candidate(uint64_t salt, uint64_t t, uint32_t n_items
   return (uint32_t)(((igmc_splitmix64(salt ^ t) >> 32) * (uint64_t)n_items) >> 32);
 }
 
+/* igmc_pair_negatives_shortlist: two more words of a pair's salt, under keys no try index can equal (tries stop below 2^20).
+ * KEY_HARD decides whether the negative is asked of the user's shortlist segment, KEY_PICK which of its entries. */
+#define IGMC_PAIR_KEY_HARD 0x4841524400000000ull /* "HARD" << 32 */
+#define IGMC_PAIR_KEY_PICK 0x5049434B00000000ull /* "PICK" << 32 */
+
+/* floor(hard_share * 2^32) for hard_share in [0, 1]: exact in double; 0 never decides hard, 2^32 always does */
+IGMC_HD uint64_t igmc_pair_hard_threshold(double hard_share) { return (uint64_t)(hard_share * 4294967296.0); }
+
+/* the pair asks the shortlist iff 32 hashed bits fall below the threshold */
+IGMC_HD int igmc_pair_hard(uint64_t salt, uint64_t thr) { return (igmc_splitmix64(salt ^ IGMC_PAIR_KEY_HARD) >> 32) < thr; }
+
+/* the entry of a segment of `len` entries (1 <= len < 2^31) a hard-decided pair picks: the multiply-shift of igmc_pair_candidate */
+IGMC_HD uint32_t igmc_pair_pick(uint64_t salt, uint32_t len) {
+  return (uint32_t)(((igmc_splitmix64(salt ^ IGMC_PAIR_KEY_PICK) >> 32) * (uint64_t)len) >> 32);
+}
+
 /* bijective in `id` for fixed salt */
 IGMC_HD uint32_t igmc_sample_key(uint64_t salt, uint32_t id) {
   return igmc_fmix32(igmc_fmix32(id + (uint32_t)salt) ^ (uint32_t)(salt >> 32));
