@@ -1,6 +1,7 @@
 // cand_tile.h -- THE definition of a user's candidates C (items in range, not in the user's row where exclude_seen, item_ok),
 // as LDS ballots over a tile of items: shared by candidates.hip (the exhaustive and the sampled lists) and shortlist.hip (the
-// co-rating shortlist), so that the three kinds of segment can never disagree about what a candidate is.
+// co-rating shortlist), so that the three kinds of segment can never disagree about what a candidate is -- nor, with the tile
+// walk (CandTiles) and the placement (cand_place_tile) below, about where it lands in its segment.
 #pragma once
 #include "launch.h"
 
@@ -71,4 +72,49 @@ __device__ __forceinline__ void cand_build_tile(const CandArgs& a, CandLds<SAMPL
     }
   }
   __syncthreads();
+}
+
+// every walk over C: body(tile0, nw) for the tiles one after the other, their ballots rebuilt unless the graph is one tile
+// (built by the first walk).  report: the first walk reports the must items out of range
+template <bool SAMPLED>
+struct CandTiles {
+  const CandArgs& a;
+  CandLds<SAMPLED>& s;
+  int lo, hi;              // the user's row, where seen items are excluded
+  int64_t mo, me;          // the request's must list
+  bool report;
+  bool built = false;
+  template <class Body>
+  __device__ __forceinline__ void operator()(Body&& body) {
+    const int n_items = a.g.n_items;
+    for (int tile0 = 0; tile0 < n_items; tile0 += CAND_TILE) {
+      const int left = n_items - tile0;
+      const int nw = left >= CAND_TILE ? CAND_TILE_WORDS : (left + 63) >> 6;
+      if (!(n_items <= CAND_TILE && built)) cand_build_tile(a, s, lo, hi, mo, me, tile0, nw, report && !built);
+      body(tile0, nw);
+    }
+    built = true;
+  }
+};
+
+// WHERE a candidate lands: the items of s.pool (the words a tile emits) go to base + done + their rank in the tile, the
+// word's share a block scan of the words' popcounts, a lane's the popcount of its word below it; store(pos, item, w, lane)
+// only for pos in [0, end) -- what has no place is reported by the caller, never written.  Returns the tile's total; pool and
+// woff may be rebuilt once it returns.
+template <bool SAMPLED, class Store>
+__device__ __forceinline__ int cand_place_tile(CandLds<SAMPLED>& s, int tile0, int nw, int64_t base, int done, int64_t end,
+                                               Store&& store) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nwave = IGMC_BLOCK >> 6;
+  int tile_total;
+  s.woff[t] = igmc_block_scan_excl(t < nw ? __popcll(s.pool[t]) : 0, &tile_total, s.smi);
+  __syncthreads();
+  for (int w = wave; w < nw; w += nwave) {
+    const unsigned long long m = s.pool[w];
+    if ((m >> lane) & 1ull) {
+      const int64_t pos = base + done + s.woff[w] + __popcll(m & ((1ull << lane) - 1ull));
+      if (pos >= 0 && pos < end) store(pos, tile0 + w * 64 + lane, w, lane);
+    }
+  }
+  __syncthreads();
+  return tile_total;
 }

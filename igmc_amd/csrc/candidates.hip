@@ -23,7 +23,8 @@
 //                  -- LDS histogram / list-cursor adds.
 //                  SAMPLED = false compiles the must bitmap, the forced ballots and every key out: the count is one walk,
 //                  the fill is one walk (the emission; it learns the segment's total there).
-//                  SAMPLED = true, the fill: the threshold T = the k-th smallest key of the pool: one histogram walk over the
+//                  SAMPLED = true, the fill: the threshold T = the k-th smallest key of the pool (kth_key.h's steps, shared with
+//                  the extraction's per-hop cap and the shortlist's vote order): one histogram walk over the
 //                  keys' top byte finds the byte b that holds it, the keys OF b (|N| / 256 on average) are parked in a short
 //                  list and the r-th of them is found by counting; a byte with more keys than the list holds goes through
 //                  the remaining three radix passes instead.  Keys are a bijection of the id (igmc_rng.h): exactly k keys
@@ -42,7 +43,8 @@
 // Plain vector stores only (error words: a vector atomic OR, reached on errors only).
 #include "launch.h"
 #include "select.h"
-#include "cand_tile.h"      // CAND_TILE, CandLds, cand_build_tile: the one definition of C
+#include "cand_tile.h"      // CAND_TILE, CandLds, cand_build_tile: the one definition of C; CandTiles, cand_place_tile
+#include "kth_key.h"        // the k-th smallest key of the pool
 
 #define SEG_LDS_WORDS 4096                         // selection words a workgroup stages (32 KB); also 64 lists of 64 to merge
 static_assert(IGMC_SEGSEL_MAX_SPLIT * IGMC_SELECT_MAX_NUM <= SEG_LDS_WORDS, "the merge stages every partial list");
@@ -51,8 +53,6 @@ template <bool FILL, bool SAMPLED>
 __global__ __launch_bounds__(IGMC_BLOCK) void k_candidates(CandArgs a) {
   __shared__ CandLds<SAMPLED> s;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nwave = IGMC_BLOCK >> 6;
-  const int n_items = a.g.n_items;
-  const bool one_tile = n_items <= CAND_TILE;
   for (int q = blockIdx.x; q < a.nq; q += gridDim.x) {
     const int u = a.users[q];
     if (u < 0 || u >= a.g.n_users) {        // (uniform over the workgroup) no row is read; the segment is empty
@@ -74,17 +74,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_candidates(CandArgs a) {
         }
       }
     }
-    // every walk: the tiles one after the other, their ballots rebuilt unless the graph is one tile (built by the first walk)
-    bool built = false;
-    auto tiles = [&](auto&& body) {
-      for (int tile0 = 0; tile0 < n_items; tile0 += CAND_TILE) {
-        const int left = n_items - tile0;
-        const int nw = left >= CAND_TILE ? CAND_TILE_WORDS : (left + 63) >> 6;
-        if (!(one_tile && built)) cand_build_tile(a, s, lo, hi, mo, me, tile0, nw, !built);
-        body(tile0, nw);
-      }
-      built = true;
-    };
+    CandTiles<SAMPLED> tiles{a, s, lo, hi, mo, me, true};        // every walk below
 
     // ---- walk 1: |N| and |M n C|.  Not for the exhaustive fill: its emission is its only walk
     int n_pool = 0, n_forc = 0;
@@ -111,75 +101,30 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_candidates(CandArgs a) {
       uint64_t salt = 0;
       bool by_key = false, all = true;
       if constexpr (SAMPLED) {
-        // keys of the pool items of a tile, a lane per item
-        auto keys = [&](int tile0, int nw, auto&& f) {
-          for (int w = wave; w < nw; w += nwave)
-            if ((s.pool[w] >> lane) & 1ull) f(igmc_sample_key(salt, (uint32_t)(tile0 + w * 64 + lane)));
+        // f(key) for the pool items, a lane per item (a key walk reads the pool alone, which a tile rebuild writes behind its
+        // own barriers: no barrier per tile)
+        auto walk = [&](auto&& f) {
+          tiles([&](int tile0, int nw) {
+            for (int w = wave; w < nw; w += nwave)
+              if ((s.pool[w] >> lane) & 1ull) f(igmc_sample_key(salt, (uint32_t)(tile0 + w * 64 + lane)));
+          });
         };
         by_key = kk > 0 && kk < n_pool;
         all = kk == n_pool;
         salt = igmc_negative_salt(a.seed, a.draw, (uint64_t)(uint32_t)u);
         if (by_key) {
-          s.hist[t] = 0;
-          __syncthreads();
-          tiles([&](int tile0, int nw) {
-            keys(tile0, nw, [&](uint32_t key) { atomicAdd(&s.hist[key >> 24], 1); });
-            __syncthreads();
-          });
-          int tot;
-          int c = s.hist[t];
-          int ex = igmc_block_scan_excl(c, &tot, s.smi);
-          if (c > 0 && ex < kk && kk <= ex + c) {
-            s.smi[8] = t;
-            s.smi[9] = kk - ex;
-            s.smi[10] = c;
-          }
-          if (t == 0) s.smi[11] = 0;
-          __syncthreads();
-          const uint32_t b = (uint32_t)s.smi[8];
-          int r = s.smi[9];
-          const int cb = s.smi[10];
-          __syncthreads();
-          if (cb <= IGMC_SAMPLE_PARK) {
-            tiles([&](int tile0, int nw) {
-              keys(tile0, nw, [&](uint32_t key) {
-                if ((key >> 24) == b) s.ckey[atomicAdd(&s.smi[11], 1)] = key;
-              });
-              __syncthreads();
+          const KthBin top = kth_pass(walk, 0u, 0u, 24, kk, s.hist, s.smi);
+          if (kth_parks(top.c)) {
+            walk([&](uint32_t key) {
+              if ((key >> 24) == top.b) s.ckey[atomicAdd(&s.smi[KTH_SM_CURSOR], 1)] = key;
             });
-            if (t < cb) {
-              const uint32_t mine = s.ckey[t];
-              int below = 0;
-              for (int j = 0; j < cb; ++j) below += s.ckey[j] < mine;
-              if (below == r - 1) s.smi[12] = (int)mine;        // (keys never tie: one thread)
-            }
             __syncthreads();
-            T = (uint32_t)s.smi[12];
+            if (t < top.c && kth_parked_below(s.ckey, top.c) == top.r - 1) s.smi[KTH_SM_T] = (int)s.ckey[t];        // (one thread)
+            __syncthreads();
+            T = (uint32_t)s.smi[KTH_SM_T];
           } else {
-            uint32_t prefix = b << 24, mask = 0xFF000000u;
-            for (int pass = 2; pass >= 0; --pass) {
-              const int shift = pass * 8;
-              s.hist[t] = 0;
-              __syncthreads();
-              tiles([&](int tile0, int nw) {
-                keys(tile0, nw, [&](uint32_t key) {
-                  if ((key & mask) == prefix) atomicAdd(&s.hist[(key >> shift) & 255u], 1);
-                });
-                __syncthreads();
-              });
-              c = s.hist[t];
-              ex = igmc_block_scan_excl(c, &tot, s.smi);
-              if (c > 0 && ex < r && r <= ex + c) {
-                s.smi[8] = t;
-                s.smi[9] = r - ex;
-              }
-              __syncthreads();
-              prefix |= ((uint32_t)s.smi[8]) << shift;
-              mask |= 0xFFu << shift;
-              r = s.smi[9];
-              __syncthreads();
-            }
-            T = prefix;
+            int r = top.r;
+            T = kth_radix(walk, top.b << 24, 0xFF000000u, 2, r, s.hist, s.smi);
           }
         }
       }
@@ -199,23 +144,12 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_candidates(CandArgs a) {
           }
           __syncthreads();
         }
-        int tile_total;
-        s.woff[t] = igmc_block_scan_excl(t < nw ? __popcll(s.pool[t]) : 0, &tile_total, s.smi);
-        __syncthreads();
-        for (int w = wave; w < nw; w += nwave) {
-          const unsigned long long m = s.pool[w];
-          if ((m >> lane) & 1ull) {
-            const int64_t pos = base + done + s.woff[w] + __popcll(m & ((1ull << lane) - 1ull));
-            if (pos >= 0 && pos < end) {        // (what has no place is reported below, never written)
-              a.link_u[pos] = u;
-              a.link_v[pos] = tile0 + w * 64 + lane;
-              if constexpr (SAMPLED)
-                if (a.forced) a.forced[pos] = (uint8_t)((s.forc[w] >> lane) & 1ull);
-            }
-          }
-        }
-        done += tile_total;
-        __syncthreads();
+        done += cand_place_tile(s, tile0, nw, base, done, end, [&](int64_t pos, int item, int w, int ln) {
+          a.link_u[pos] = u;
+          a.link_v[pos] = item;
+          if constexpr (SAMPLED)
+            if (a.forced) a.forced[pos] = (uint8_t)((s.forc[w] >> ln) & 1ull);
+        });
       });
       if constexpr (!SAMPLED) total = done;        // (the exhaustive fill took no count walk)
       // bit 0: the segment reaches past `capacity` (nothing was written there); bit 2: the offsets are not the counts'

@@ -24,6 +24,7 @@
 //           k_fill          (batch offsets + dst-sorted CSR of the batch, labels, PyG `batch` vector; S per link)
 //           k_edge_flags    (edge dropout keep flags, reference models.py:193-198)
 #include "launch.h"
+#include "kth_key.h"
 
 struct ExtractArgs {
   GraphDev g;
@@ -44,6 +45,23 @@ __device__ __forceinline__ void bm_clear(uint32_t* a, int W) {
   for (int w = threadIdx.x; w < W; w += IGMC_BLOCK) a[w] = 0u;
 }
 __device__ __forceinline__ bool bm_test(const uint32_t* a, int j) { return (a[j >> 5] >> (j & 31)) & 1u; }
+// f(id) for every set bit of bm, a word per thread at a time; FILTER: the bit stays only where f(id) holds
+template <bool FILTER, class F>
+__device__ __forceinline__ void bm_for_each(uint32_t* bm, int W, F&& f) {
+  for (int w = threadIdx.x; w < W; w += IGMC_BLOCK) {
+    uint32_t bits = bm[w], keep = 0u;
+    while (bits) {
+      const int bp = __ffs((int)bits) - 1;
+      bits &= bits - 1u;
+      if constexpr (FILTER) {
+        if (f(w * 32 + bp)) keep |= 1u << bp;
+      } else {
+        f(w * 32 + bp);
+      }
+    }
+    if constexpr (FILTER) bm[w] = keep;
+  }
+}
 __device__ __forceinline__ int bm_rank(const uint32_t* sel, const uint32_t* pre, int j) {
   return (int)pre[j >> 5] + __popc(sel[j >> 5] & ((1u << (j & 31)) - 1u));
 }
@@ -75,118 +93,46 @@ __device__ int bm_prefix(const uint32_t* bm, uint32_t* pre, int W, int* sm) {
   return running;
 }
 
-// k-th smallest (1-based) sampling key among the set bits of bm.  Keys are a bijection of
-// the id, so exactly k candidates have key <= the returned threshold.
-__device__ uint32_t radix_select(const uint32_t* bm, int W, int k, uint64_t salt, int* hist, int* sm) {
-  uint32_t prefix = 0u, mask = 0u;
-  int remaining = k;
-  for (int pass = 3; pass >= 0; --pass) {
-    const int shift = pass * 8;
-    hist[threadIdx.x] = 0;
-    __syncthreads();
-    for (int w = threadIdx.x; w < W; w += IGMC_BLOCK) {
-      uint32_t bits = bm[w];
-      while (bits) {
-        const int bp = __ffs((int)bits) - 1;
-        bits &= bits - 1u;
-        const uint32_t key = igmc_sample_key(salt, (uint32_t)(w * 32 + bp));
-        if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
-      }
-    }
-    __syncthreads();
-    const int c = hist[threadIdx.x];
-    int tot;
-    const int ex = igmc_block_scan_excl(c, &tot, sm);
-    if (c > 0 && ex < remaining && remaining <= ex + c) {
-      sm[8] = (int)threadIdx.x;
-      sm[9] = remaining - ex;
-    }
-    __syncthreads();
-    prefix |= ((uint32_t)sm[8]) << shift;
-    mask |= 0xFFu << shift;
-    remaining = sm[9];
-    __syncthreads();
-  }
-  return prefix;
-}
-
-// keep only the k candidates with the smallest keys (uniform k-subset, reference :222-229).  Two walks over the candidate
-// bits: (1) histogram of the keys' top byte -> the byte b that holds the k-th smallest key and how many (r) of its keys are
-// wanted; (2) keep every key below b outright and park the keys OF b (cnt / 256 of them on average) in a short list, whose
-// r smallest are then found by counting -- each parked key against the others -- and set again.  A list that would not
-// fit (more than 256 keys in one byte of a hash: never on the bundled datasets, whose fringes stay far below 65 536
-// candidates; beyond that a byte holds cnt / 256 > 256 keys on average -- the raters of a popular item on an ml_25m-sized
-// graph -- and tests/extract_wide_checks.py draws from 70 000 and 90 000) goes through radix_select's four passes instead;
-// the kept set is the same either way: the k smallest keys, which never tie (igmc_rng.h).
-__device__ void sample_fringe(uint32_t* bm, int W, int cnt, int k, uint64_t salt, int* hist, int* sm) {
+// keep only the k candidates with the smallest keys (uniform k-subset, reference :222-229), by the steps of kth_key.h.  Two
+// walks over the candidate bits: (1) histogram of the keys' top byte -> the byte b that holds the k-th smallest key and how
+// many (r) of its keys are wanted; (2) FUSED: keep every key below b outright and park the keys OF b (cnt / 256 of them on
+// average) in a short list, whose r smallest are then found by counting -- each parked key against the others -- and set
+// again.  A list that would not fit (more than 256 keys in one byte of a hash: never on the bundled datasets, whose fringes
+// stay far below 65 536 candidates; beyond that a byte holds cnt / 256 > 256 keys on average -- the raters of a popular item on
+// an ml_25m-sized graph -- and tests/extract_wide_checks.py draws from 70 000 and 90 000) settles the three bytes below b by
+// radix passes and keeps the keys up to the threshold instead; the kept set is the same either way: the k smallest keys,
+// which never tie (igmc_rng.h).
+__device__ __forceinline__ void sample_fringe(uint32_t* bm, int W, int cnt, int k, uint64_t salt, int* hist, int* sm) {
   if (k >= cnt) return;
   if (k <= 0) {
     bm_clear(bm, W);
     __syncthreads();
     return;
   }
-  hist[threadIdx.x] = 0;
-  __syncthreads();
-  for (int w = threadIdx.x; w < W; w += IGMC_BLOCK) {
-    uint32_t bits = bm[w];
-    while (bits) {
-      const int bp = __ffs((int)bits) - 1;
-      bits &= bits - 1u;
-      atomicAdd(&hist[igmc_sample_key(salt, (uint32_t)(w * 32 + bp)) >> 24], 1);
-    }
-  }
-  __syncthreads();
-  const int c = hist[threadIdx.x];
-  int tot;
-  const int ex = igmc_block_scan_excl(c, &tot, sm);
-  if (c > 0 && ex < k && k <= ex + c) {
-    sm[8] = (int)threadIdx.x;
-    sm[9] = k - ex;
-    sm[10] = c;
-  }
-  if (threadIdx.x == 0) sm[11] = 0;
-  __syncthreads();
-  const uint32_t b = (uint32_t)sm[8];
-  const int r = sm[9], cb = sm[10];
-  if (cb > IGMC_SAMPLE_PARK) {
-    __syncthreads();
-    const uint32_t T = radix_select(bm, W, k, salt, hist, sm);
-    for (int w = threadIdx.x; w < W; w += IGMC_BLOCK) {
-      uint32_t bits = bm[w], keep = 0u;
-      while (bits) {
-        const int bp = __ffs((int)bits) - 1;
-        bits &= bits - 1u;
-        if (igmc_sample_key(salt, (uint32_t)(w * 32 + bp)) <= T) keep |= 1u << bp;
-      }
-      bm[w] = keep;
-    }
+  auto keys = [&](auto&& f) { bm_for_each<false>(bm, W, [&](int id) { f(igmc_sample_key(salt, (uint32_t)id)); }); };
+  const KthBin top = kth_pass(keys, 0u, 0u, 24, k, hist, sm);
+  if (!kth_parks(top.c)) {
+    int r = top.r;
+    const uint32_t T = kth_radix(keys, top.b << 24, 0xFF000000u, 2, r, hist, sm);
+    bm_for_each<true>(bm, W, [&](int id) { return igmc_sample_key(salt, (uint32_t)id) <= T; });
     __syncthreads();
     return;
   }
-  uint32_t* ckey = (uint32_t*)hist;          // (every count was read before the scan's barriers)
+  uint32_t* ckey = (uint32_t*)hist;          // (kth_bin: every count has been read)
   int* cid = hist + IGMC_BLOCK;
-  for (int w = threadIdx.x; w < W; w += IGMC_BLOCK) {
-    uint32_t bits = bm[w], keep = 0u;
-    while (bits) {
-      const int bp = __ffs((int)bits) - 1;
-      bits &= bits - 1u;
-      const uint32_t key = igmc_sample_key(salt, (uint32_t)(w * 32 + bp));
-      if ((key >> 24) < b) keep |= 1u << bp;
-      else if ((key >> 24) == b) {
-        const int s = atomicAdd(&sm[11], 1);
-        ckey[s] = key;
-        cid[s] = w * 32 + bp;
-      }
+  bm_for_each<true>(bm, W, [&](int id) {
+    const uint32_t key = igmc_sample_key(salt, (uint32_t)id);
+    if ((key >> 24) == top.b) {
+      const int s = atomicAdd(&sm[KTH_SM_CURSOR], 1);
+      ckey[s] = key;
+      cid[s] = id;
     }
-    bm[w] = keep;
-  }
+    return (key >> 24) < top.b;
+  });
   __syncthreads();
-  if ((int)threadIdx.x < cb) {
-    const uint32_t mine = ckey[threadIdx.x];
-    int below = 0;
-    for (int j = 0; j < cb; ++j) below += ckey[j] < mine;
+  if ((int)threadIdx.x < top.c && kth_parked_below(ckey, top.c) < top.r) {
     const int id = cid[threadIdx.x];
-    if (below < r) atomicOr(&bm[id >> 5], 1u << (id & 31));
+    atomicOr(&bm[id >> 5], 1u << (id & 31));
   }
   __syncthreads();
 }

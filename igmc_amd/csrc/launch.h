@@ -29,10 +29,10 @@ void igmc_launch_gate(int64_t* ctrl, int q, int gk_min, long long delay_ticks, i
                       void* stream);
 void igmc_launch_fill_u8(uint8_t* p, int64_t n, uint8_t v, void* stream);
 int igmc_extract_prepare(size_t smem);
-// keys of the deciding byte that a k-th-key selection parks in its short list (extract.hip: sample_fringe; candidates.hip: the
-// sampled fill); more go through the radix passes
+// keys of the deciding byte that a k-th-key selection parks in its short list; more go through the radix passes.  Read in one
+// place: kth_key.h's kth_parks (extract.hip: sample_fringe; candidates.hip: the sampled fill)
 #ifdef IGMC_HIPEMU
-// (CPU emulation only: the tests lower the bound through the environment to drive the four-pass path)
+// (CPU emulation only: the tests lower the bound through the environment to drive the radix path)
 #include <stdlib.h>
 static inline int igmc_sample_park() { const char* e = getenv("IGMC_SAMPLE_PARK"); return e ? atoi(e) : IGMC_BLOCK; }
 #define IGMC_SAMPLE_PARK igmc_sample_park()

@@ -26,13 +26,13 @@
 //                  without a fill of n_users words.  The votes are zeroed per request (n_items words, what one selection walk
 //                  costs).
 //   selection      the threshold is the kk-th entry of the vote order over C, kk = min(m, |C|): four radix passes (byte
-//                  histograms in LDS) over key = ~votes of the pool items give the vote value V that holds it and r = how many
+//                  histograms in LDS: kth_key.h's kth_radix) over key = ~votes of the pool items give the vote value V that holds it and r = how many
 //                  items with exactly V votes are admitted (the lowest ids); kk == |C| admits everything and skips the passes.
 //                  (select.h's 64-bit word carries a FLOAT image in its high half and does not fit integer votes: the order
 //                  here is the pair (key, item id) itself -- the radix passes settle the key, the emission's running count of
 //                  ties the id.)
-//   emission       one walk in item order, the shape of k_candidates': ballots of "more than V votes" and of "exactly V",
-//                  a block scan of the tie words' popcounts admits the first r ties, a second scan places the words.
+//   emission       one walk in item order: ballots of "more than V votes" and of "exactly V", a block scan of the tie words'
+//                  popcounts admits the first r ties, k_candidates' own cand_place_tile places the words.
 //   PLACES         instead of selection + emission: for the request's queries, 256 at a time, place = #{i in C: votes[i] >
 //                  votes[j] or (votes[i] == votes[j] and i < j)}, counted per wave and summed by LDS integer adds; -1 where j is
 //                  not in C.
@@ -42,6 +42,7 @@
 // inputs alone, whatever the grid.  No float anywhere.  Plain vector loads and stores; the error word: a vector atomic OR.
 #include "launch.h"
 #include "cand_tile.h"
+#include "kth_key.h"
 
 static_assert(IGMC_SHORT_TILE_ITEMS == CAND_TILE, "the vote table and the candidate ballots cover the same tile");
 
@@ -77,7 +78,6 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_shortlist(ShortArgs a) {
   uint32_t* const lds_tab = reinterpret_cast<uint32_t*>(smem + sizeof(ShortLds));
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, nwave = IGMC_BLOCK >> 6;
   const int n_users = a.g.n_users, n_items = a.g.n_items;
-  const bool one_tile = n_items <= CAND_TILE;
   uint32_t* const row = a.scratch + (int64_t)blockIdx.x * a.row_words;
   uint32_t* votes;
   uint32_t* w;
@@ -135,18 +135,8 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_shortlist(ShortArgs a) {
     }
     __syncthreads();
 
-    // every walk over C: the tiles one after the other, their ballots rebuilt unless the graph is one tile
     const int lo = a.exclude_seen ? r0 : 0, hi = a.exclude_seen ? r1 : 0;
-    bool built = false;
-    auto tiles = [&](auto&& body) {
-      for (int tile0 = 0; tile0 < n_items; tile0 += CAND_TILE) {
-        const int left = n_items - tile0;
-        const int nw = left >= CAND_TILE ? CAND_TILE_WORDS : (left + 63) >> 6;
-        if (!(one_tile && built)) cand_build_tile(ca, s.c, lo, hi, 0, 0, tile0, nw, false);
-        body(tile0, nw);
-      }
-      built = true;
-    };
+    CandTiles<false> tiles{ca, s.c, lo, hi, 0, 0, false};        // every walk over C below
 
     if constexpr (PLACES) {
       int64_t qa = a.q_off[q], qb = a.q_off[q + 1];
@@ -200,32 +190,14 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_shortlist(ShortArgs a) {
       // ---- the threshold: T = the key (~votes) of the kk-th of the vote order, r = the items of that key admitted
       uint32_t T = 0u;
       int r = kk;
-      if (by_key) {
-        uint32_t mask = 0u;
-        for (int shift = 24; shift >= 0; shift -= 8) {
-          s.hist[t] = 0;
-          __syncthreads();
+      if (by_key) {        // (the walk reads the pool and the votes alone: no barrier per tile)
+        auto walk = [&](auto&& f) {
           tiles([&](int tile0, int nw) {
             for (int wd = wave; wd < nw; wd += nwave)
-              if ((s.c.pool[wd] >> lane) & 1ull) {
-                const uint32_t key = ~votes[tile0 + wd * 64 + lane];
-                if ((key & mask) == T) atomicAdd(&s.hist[(key >> shift) & 255u], 1);
-              }
-            __syncthreads();
+              if ((s.c.pool[wd] >> lane) & 1ull) f(~votes[tile0 + wd * 64 + lane]);
           });
-          int tot;
-          const int c = s.hist[t];
-          const int ex = igmc_block_scan_excl(c, &tot, s.c.smi);
-          if (c > 0 && ex < r && r <= ex + c) {
-            s.c.smi[8] = t;
-            s.c.smi[9] = r - ex;
-          }
-          __syncthreads();
-          T |= ((uint32_t)s.c.smi[8]) << shift;
-          mask |= 0xFFu << shift;
-          r = s.c.smi[9];
-          __syncthreads();
-        }
+        };
+        T = kth_radix(walk, 0u, 0u, 3, r, s.hist, s.c.smi);
       }
       // ---- the emission
       const int64_t base = a.off[q];
@@ -254,24 +226,12 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_shortlist(ShortArgs a) {
           if (lane == 0) s.c.pool[wd] |= ma;
         }
         __syncthreads();
-        int tile_total;
-        s.c.woff[t] = igmc_block_scan_excl(t < nw ? __popcll(s.c.pool[t]) : 0, &tile_total, s.c.smi);
-        __syncthreads();
-        for (int wd = wave; wd < nw; wd += nwave) {
-          const unsigned long long m = s.c.pool[wd];
-          if ((m >> lane) & 1ull) {
-            const int item = tile0 + wd * 64 + lane;
-            const int64_t pos = base + done + s.c.woff[wd] + __popcll(m & ((1ull << lane) - 1ull));
-            if (pos >= 0 && pos < end) {        // (what has no place is reported below, never written)
-              a.link_u[pos] = u;
-              a.link_v[pos] = item;
-              if (a.votes_out) a.votes_out[pos] = votes[item];
-            }
-          }
-        }
-        done += tile_total;
+        done += cand_place_tile(s.c, tile0, nw, base, done, end, [&](int64_t pos, int item, int, int) {
+          a.link_u[pos] = u;
+          a.link_v[pos] = item;
+          if (a.votes_out) a.votes_out[pos] = votes[item];
+        });
         tdone += tie_total;
-        __syncthreads();
       });
       // bit 0: the segment reaches past `capacity` (nothing was written there); bit 2: the offsets are not the clamped counts'
       const int bad = ((base + kk > a.capacity) ? 1 : 0) | ((base < 0 || a.off[q + 1] - base != (int64_t)kk) ? 4 : 0);

@@ -7,7 +7,7 @@ Every other extraction test runs on graphs of at most 189 bitmap words a side (`
 ``for (w = tid; w < W; w += IGMC_BLOCK)`` loop runs once, the ``running`` carries of ``bm_prefix`` / ``append_fringe`` are never
 used) or, on the one wider graph (test_gpu_headline), one hop with cap 100 and fringes of 3 000.  The rows here:
 
-  a  h = 1, cap 100, links on a 90 000-user item     split launch + k_relm; the deciding byte holds > 256 keys: radix_select
+  a  h = 1, cap 100, links on a 90 000-user item     split launch + k_relm; the deciding byte holds > 256 keys: kth_radix
   b  h = 1, ratio 0.5, no cap, the same item         k_count / k_fill on sides of 45 000; radix with a non-zero prefix
   c  h = 1, ratio 0.29, a 70 000- and the 90 000-    the 256-key bound between parking and the radix passes from both sides
      user item
@@ -27,7 +27,7 @@ is.  Everything is integer: every comparison is exact.
 PROOFS that a row reached its path are computed on the host from the text of ``include/igmc_rng.h`` restated in numpy
 (``sample_salt`` here, ``sampled_candidates_checks.sample_key``) and asserted BEFORE any comparison: per hop-1 draw the
 histogram of ``key >> 24`` over the candidate set, the byte that holds the k-th smallest key and that byte's count -- more than
-256 is ``radix_select``, at most 256 the parked list (``sample_fringe``).  A device build has no hook to force either."""
+256 is ``kth_radix``, at most 256 the parked list (``sample_fringe``).  A device build has no hook to force either."""
 import ctypes
 import functools
 
@@ -42,7 +42,7 @@ from test_extract_twin import compare
 
 CV = np.arange(1, 6, dtype=np.float64)
 SEED, EPOCH = 11, 4
-PARK = 256                       # keys of the deciding byte that sample_fringe parks (IGMC_BLOCK); more: radix_select
+PARK = 256                       # keys of the deciding byte that sample_fringe parks (IGMC_BLOCK); more: kth_radix
 HUB = 60000                      # a hop-1 draw over at least this many candidates is a "hub draw"
 KEYS = ('node_off', 'n_users', 'node_label', 'node_gid', 'node_graph', 'row_ptr', 'col', 'erel', 'elab', 'eflag', 'y')
 QUIET = 16                       # rows of more links than this print a summary, not a line per link and side
@@ -248,7 +248,7 @@ def prove_paths(name, row, G, links, seed, epoch):
             'row %s does not take the park / radix bound from both sides: %s' % (name, [d['count'] for d in hub])
     if row.get('top_byte_zero'):
         assert all(d['byte'] == 0 for d in hub)
-    if row.get('every_byte_nonzero'):       # the k-th smallest key IS radix_select's prefix: a non-zero byte found in every pass
+    if row.get('every_byte_nonzero'):       # the k-th smallest key IS kth_radix's prefix: a non-zero byte found in every pass
         assert all((d['kth'] >> s) & 255 for d in hub for s in (24, 16, 8, 0)), ['%08x' % d['kth'] for d in hub]
         assert all(d['kth'] >> 24 == d['byte'] for d in hub)
     return draws

@@ -273,6 +273,28 @@ def check_fallback_selection(be, n_items, more_than):
     g.close()
 
 
+def check_park_bound(be):
+    """3b. The edge of "park or radix" (``kth_key.h``: ``kth_parks``, the one comparison with the list's 256 entries): a deciding
+    byte of exactly 256 pool keys is parked, one of exactly 257 goes through the radix passes, and either way the k-th key may be
+    the first or the last of its byte.  User 0 of the graph has an empty row: the pool is all 66 000 items, five tiles."""
+    n_items = 66000
+    A = graph_with_corner_rows(3, n_items, 77).tocsr()
+    assert A.indptr[1] == A.indptr[0]
+    g = engine.Graph(A, device=be.device, lib=be.lib)
+    users = np.array([0], np.int32)
+    top = (sample_key(negative_salt(1, 0, 0), np.arange(n_items)) >> np.uint64(24)).astype(np.int64)
+    hist = np.bincount(top, minlength=256)
+    before = np.cumsum(hist) - hist
+    for count in (256, 257):
+        bins = np.nonzero(hist == count)[0]
+        assert len(bins), 'no top byte holds exactly %d keys' % count
+        b = int(bins[0])
+        for k in (int(before[b]) + 1, int(before[b]) + count):          # the first and the last key of the byte
+            assert deciding_byte_count(A, 0, k) == count
+            compare(sample_dev(be, g, users, k, seed=1, draw=0), segments_ref(A, users, k, seed=1, draw=0), (count, b, k))
+    g.close()
+
+
 def check_many_users(be, n_requests=MANY, permuted=True):
     """4. ``MANY`` requests over a 12 x 20 graph (the launch is capped at 65 536 workgroups: some take a second request),
     and (``permuted``) the same requests in another order: every segment unchanged, so the draw is keyed by the user id."""

@@ -49,9 +49,10 @@ def test_sampler_free_run(be, name):
 
 
 def test_sampler_four_pass_path_keeps_the_same_subset(be, monkeypatch):
-    """sample_fringe parks the keys of the deciding byte in a 256-entry list and falls back to radix_select's four passes
-    when they would not fit -- which a hash never produces.  With a bound of 0 (emulation builds read it from the environment)
-    the fallback is taken on every draw and must extract the very same batches."""
+    """sample_fringe parks the keys of the deciding byte in a 256-entry list and falls back to radix passes over the three
+    bytes below it (kth_key.h: kth_radix; the top byte's pass, already done, makes four) when they would not fit -- which a
+    hash never produces.  With a bound of 0 (emulation builds read it from the environment) the fallback is taken on every
+    draw and must extract the very same batches."""
     for name in ('synth_cap', 'synth_h2_ratio'):
         case = dict(CASES[name])
         monkeypatch.delenv('IGMC_SAMPLE_PARK', raising=False)

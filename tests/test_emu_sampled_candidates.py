@@ -39,6 +39,10 @@ def test_a_crowded_deciding_byte_goes_through_the_radix_passes(monkeypatch):
     SC.check_fallback_selection(EmuBackend(), 20000, 0)
 
 
+def test_a_deciding_byte_of_256_keys_is_parked_and_one_of_257_is_not():
+    SC.check_park_bound(EmuBackend())          # (the default bound: no IGMC_SAMPLE_PARK)
+
+
 def test_the_same_users_in_another_order_keep_their_segments():
     SC.check_many_users(EmuBackend(), 3000)
 

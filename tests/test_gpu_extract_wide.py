@@ -1,6 +1,6 @@
 """``igmc_amd/csrc/extract.hip`` on a real MI355X on wide rating graphs, against the host twin and the extraction oracle: the
 rows, proofs and checks of tests/extract_wide_checks.py, which the emulator runs too (test_emu_extract_wide.py).  What the
-single-threaded emulator cannot show is what these are for: the barriers around ``radix_select``'s histogram and mailboxes
+single-threaded emulator cannot show is what these are for: the barriers around ``kth_radix``'s histogram and mailboxes
 (``sm[8..11]``) under real wave scheduling, ``hist`` re-used as the parked key / id lists, 256 threads carrying ``running``
 through a second and a thirteenth round of the bitmap scans, and the emission kernels' prefix loops over more than 256 links.
 No hook lowers the 256-key bound on a device: the fringes are wide enough to cross it, which each row proves on the host first.

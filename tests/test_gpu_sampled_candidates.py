@@ -35,6 +35,10 @@ def test_a_crowded_deciding_byte_goes_through_the_radix_passes(be):
     SC.check_fallback_selection(be, 100000, 256)
 
 
+def test_a_deciding_byte_of_256_keys_is_parked_and_one_of_257_is_not(be):
+    SC.check_park_bound(be)
+
+
 def test_more_users_than_workgroups_and_the_same_users_in_another_order(be):
     SC.check_many_users(be)
 
