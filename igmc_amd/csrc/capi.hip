@@ -1189,20 +1189,26 @@ static void end_call(igmc_model* m, const igmc_batch* b, int training, int use_e
   m->last_flags = use_edge_flags;
 }
 
-// Adam's bias corrections of step t as the kernels take them: lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t).  With a control
-// block the kernel forms them from the block's own step counter: zeros
-struct AdamScalars {
-  float step_size, inv_sqrt_bc2;
-};
-static AdamScalars adam_scalars(const int64_t* d_ctrl, int64_t t, float lr, float beta1, float beta2) {
-  AdamScalars a = {0.f, 0.f};
+// Adam's scalars of step t as the kernels take them: the bias corrections lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t), then the
+// constants.  With a control block the kernel takes all six from the block, the corrections from its own step counter: zeros
+static AdamHyper adam_scalars(const int64_t* d_ctrl, int64_t t, float lr, float beta1, float beta2, float eps, float wd) {
+  AdamHyper h = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (!d_ctrl) {
     const double bc1 = 1.0 - std::pow((double)beta1, (double)t);
     const double bc2 = 1.0 - std::pow((double)beta2, (double)t);
-    a.step_size = (float)((double)lr / bc1);
-    a.inv_sqrt_bc2 = (float)(1.0 / std::sqrt(bc2));
+    h = {(float)((double)lr / bc1), (float)(1.0 / std::sqrt(bc2)), beta1, beta2, eps, wd};
   }
-  return a;
+  return h;
+}
+// The fused step's optimiser tail
+static AdamTail adam_tail(igmc_model* m, float* d_params, float* d_exp_avg, float* d_exp_avg_sq, const AdamHyper& h, int64_t* d_ctrl,
+                          float* d_loss, double* d_total) {
+  AdamTail at;
+  memset(&at, 0, sizeof(at));
+  at.p = d_params; at.m1 = d_exp_avg; at.m2 = d_exp_avg_sq;
+  at.h = h;
+  at.ctrl = d_ctrl; at.done = m->done_ctr; at.loss = d_loss; at.total = d_total;
+  return at;
 }
 
 extern "C" int igmc_model_forward(igmc_model* m, const float* d_params, const igmc_batch* b, int training,
@@ -1212,8 +1218,8 @@ extern "C" int igmc_model_forward(igmc_model* m, const float* d_params, const ig
   if (check_call(m, b, d_params && d_out, &why)) IGMC_FAIL(why);
   const StepPlan sp = begin_call(m, b, training ? IGMC_CALL_CONV : IGMC_CALL_EVAL, stream);
   ImgScope img(m, d_params);
-  igmc_launch_forward(m->d, b->d, sp, d_params, b->last_B, training, use_edge_flags, d_lin_mask, seed, step, multiply_by,
-                      d_out, stream);
+  const StepHead hd = {d_params, d_lin_mask, seed, step, multiply_by, 0.f, d_out};
+  igmc_launch_forward(m->d, b->d, sp, b->last_B, training, use_edge_flags, hd, stream);
   img.done_unchanged();
   HIPCHECK(hipGetLastError());
   end_call(m, b, training, use_edge_flags);
@@ -1242,8 +1248,8 @@ extern "C" int igmc_model_loss_grad(igmc_model* m, const float* d_params, const 
   if (check_call(m, b, d_params && d_out && d_grad, &why)) IGMC_FAIL(why);
   const StepPlan sp = begin_call(m, b, IGMC_CALL_STEP, stream);
   ImgScope img(m, d_params);
-  igmc_launch_loss_grad(m->d, b->d, sp, (float*)d_params, b->last_B, use_edge_flags, d_lin_mask, seed, step,
-                        multiply_by, ARR, grad_scale, arr_scale, d_out, d_grad, d_loss, nullptr, stream);
+  const StepHead hd = {d_params, d_lin_mask, seed, step, multiply_by, grad_scale, d_out};
+  igmc_launch_loss_grad(m->d, b->d, sp, b->last_B, use_edge_flags, hd, ARR, arr_scale, d_grad, d_loss, nullptr, stream);
   img.done_unchanged();
   HIPCHECK(hipGetLastError());
   end_call(m, b, 1, use_edge_flags);
@@ -1254,8 +1260,7 @@ extern "C" int igmc_adam_step(float* d_params, const float* d_grad, float* d_exp
                               int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay,
                               void* stream) {
   if (!d_params || !d_grad || !d_exp_avg || !d_exp_avg_sq || n <= 0 || step < 1) IGMC_FAIL("bad arguments");
-  const AdamScalars as = adam_scalars(nullptr, step, lr, beta1, beta2);
-  igmc_launch_adam(d_params, d_grad, d_exp_avg, d_exp_avg_sq, n, as.step_size, as.inv_sqrt_bc2, beta1, beta2, eps, weight_decay,
+  igmc_launch_adam(d_params, d_grad, d_exp_avg, d_exp_avg_sq, n, adam_scalars(nullptr, step, lr, beta1, beta2, eps, weight_decay),
                    nullptr, 0, stream);
   HIPCHECK(hipGetLastError());
   return 0;
@@ -1451,7 +1456,8 @@ extern "C" int igmc_pair_loss_grad(igmc_model* m, const float* d_params, const i
   const int B = b->last_B;
   const StepPlan sp = begin_call(m, b, IGMC_CALL_CONV, stream);
   ImgScope img(m, d_params);
-  igmc_launch_forward(m->d, b->d, sp, d_params, B, 1, use_edge_flags, d_lin_mask, seed, step, multiply_by, d_out, stream);
+  const StepHead hd = {d_params, d_lin_mask, seed, step, multiply_by, 0.f, d_out};
+  igmc_launch_forward(m->d, b->d, sp, B, 1, use_edge_flags, hd, stream);
   igmc_launch_pair_loss(d_out, b->d.y, B, mse_weight, d_gout, d_stats, stream);
   igmc_launch_backward(m->d, b->d, sp, d_params, B, use_edge_flags, d_gout, 0, 0.f, multiply_by, 2.f, ARR, d_grad, stream);
   igmc_launch_pair_arr(m->d.arr_part, ARR, d_stats, stream);
@@ -1724,7 +1730,7 @@ extern "C" int igmc_model_check(igmc_model* m, void* stream) {
 extern "C" int igmc_adam_step_ctrl(float* d_params, const float* d_grad, float* d_exp_avg, float* d_exp_avg_sq,
                                    int64_t n, const int64_t* d_ctrl, void* stream) {
   if (!d_params || !d_grad || !d_exp_avg || !d_exp_avg_sq || n <= 0 || !d_ctrl) IGMC_FAIL("bad arguments");
-  igmc_launch_adam(d_params, d_grad, d_exp_avg, d_exp_avg_sq, n, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, (int64_t*)d_ctrl, 0, stream);
+  igmc_launch_adam(d_params, d_grad, d_exp_avg, d_exp_avg_sq, n, AdamHyper{}, (int64_t*)d_ctrl, 0, stream);
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -1735,9 +1741,8 @@ extern "C" int igmc_step_finish(igmc_model* m, const igmc_batch* b, float* d_par
                                 float weight_decay, void* stream) {
   if (!m || !b || !d_params || !d_grad || !d_exp_avg || !d_exp_avg_sq || !d_loss) IGMC_FAIL("bad arguments");
   if (!d_ctrl && step < 1) IGMC_FAIL("step must be >= 1");
-  const AdamScalars as = adam_scalars(d_ctrl, step, lr, beta1, beta2);
-  igmc_launch_finish(m->d, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, as.step_size, as.inv_sqrt_bc2, beta1, beta2, eps,
-                     weight_decay, d_ctrl, ARR, d_loss, d_total, m->last_flags, stream);
+  igmc_launch_finish(m->d, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, adam_scalars(d_ctrl, step, lr, beta1, beta2, eps, weight_decay),
+                     d_ctrl, ARR, d_loss, d_total, m->last_flags, stream);
   m->img_valid = 0;      // (the parameters moved, the weight images did not)
   m->img_hint = 0;
   HIPCHECK(hipGetLastError());
@@ -1752,13 +1757,13 @@ extern "C" int igmc_train_step(igmc_model* m, float* d_params, const igmc_batch*
   std::string why;
   if (check_call(m, b, d_params && d_out && d_grad && d_exp_avg && d_exp_avg_sq && d_loss, &why)) IGMC_FAIL(why);
   if (!d_ctrl && adam_t < 1) IGMC_FAIL("adam_t must be >= 1");
-  const AdamScalars as = adam_scalars(d_ctrl, adam_t, lr, beta1, beta2);
+  const AdamTail at = adam_tail(m, d_params, d_exp_avg, d_exp_avg_sq, adam_scalars(d_ctrl, adam_t, lr, beta1, beta2, eps, weight_decay),
+                                d_ctrl, d_loss, d_total);
   const StepPlan sp = begin_call(m, b, IGMC_CALL_STEP, stream);
   ImgScope img(m, d_params);
   int emitted = 0;
-  igmc_launch_train_step(m->d, b->d, sp, d_params, b->last_B, use_edge_flags, d_lin_mask, seed, step, multiply_by, ARR,
-                         d_out, d_grad, d_exp_avg, d_exp_avg_sq, as.step_size, as.inv_sqrt_bc2, beta1, beta2, eps, weight_decay,
-                         d_ctrl, m->done_ctr, d_loss, d_total, stream, 0.f, nullptr, &emitted);
+  const StepHead hd = {d_params, d_lin_mask, seed, step, multiply_by, 1.0f / (float)b->last_B, d_out};      // (one rank: the mean over the batch)
+  igmc_launch_loss_grad(m->d, b->d, sp, b->last_B, use_edge_flags, hd, ARR, 1.0f, d_grad, nullptr, &at, stream, nullptr, &emitted);
   img.done_updated(emitted);
   HIPCHECK(hipGetLastError());
   end_call(m, b, 1, use_edge_flags);
@@ -2201,28 +2206,26 @@ extern "C" int igmc_train_step_dp(igmc_model* m, igmc_comm* comm, float* d_param
   std::string why;
   if (check_call(m, b, d_params && d_out && d_grad && d_exp_avg && d_exp_avg_sq && d_loss, &why)) IGMC_FAIL(why);
   if (!d_ctrl && adam_t < 1) IGMC_FAIL("adam_t must be >= 1");
-  const AdamScalars as = adam_scalars(d_ctrl, adam_t, lr, beta1, beta2);
+  const AdamHyper ah = adam_scalars(d_ctrl, adam_t, lr, beta1, beta2, eps, weight_decay);
   const int world = comm ? comm->world : 1;
   const int B = b->last_B;
   const float gscale = 1.0f / ((float)B * (float)world);
   const StepPlan sp = begin_call(m, b, IGMC_CALL_STEP, stream);
   ImgScope img(m, d_params);
   int emitted = 0;
+  const StepHead hd = {d_params, d_lin_mask, seed, step, multiply_by, gscale, d_out};
   if (sp.exchange_inside) {
     StepExchange x = {comm_sum2, comm, (comm && comm->peer) ? comm->d_state + 2 : nullptr};
     // (the ARR term depends on the weights only: every rank adds it in full AFTER the exchange)
-    const int rc = igmc_launch_train_step(m->d, b->d, sp, d_params, B, use_edge_flags, d_lin_mask, seed, step, multiply_by,
-                                          ARR, d_out, d_grad, d_exp_avg, d_exp_avg_sq, as.step_size, as.inv_sqrt_bc2, beta1,
-                                          beta2, eps, weight_decay, d_ctrl, m->done_ctr, d_loss, d_total, stream, gscale,
-                                          comm ? &x : nullptr, &emitted);
+    const AdamTail at = adam_tail(m, d_params, d_exp_avg, d_exp_avg_sq, ah, d_ctrl, d_loss, d_total);
+    const int rc = igmc_launch_loss_grad(m->d, b->d, sp, B, use_edge_flags, hd, ARR, 1.0f, d_grad, nullptr, &at, stream,
+                                         comm ? &x : nullptr, &emitted);
     img.done_updated(emitted);
     if (rc) return 1;
   } else {
-    igmc_launch_loss_grad(m->d, b->d, sp, d_params, B, use_edge_flags, d_lin_mask, seed, step, multiply_by, ARR, gscale,
-                          1.0f / (float)world, d_out, d_grad, nullptr, nullptr, stream);
+    igmc_launch_loss_grad(m->d, b->d, sp, B, use_edge_flags, hd, ARR, 1.0f / (float)world, d_grad, nullptr, nullptr, stream);
     if (comm && comm_sum2(comm, d_grad, m->d.n_params, nullptr, 0, stream)) return 1;
-    igmc_launch_finish(m->d, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, as.step_size, as.inv_sqrt_bc2, beta1, beta2, eps,
-                       weight_decay, d_ctrl, ARR, d_loss, d_total, use_edge_flags, stream);
+    igmc_launch_finish(m->d, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, ah, d_ctrl, ARR, d_loss, d_total, use_edge_flags, stream);
     img.done_updated(0);
   }
   HIPCHECK(hipGetLastError());
@@ -2336,7 +2339,8 @@ extern "C" int igmc_sortpool_forward(igmc_sortpool* sp, const float* d_params, c
   StepPlan plan;
   igmc_step_plan(m->d, b->d, b->last_B, IGMC_CALL_CONV, &plan);
   igmc_launch_conv_forward(m->d, b->d, plan, sp->pe, b->last_B, training, use_edge_flags, stream);
-  igmc_launch_sp_forward(m->d, sp->d, b->d, d_params, b->last_B, training, d_lin_mask, seed, step, d_out, stream);
+  const StepHead hd = {d_params, d_lin_mask, seed, step, 1.f, 0.f, d_out};
+  igmc_launch_sp_forward(m->d, sp->d, b->d, b->last_B, training, hd, stream);
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -2358,7 +2362,8 @@ extern "C" int igmc_sortpool_loss_grad(igmc_sortpool* sp, const float* d_params,
   StepPlan plan;
   igmc_step_plan(md, b->d, B, IGMC_CALL_CONV, &plan);
   igmc_launch_conv_forward(md, b->d, plan, sp->pe, B, 1, use_edge_flags, stream);
-  igmc_launch_sp_forward(m->d, sp->d, b->d, d_params, B, 1, d_lin_mask, seed, step, d_out, stream);
+  const StepHead hd = {d_params, d_lin_mask, seed, step, 1.f, 0.f, d_out};
+  igmc_launch_sp_forward(m->d, sp->d, b->d, B, 1, hd, stream);
   igmc_launch_sp_backward(m->d, sp->d, b->d, d_params, B, grad_scale > 0.f ? grad_scale : 1.f / (float)B, stream);
   igmc_launch_conv_backward(md, b->d, plan, sp->pe, B, use_edge_flags, ARR * arr_scale, sp->ge, stream);
   igmc_launch_sp_wgrad(m->d, sp->d, b->d, B, sp->ge, d_grad, stream);
@@ -2374,11 +2379,10 @@ extern "C" int igmc_sortpool_step_finish(igmc_sortpool* sp, const igmc_batch* b,
                                          float weight_decay, void* stream) {
   if (!sp || !b || !d_params || !d_grad || !d_exp_avg || !d_exp_avg_sq || !d_loss) IGMC_FAIL("bad arguments");
   if (!d_ctrl && step < 1) IGMC_FAIL("step must be >= 1");
-  const AdamScalars as = adam_scalars(d_ctrl, step, lr, beta1, beta2);
   ModelDev md = sp->m->d;
   md.n_params = sp->d.n_params;          // Adam runs over the sort-pool family's own flat buffer
-  igmc_launch_finish(md, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, as.step_size, as.inv_sqrt_bc2, beta1, beta2, eps,
-                     weight_decay, d_ctrl, ARR, d_loss, d_total, sp->m->last_flags, stream);
+  igmc_launch_finish(md, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, adam_scalars(d_ctrl, step, lr, beta1, beta2, eps, weight_decay),
+                     d_ctrl, ARR, d_loss, d_total, sp->m->last_flags, stream);
   HIPCHECK(hipGetLastError());
   return 0;
 }

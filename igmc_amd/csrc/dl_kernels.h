@@ -62,6 +62,11 @@ __device__ __forceinline__ DlRows dl_rows(int n_own, int nq, int q) {
   r.nact = left < 0 ? 0 : (left < bpw ? left : bpw);
   return r;
 }
+// the padded width of an adjacency block row in the dense-layer kernels' LDS (step_plan.h sizes the LDS plans from it)
+static int dl_kp(const BatchDev& b) {
+  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
+  return 32 * ((cmax + 31) >> 5) + 8;
+}
 // Workgroups of a subgraph: at least one per 128 rows of a side's slot capacity, then -- while the whole launch still fits one
 // workgroup per CU (224) and the partial-table slots -- one more for the side whose workgroups would hold the most bundles, as
 // long as that is more than two: the bundles of a side are split evenly over its workgroups (dl_rows), so a 101 + 101-row
@@ -1680,10 +1685,9 @@ __global__ __launch_bounds__(512) void k_head_sub(BatchDev b, ModelDev m, const 
   head_sub_compute<true>(hp, b, m, P, g, (int)threadIdx.x, nu, nv, (float*)smem, inj_mask, seed, step, mult, grad_scale, out);
 }
 
-void igmc_launch_head_sub(const ModelDev& m, const BatchDev& b, const float* P, int B, const uint8_t* inj_mask, uint64_t seed,
-                          uint64_t step, float mult, float grad_scale, float* out, void* stream) {
-  IGMC_PLAUNCH("k_head_sub", k_head_sub, B, 512, (size_t)igmc_head_sub_lds_floats(m.D) * sizeof(float), stream, b, m, P, inj_mask,
-               seed, step, mult, grad_scale, out);
+void igmc_launch_head_sub(const ModelDev& m, const BatchDev& b, int B, const StepHead& hd, void* stream) {
+  IGMC_PLAUNCH("k_head_sub", k_head_sub, B, 512, (size_t)igmc_head_sub_lds_floats(m.D) * sizeof(float), stream, b, m, hd.P,
+               hd.inj_mask, hd.seed, hd.step, hd.mult, hd.grad_scale, hd.out);
 }
 
 // Layer 0 of the dense per-layer path (one-hot input): per row the histogram of (relation, label of the neighbour) over
@@ -1824,22 +1828,72 @@ static size_t dl0_lds(int kp) {
   return ((size_t)(8 * kp >> 1) + (size_t)DL_NW * 4 * kp + (size_t)DL_NW * 16 * G2_XP + 1024) * 4;
 }
 
-void igmc_launch_dl_layer0(const ModelDev& m, const BatchDev& b, int B, int training, int use_flags, void* stream) {
-  Dl0Args a;
+// ---- what the launchers of this file share
+// The arena fields every Dl*Args has (zeroes the rest); s_lab / slot where the struct has them
+template <typename A>
+static auto dl_fill_slots(A& a, const BatchDev& b, int) -> decltype((void)a.s_lab) { a.s_lab = b.s_lab; a.slot = b.slot; }
+template <typename A>
+static void dl_fill_slots(A&, const BatchDev&, long) {}
+template <typename A>
+static void dl_fill_arena(A& a, const BatchDev& b, int B) {
   memset(&a, 0, sizeof(a));
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
   a.n_users = b.n_users; a.n_items = b.n_items; a.node_off = b.node_off; a.node_label = b.node_label;
   a.relm = b.relm; a.relmT = b.relmT;
   a.cap_u = b.cap_u; a.cap_v = b.cap_v; a.relm_ld = b.relm_ld; a.relmT_ld = b.relmT_ld;
-  { const DlSplit sq = dl_split(b.cap_u, b.cap_v, B); a.nqu = sq.nqu; a.nqv = sq.nqv; } a.R = m.R; a.L = m.L; a.kp = 32 * ((cmax + 31) >> 5) + 8;
+  const DlSplit sq = dl_split(b.cap_u, b.cap_v, B);
+  a.nqu = sq.nqu; a.nqv = sq.nqv; a.kp = dl_kp(b);
+  dl_fill_slots(a, b, 0);
+}
+static int dl_timing() {
+  const char* e = getenv("IGMC_DL_TIMING");
+  return e ? atoi(e) : 0;
+}
+// The variant maps: every instantiation of a kernel template by its runtime flags, ONE function per template.  A launch takes
+// its kernel from the map and igmc_dl_prepare walks the map's whole domain: no instantiation is named anywhere else
+// (the order of the maps and of their flags is the order of the kernels in the code object)
+using Dl0Kernel = void (*)(Dl0Args);
+using DlKernel = void (*)(DlArgs);
+using DlfKernel = void (*)(DlfArgs);
+using DlbKernel = void (*)(DlbArgs);
+enum { DL_LAYER_FWD, DL_LAYER_BWD, DL_LAYER_BWD_TS, DL_LAYER_FORMS };       // k_dl_layer: backward, ... on relation-space tables
+enum { DLF_ONE, DLF_TWO, DLF_TWO_SPLIT, DLF_FORMS };                       // k_dl_fwd: relation groups, the group-split form
+enum { DLB_ONE, DLB_ONE_DENSE3, DLB_TWO, DLB_TWO_SPLIT, DLB_FORMS };       // k_dl_bwd: ... (dense3: one group only)
+static DlKernel dl_layer_kernel(bool use_flags, int form) {
+  DlKernel k = nullptr;
+  if (form == DL_LAYER_BWD_TS) igmc_dispatch([&](auto uf) { k = k_dl_layer<uf(), true, true>; }, use_flags);
+  else if (form == DL_LAYER_BWD) igmc_dispatch([&](auto uf) { k = k_dl_layer<uf(), true, false>; }, use_flags);
+  else igmc_dispatch([&](auto uf) { k = k_dl_layer<uf(), false, false>; }, use_flags);
+  return k;
+}
+static DlbKernel dl_bwd_kernel(bool use_flags, int form) {
+  DlbKernel k = nullptr;
+  if (form == DLB_ONE) igmc_dispatch([&](auto uf) { k = k_dl_bwd<uf(), 1, false>; }, use_flags);
+  else if (form == DLB_TWO) igmc_dispatch([&](auto uf) { k = k_dl_bwd<uf(), 2, false>; }, use_flags);
+  else if (form == DLB_ONE_DENSE3) igmc_dispatch([&](auto uf) { k = k_dl_bwd<uf(), 1, true>; }, use_flags);
+  else igmc_dispatch([&](auto uf) { k = k_dl_bwd<uf(), 2, false, true>; }, use_flags);
+  return k;
+}
+static DlfKernel dl_fwd_kernel(bool use_flags, bool store, int form) {
+  DlfKernel k = nullptr;
+  if (form == DLF_ONE) igmc_dispatch([&](auto st, auto uf) { k = k_dl_fwd<uf(), st(), 1>; }, store, use_flags);
+  else if (form == DLF_TWO) igmc_dispatch([&](auto st, auto uf) { k = k_dl_fwd<uf(), st(), 2>; }, store, use_flags);
+  else igmc_dispatch([&](auto st, auto uf) { k = k_dl_fwd<uf(), st(), 2, true>; }, store, use_flags);
+  return k;
+}
+static Dl0Kernel dl_layer0_kernel(bool use_flags, bool store) {
+  Dl0Kernel k = nullptr;
+  igmc_dispatch([&](auto st, auto uf) { k = k_dl_layer0<uf(), st()>; }, store, use_flags);
+  return k;
+}
+
+void igmc_launch_dl_layer0(const ModelDev& m, const BatchDev& b, int B, int training, int use_flags, void* stream) {
+  Dl0Args a;
+  dl_fill_arena(a, b, B);
+  a.R = m.R; a.L = m.L;
   a.t0 = m.g2_w + 6 * G2_WIMG;
   a.out = m.h[0];
   a.cnt0 = training ? m.cnt0 : nullptr;
-  const int grid = B * (a.nqu + a.nqv);
-  const size_t sm = dl0_lds(a.kp);
-  igmc_dispatch([&](auto uf, auto tr) {
-    IGMC_PLAUNCH("k_dl_layer0", (k_dl_layer0<uf(), tr()>), grid, DL_THREADS, sm, stream, a);
-  }, use_flags != 0, training != 0);
+  IGMC_PLAUNCH("k_dl_layer0", dl_layer0_kernel(use_flags != 0, training != 0), B * (a.nqu + a.nqv), DL_THREADS, dl0_lds(a.kp), stream, a);
 }
 
 static size_t dl_lds(int kp, bool ts = false) {
@@ -1856,11 +1910,8 @@ void igmc_launch_g2_compose(const ModelDev& m, const float* P, void* stream) {
 void igmc_launch_dl_layer(const ModelDev& m, const BatchDev& b, const float* P, int B, int l, int bwd, int use_flags,
                           float* zero_out, void* stream, int tables) {
   DlArgs a;
-  memset(&a, 0, sizeof(a));
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
-  a.n_users = b.n_users; a.n_items = b.n_items; a.node_off = b.node_off; a.relm = b.relm; a.relmT = b.relmT;
-  a.cap_u = b.cap_u; a.cap_v = b.cap_v; a.relm_ld = b.relm_ld; a.relmT_ld = b.relmT_ld;
-  { const DlSplit sq = dl_split(b.cap_u, b.cap_v, B); a.nqu = sq.nqu; a.nqv = sq.nqv; } a.R = m.R; a.D = m.D; a.l = l; a.kp = 32 * ((cmax + 31) >> 5) + 8;
+  dl_fill_arena(a, b, B);
+  a.R = m.R; a.D = m.D; a.l = l;
   a.in = bwd ? m.dpre[l] : m.h[l - 1];
   a.hprev = m.h[l - 1];
   a.out = bwd ? m.dpre[l - 1] : m.h[l];
@@ -1872,30 +1923,21 @@ void igmc_launch_dl_layer(const ModelDev& m, const BatchDev& b, const float* P, 
   a.img = m.g2_w + (size_t)((l - 1) * 2 + (bwd ? 1 : 0)) * G2_WIMG;
   a.bias = P + m.off_bias[l]; a.att = P + m.off_att[l];
   a.L = m.L;
-  const int grid = B * (a.nqu + a.nqv);
   if (bwd && tables) {       // relation-space tables instead of G / d att partials
     a.ts_part = m.ts_part; a.ts_stride = m.ts_stride; a.slot_stride = (B + 7) & ~7;
-    a.cnt0 = m.cnt0; a.node_label = b.node_label;
+    a.cnt0 = m.cnt0;
     a.gagg = nullptr; a.Y = nullptr; a.gatt_part = nullptr;
   }
-  const size_t sm = dl_lds(a.kp, bwd && tables);
-  igmc_dispatch([&](auto uf) {
-    if (bwd && tables) IGMC_PLAUNCH("k_dl_layer_bwd", (k_dl_layer<uf(), true, true>), grid, DL_THREADS, sm, stream, a);
-    else if (bwd) IGMC_PLAUNCH("k_dl_layer_bwd", (k_dl_layer<uf(), true, false>), grid, DL_THREADS, sm, stream, a);
-    else IGMC_PLAUNCH("k_dl_layer_fwd", (k_dl_layer<uf(), false, false>), grid, DL_THREADS, sm, stream, a);
-  }, use_flags != 0);
+  const int form = !bwd ? DL_LAYER_FWD : tables ? DL_LAYER_BWD_TS : DL_LAYER_BWD;
+  IGMC_PLAUNCH(bwd ? "k_dl_layer_bwd" : "k_dl_layer_fwd", dl_layer_kernel(use_flags != 0, form), B * (a.nqu + a.nqv), DL_THREADS,
+               dl_lds(a.kp, bwd && tables), stream, a);
 }
 
 void igmc_launch_dl_fwd(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
                         int use_flags, float* zero_out, void* stream) {
   DlfArgs a;
-  memset(&a, 0, sizeof(a));
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
-  a.n_users = b.n_users; a.n_items = b.n_items; a.node_off = b.node_off; a.node_label = b.node_label;
-  a.relm = b.relm; a.relmT = b.relmT;
-  a.cap_u = b.cap_u; a.cap_v = b.cap_v; a.relm_ld = b.relm_ld; a.relmT_ld = b.relmT_ld;
-  { const DlSplit sq = dl_split(b.cap_u, b.cap_v, B); a.nqu = sq.nqu; a.nqv = sq.nqv; } a.R = m.R; a.L = m.L; a.kp = 32 * ((cmax + 31) >> 5) + 8;
-  a.s_lab = b.s_lab; a.slot = b.slot;
+  dl_fill_arena(a, b, B);
+  a.R = m.R; a.L = m.L;
   for (int l = 0; l < 4; ++l) {
     a.h[l] = m.h[l];
     a.off_bias[l] = (int)m.off_bias[l];
@@ -1906,40 +1948,29 @@ void igmc_launch_dl_fwd(const ModelDev& m, const BatchDev& b, const StepPlan& sp
   a.ex = m.g2_ex; a.ex_stride = m.g2_ex_stride;
   a.gs_bar = m.gs_bar; a.gs_err = m.gs_err;
   a.self_seq = sp.self_seq;
-  a.timing = getenv("IGMC_DL_TIMING") ? atoi(getenv("IGMC_DL_TIMING")) : 0;
+  a.timing = dl_timing();
   a.B = B;
-  const int grid = 8 * ((B + 7) / 8) * (a.nqu + a.nqv);      // (XCD-aligned blocks of 8 * members workgroups: DLX_DECODE)
+  const int nmem = a.nqu + a.nqv;
+  const int grid = 8 * ((B + 7) / 8) * nmem;      // (XCD-aligned blocks of 8 * members workgroups: DLX_DECODE)
   const int ng = g2_groups(m.R, m.L);
   const int gs = sp.gsplit;
   const size_t sm = (size_t)(gs ? dlf_words_gs(a.kp) : dlf_words(a.kp, ng)) * 4;
-#ifdef IGMC_HIPEMU
-  hipemu::rt().co_cs = a.nqu + a.nqv;                   // the members of a subgraph run together:
-  hipemu::rt().co_stride = 8;                           // workgroups 8 nmem j + x + 8 rem
-  hipemu::rt().co_block = 8 * (a.nqu + a.nqv);
-#endif
-  igmc_dispatch([&](auto uf, auto tr) {
-    if (ng == 1) IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<uf(), tr(), 1>), grid, DL_THREADS, sm, stream, a);
-    else if (gs) IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<uf(), tr(), 2, true>), grid, DL_THREADS, sm, stream, a);
-    else IGMC_PLAUNCH("k_dl_fwd", (k_dl_fwd<uf(), tr(), 2>), grid, DL_THREADS, sm, stream, a);
-  }, use_flags != 0, training != 0);
+  igmc_emu_cluster(nmem, 8, 8 * nmem);      // the members of a subgraph run together: workgroups 8 nmem j + x + 8 rem
+  IGMC_PLAUNCH("k_dl_fwd", dl_fwd_kernel(use_flags != 0, training != 0, ng == 1 ? DLF_ONE : gs ? DLF_TWO_SPLIT : DLF_TWO), grid,
+               DL_THREADS, sm, stream, a);
 }
 
 void igmc_launch_dl_bwd(const ModelDev& m, const BatchDev& b, const StepPlan& sp, int B, int use_flags, void* stream,
-                        const DlHead* head, int dense3) {
+                        const StepHead* head, int dense3) {
   DlbArgs a;
-  memset(&a, 0, sizeof(a));
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
-  a.n_users = b.n_users; a.n_items = b.n_items; a.node_off = b.node_off; a.node_label = b.node_label;
-  a.relm = b.relm; a.relmT = b.relmT;
-  a.cap_u = b.cap_u; a.cap_v = b.cap_v; a.relm_ld = b.relm_ld; a.relmT_ld = b.relmT_ld;
-  { const DlSplit sq = dl_split(b.cap_u, b.cap_v, B); a.nqu = sq.nqu; a.nqv = sq.nqv; } a.R = m.R; a.L = m.L; a.D = m.D; a.kp = 32 * ((cmax + 31) >> 5) + 8;
-  a.s_lab = b.s_lab; a.slot = b.slot;
+  dl_fill_arena(a, b, B);
+  a.R = m.R; a.L = m.L; a.D = m.D;
   for (int l = 0; l < 3; ++l) a.h[l] = m.h[l];
   a.dpre3 = m.dpre[3]; a.gfeat = m.gfeat; a.g2_w = m.g2_w; a.cnt0 = m.cnt0;
   a.ts_part = m.ts_part; a.ts_stride = m.ts_stride; a.slot_stride = (B + 7) & ~7;
   a.ex = m.g2_ex; a.ex_stride = m.g2_ex_stride;
   a.gs_bar = m.gs_bar; a.gs_err = m.gs_err;
-  a.timing = getenv("IGMC_DL_TIMING") ? atoi(getenv("IGMC_DL_TIMING")) : 0;
+  a.timing = dl_timing();
   if (dense3) {
     a.dense3 = 1;
     for (int l = 0; l < 3; ++l) a.dcat[l] = m.dcat[l];
@@ -1949,44 +1980,31 @@ void igmc_launch_dl_bwd(const ModelDev& m, const BatchDev& b, const StepPlan& sp
     a.mult = head->mult; a.grad_scale = head->grad_scale; a.out = head->out;
   }
   a.B = B;
-  const int grid = 8 * ((B + 7) / 8) * (a.nqu + a.nqv);      // (XCD-aligned blocks of 8 * members workgroups: DLX_DECODE)
+  const int nmem = a.nqu + a.nqv;
+  const int grid = 8 * ((B + 7) / 8) * nmem;      // (XCD-aligned blocks of 8 * members workgroups: DLX_DECODE)
   const int gs = !dense3 && sp.gsplit;
-  const size_t sm = (size_t)(gs ? dlb_words_gs(a.kp) : dlb_words(a.kp, g2_groups(m.R, m.L))) * 4;
-#ifdef IGMC_HIPEMU
-  hipemu::rt().co_cs = a.nqu + a.nqv;
-  hipemu::rt().co_stride = 8;
-  hipemu::rt().co_block = 8 * (a.nqu + a.nqv);
-#endif
   const int ng = g2_groups(m.R, m.L);
-  igmc_dispatch([&](auto uf) {      // (relation groups: centre-node readout only -- a dense3 plan asks for the one-group layout)
-    if (ng == 1 && dense3) IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<uf(), 1, true>), grid, DL_THREADS, sm, stream, a);
-    else if (ng == 1) IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<uf(), 1, false>), grid, DL_THREADS, sm, stream, a);
-    else if (gs) IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<uf(), 2, false, true>), grid, DL_THREADS, sm, stream, a);
-    else IGMC_PLAUNCH("k_dl_bwd", (k_dl_bwd<uf(), 2, false>), grid, DL_THREADS, sm, stream, a);
-  }, use_flags != 0);
+  const size_t sm = (size_t)(gs ? dlb_words_gs(a.kp) : dlb_words(a.kp, ng)) * 4;
+  igmc_emu_cluster(nmem, 8, 8 * nmem);
+  // (relation groups: centre-node readout only -- a dense3 plan asks for the one-group layout)
+  const int form = ng == 1 ? (dense3 ? DLB_ONE_DENSE3 : DLB_ONE) : gs ? DLB_TWO_SPLIT : DLB_TWO;
+  IGMC_PLAUNCH("k_dl_bwd", dl_bwd_kernel(use_flags != 0, form), grid, DL_THREADS, sm, stream, a);
 }
 
 int igmc_dl_prepare() {
 #ifndef IGMC_HIPEMU
-  const int mx = 160 * 1024;
-  if (hipFuncSetAttribute((const void*)k_dl_layer<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_dl_layer<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_dl_layer<true, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_dl_layer<false, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_dl_layer<true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_dl_layer<false, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) return 1;
-#define DL_MAXLDS(k) if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) return 1
-  DL_MAXLDS((k_dl_bwd<true, 1, false>)); DL_MAXLDS((k_dl_bwd<false, 1, false>)); DL_MAXLDS((k_dl_bwd<true, 2, false>)); DL_MAXLDS((k_dl_bwd<false, 2, false>));
-  DL_MAXLDS((k_dl_bwd<true, 1, true>)); DL_MAXLDS((k_dl_bwd<false, 1, true>));
-  DL_MAXLDS((k_dl_bwd<true, 2, false, true>)); DL_MAXLDS((k_dl_bwd<false, 2, false, true>));
-  DL_MAXLDS((k_dl_fwd<true, true, 1>)); DL_MAXLDS((k_dl_fwd<false, true, 1>)); DL_MAXLDS((k_dl_fwd<true, false, 1>)); DL_MAXLDS((k_dl_fwd<false, false, 1>));
-  DL_MAXLDS((k_dl_fwd<true, true, 2>)); DL_MAXLDS((k_dl_fwd<false, true, 2>)); DL_MAXLDS((k_dl_fwd<true, false, 2>)); DL_MAXLDS((k_dl_fwd<false, false, 2>));
-  DL_MAXLDS((k_dl_fwd<true, true, 2, true>)); DL_MAXLDS((k_dl_fwd<false, true, 2, true>)); DL_MAXLDS((k_dl_fwd<true, false, 2, true>)); DL_MAXLDS((k_dl_fwd<false, false, 2, true>));
-#undef DL_MAXLDS
-  if (hipFuncSetAttribute((const void*)k_dl_layer0<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_dl_layer0<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_dl_layer0<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_dl_layer0<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx) != hipSuccess) return 1;
+  const auto max_lds = [](const void* k) { return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess; };
+  for (int uf = 0; uf < 2; ++uf) {
+    for (int st = 0; st < 2; ++st) {
+      if (max_lds((const void*)dl_layer0_kernel(uf, st))) return 1;
+      for (int f = 0; f < DLF_FORMS; ++f)
+        if (max_lds((const void*)dl_fwd_kernel(uf, st, f))) return 1;
+    }
+    for (int f = 0; f < DL_LAYER_FORMS; ++f)
+      if (max_lds((const void*)dl_layer_kernel(uf, f))) return 1;
+    for (int f = 0; f < DLB_FORMS; ++f)
+      if (max_lds((const void*)dl_bwd_kernel(uf, f))) return 1;
+  }
 #endif
   return 0;
 }

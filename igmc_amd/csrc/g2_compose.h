@@ -167,9 +167,17 @@ int igmc_g2_xcd_ok() {
 // returns 1 when the launch leaves the advance of the launch sequence number to the caller's next kernel (k_tail_ts)
 int g_igmc_compose_count = 0;      // launches of k_g2_compose so far (capi.hip: did a call refresh the weight images)
 
-int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
-                            int use_flags, const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float grad_scale,
-                            float* out, void* stream, int nstash, const int64_t* stash_ctrl) {
+// Every instantiation of k_graph_step2, by its flags: the launch takes its kernel from here and igmc_g2_prepare walks the whole
+// domain, so a variant cannot be launched without its LDS limit raised
+using G2Kernel = void (*)(G2Args);
+static G2Kernel g2_kernel(bool use_flags, bool training, bool clustered) {
+  G2Kernel k = nullptr;
+  igmc_dispatch([&](auto cl, auto tr, auto uf) { k = k_graph_step2<uf(), tr(), cl()>; }, clustered, training, use_flags);
+  return k;
+}
+
+int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan& sp, int B, int training, int use_flags,
+                            const StepHead& hd, void* stream, int nstash, const int64_t* stash_ctrl) {
   const G2Layout& lay = sp.lay;
   const int cs = sp.cs;
   G2Args a;
@@ -187,13 +195,8 @@ int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan
   a.lmask = m.lmask; a.ctrl = m.ctrl;
   a.off_basis3 = (int)m.off_basis[3]; a.off_att3 = (int)m.off_att[3]; a.off_root3 = (int)m.off_root[3];
   a.off_l1w = (int)m.off_l1w; a.off_l1b = (int)m.off_l1b; a.off_l2w = (int)m.off_l2w; a.off_l2b = (int)m.off_l2b;
-  a.P = P;
-  a.inj_mask = inj_mask;
-  a.seed = seed;
-  a.step = step;
-  a.mult = mult;
-  a.grad_scale = grad_scale;
-  a.out = out;
+  a.P = hd.P; a.inj_mask = hd.inj_mask; a.seed = hd.seed; a.step = hd.step; a.mult = hd.mult; a.grad_scale = hd.grad_scale;
+  a.out = hd.out;
   a.lay2 = lay;
   a.timing = getenv("IGMC_GS_TIMING") ? 1 : 0;
   a.ts = (g_igmc_prof_on == 2) ? m.gs_ts : nullptr;
@@ -214,21 +217,15 @@ int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan
   const int grid = sp.grid + a.nstash;      // (clusters in XCD-aligned blocks of 8 cs workgroups [+ the stash role])
   const size_t sm = (size_t)lay.words * 4;
   if (!m.img_current) {
-    IGMC_PLAUNCH("k_g2_compose", k_g2_compose, 2 * 3 * g2_groups(m.R, m.L) * (G2_NR + 1) + g2_t0_rows(m.R, m.L) / 32, G2C_THREADS, 0, stream, m, P, m.g2_w);
+    IGMC_PLAUNCH("k_g2_compose", k_g2_compose, 2 * 3 * g2_groups(m.R, m.L) * (G2_NR + 1) + g2_t0_rows(m.R, m.L) / 32, G2C_THREADS, 0, stream, m, hd.P, m.g2_w);
     ++g_igmc_compose_count;
   }
-#ifdef IGMC_HIPEMU
-  if (cs > 1) {        // (after the launch above: a launch consumes the co-residency request)
-    hipemu::rt().co_cs = cs;
-    hipemu::rt().co_stride = 8;        // members of cluster (j, x) = workgroups 8 cs j + x + 8 c
-    hipemu::rt().co_block = 8 * cs;
-  }
-#endif
+  // (after the launch above: a launch consumes the co-residency request.  Members of cluster (j, x) = workgroups 8 cs j + x + 8 c)
+  if (cs > 1) igmc_emu_cluster(cs, 8, 8 * cs);
   if (getenv("IGMC_GS_TRACE")) fprintf(stderr, "[igmc] k_graph_step B=%d train=%d flags=%d v2 kp=%d lds=%zu cluster=%d grid=%d\n", B, training, use_flags, lay.kp, sm, cs, grid);
   // (cs > 1: one subgraph per workgroup -- the straight-line variants)
-  igmc_dispatch([&](auto uf, auto tr, auto cl) {
-    IGMC_PLAUNCH(tr() ? "k_graph_step" : "k_graph_fwd", (k_graph_step2<uf(), tr(), cl()>), grid, G2_THREADS, sm, stream, a);
-  }, use_flags != 0, training != 0, cs > 1);
+  IGMC_PLAUNCH(training ? "k_graph_step" : "k_graph_fwd", g2_kernel(use_flags != 0, training != 0, cs > 1), grid, G2_THREADS, sm,
+               stream, a);
   return a.self_seq ? 0 : 1;
 }
 
@@ -239,11 +236,8 @@ int igmc_g2_prepare() {
   (void)igmc_g2_xcd_ok();      // (probed here, at model creation: never inside a stream capture)
 #ifndef IGMC_HIPEMU
   const int mx = 160 * 1024;
-  const void* fns[8] = {(const void*)k_graph_step2<true, true, true>,   (const void*)k_graph_step2<false, true, true>,
-                        (const void*)k_graph_step2<true, false, true>,  (const void*)k_graph_step2<false, false, true>,
-                        (const void*)k_graph_step2<true, true, false>,  (const void*)k_graph_step2<false, true, false>,
-                        (const void*)k_graph_step2<true, false, false>, (const void*)k_graph_step2<false, false, false>};
-  for (const void* fn : fns) {
+  for (int v = 0; v < 8; ++v) {
+    const void* fn = (const void*)g2_kernel(v & 1, v & 2, v & 4);
     // (the limit is on static + dynamic LDS: the training forms carry the stash role's static arrays, which
     //  igmc_g2_layout leaves room for)
     hipFuncAttributes fa;

@@ -47,10 +47,45 @@ struct ModelAux {
   void* s2;
   void* ev[8];
 };
+// The head's inputs of a call: parameters, the injected dropout mask (or null: drawn from seed / step), the output scale, the
+// scale of the loss gradient (training steps; 0 elsewhere) and where the predictions go.  Filled once per call (capi.hip).
+struct StepHead {
+  const float* P;
+  const uint8_t* inj_mask;
+  uint64_t seed, step;
+  float mult, grad_scale;
+  float* out;
+};
+// Adam's scalars of one step: lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t) and the optimiser's constants.  All zero where the
+// kernel reads them from a control block (adam_hyper_from_ctrl) or the stash (adam_hyper_from_stash) instead.
+struct AdamHyper {
+  float step_size, inv_sqrt_bc2, beta1, beta2, eps, wd;
+};
+// optional optimiser tail of k_finalize (single-GPU fused step): Adam on the parameters whose gradient the
+// workgroup just produced (conv layers) / on a slice of the lin parameters (extra workgroups), then the LAST
+// workgroup to finish emits loss / epoch total and advances the control block.
+struct AdamTail {
+  int enabled;
+  float* p;
+  float* m1;
+  float* m2;
+  AdamHyper h;
+  int64_t* ctrl;
+  int* done;
+  BatchDev b;
+  float ARR;
+  float* loss;
+  double* total;
+  int use_flags;      // the step ran under edge dropout (the tick then also checks the arena's dropout stamp)
+  const int* skip;    // data-parallel step: set by the gradient exchange when its sums did not arrive (StepExchange::failed);
+                      // the whole launch then returns at once -- no parameter, moment or counter is touched
+};
+// (kernel arguments: the six floats stand where they always stood)
+static_assert(sizeof(AdamHyper) == 24 && offsetof(AdamTail, h) == 32 && offsetof(AdamTail, ctrl) == 56 &&
+              offsetof(AdamTail, b) == 72, "AdamTail's kernarg layout");
 struct StepPlan;      // what a call launches: below (step_plan.h builds it, the launch sequences read it)
-void igmc_launch_forward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
-                         int use_flags, const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult,
-                         float* out, void* stream);
+void igmc_launch_forward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, int B, int training, int use_flags,
+                         const StepHead& hd, void* stream);
 void igmc_launch_conv_forward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
                               int use_flags, void* stream);
 void igmc_launch_conv_backward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int use_flags,
@@ -58,7 +93,6 @@ void igmc_launch_conv_backward(const ModelDev& m, const BatchDev& b, const StepP
 void igmc_launch_backward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int use_flags,
                           const float* gout, int from_err, float grad_scale, float mult, float drop_scale,
                           float arr_coef, float* grad, void* stream);
-struct AdamTail;
 // Data-parallel step: the REDUCED gradient sources of the step (relation-space tables + d att partials of the subgraph
 // kernel, or the basis-space partial sums of the per-layer path; plus the lin1 / lin2 gradients in `grad`) are summed over
 // the ranks between their reduction and the gradient / Adam kernel -- the step keeps its single-GPU kernels, the exchange
@@ -70,17 +104,11 @@ struct StepExchange {
                           // gradient / Adam kernel behind it then leaves parameters, moments and step counters alone; or null
 };
 // returns 0, or the exchange's error code
-int igmc_launch_loss_grad(const ModelDev& m, const BatchDev& b, const StepPlan& sp, float* P, int B, int use_flags,
-                          const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float ARR,
-                          float grad_scale, float arr_scale, float* out, float* grad, float* loss, const AdamTail* adam,
-                          void* stream, const StepExchange* xch = nullptr, int* img_emitted = nullptr);
-// (sp: a plan of kind IGMC_CALL_STEP; grad_scale 0: 1 / B; xch: see StepExchange -- only where sp.exchange_inside says so;
+int igmc_launch_loss_grad(const ModelDev& m, const BatchDev& b, const StepPlan& sp, int B, int use_flags, const StepHead& hd,
+                          float ARR, float arr_scale, float* grad, float* loss, const AdamTail* adam, void* stream,
+                          const StepExchange* xch = nullptr, int* img_emitted = nullptr);
+// (sp: a plan of kind IGMC_CALL_STEP; xch: see StepExchange -- only where sp.exchange_inside says so;
 //  *img_emitted = 1 when the step's last kernel also left the weight images of the updated parameters in m.g2_w)
-int igmc_launch_train_step(const ModelDev& m, const BatchDev& b, const StepPlan& sp, float* P, int B, int use_flags,
-                           const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float ARR, float* out,
-                           float* grad, float* m1, float* m2, float step_size, float inv_sqrt_bc2, float beta1,
-                           float beta2, float eps, float wd, int64_t* ctrl, int* done, float* loss, double* total,
-                           void* stream, float grad_scale = 0.f, const StepExchange* xch = nullptr, int* img_emitted = nullptr);
 void igmc_launch_loss(const ModelDev& m, const BatchDev& b, float ARR, float* loss, void* stream);
 void igmc_launch_sse(const BatchDev& b, const float* out, double* acc, int64_t* ctrl, void* stream);
 // scores.hip: the scoring step's tail (k_sse_acc + the outputs / labels filed at their positions) and the extremes of a key array
@@ -243,11 +271,9 @@ void igmc_launch_loo_fill(const GraphDev& g, const BatchDev& b, int B, int64_t l
 void igmc_launch_loo_deltas(const float* scores, const int64_t* var_off, int64_t n_links, float* base, float* delta, float* key,
                             const int64_t* seg_off, void* stream);
 int igmc_model_prepare(const ModelDev& m);
-void igmc_launch_adam(float* p, const float* g, float* m1, float* m2, int64_t n, float step_size,
-                      float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd, int64_t* ctrl, int tick,
+void igmc_launch_adam(float* p, const float* g, float* m1, float* m2, int64_t n, const AdamHyper& h, int64_t* ctrl, int tick,
                       void* stream);
-void igmc_launch_finish(const ModelDev& m, const BatchDev& b, float* p, const float* g, float* m1, float* m2,
-                        float step_size, float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd,
+void igmc_launch_finish(const ModelDev& m, const BatchDev& b, float* p, const float* g, float* m1, float* m2, const AdamHyper& h,
                         int64_t* ctrl, float ARR, float* loss, double* total, int use_flags, void* stream);
 
 // graphstep2.hip: one cluster of workgroups per enclosing subgraph, relational aggregation on the matrix cores
@@ -307,26 +333,17 @@ int igmc_dl_always();        // IGMC_DL_ALWAYS=1 (test hook): arenas with small 
 void igmc_launch_g2_compose(const ModelDev& m, const float* P, void* stream);
 void igmc_launch_dl_layer0(const ModelDev& m, const BatchDev& b, int B, int training, int use_flags, void* stream);
 // (head != NULL: the launch runs the subgraphs' loss head itself -- no k_head_sub launch in front of it)
-struct DlHead {
-  const float* P;
-  const uint8_t* inj_mask;
-  uint64_t seed, step;
-  float mult, grad_scale;
-  float* out;
-};
 // (dense3: the sort-pool family's backward -- dPre_3 of every row from m.dpre[3], the readout gradient of layers 0..2 from m.dcat)
 void igmc_launch_dl_bwd(const ModelDev& m, const BatchDev& b, const StepPlan& sp, int B, int use_flags, void* stream,
-                        const DlHead* head = nullptr, int dense3 = 0);
+                        const StepHead* head = nullptr, int dense3 = 0);
 void igmc_launch_dl_fwd(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
                         int use_flags, float* zero_out, void* stream);
-void igmc_launch_head_sub(const ModelDev& m, const BatchDev& b, const float* P, int B, const uint8_t* inj_mask, uint64_t seed,
-                          uint64_t step, float mult, float grad_scale, float* out, void* stream);
+void igmc_launch_head_sub(const ModelDev& m, const BatchDev& b, int B, const StepHead& hd, void* stream);
 void igmc_launch_dl_layer(const ModelDev& m, const BatchDev& b, const float* P, int B, int l, int bwd, int use_flags,
                           float* zero_out, void* stream, int tables = 0);
 // (stash_ctrl / nstash = 4: four more workgroups behind sp.grid run the stash role of the one-launch tail that follows)
-int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
-                            int use_flags, const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float grad_scale,
-                            float* out, void* stream, int nstash = 0, const int64_t* stash_ctrl = nullptr);
+int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan& sp, int B, int training, int use_flags,
+                            const StepHead& hd, void* stream, int nstash = 0, const int64_t* stash_ctrl = nullptr);
 
 // ---- per-kernel timing (HIP events on the launch stream; bench.py's roofline leg) ----
 void igmc_prof_begin(const char* name, void* stream);
@@ -339,6 +356,18 @@ extern int g_igmc_prof_on;
     IGMC_LAUNCH(kern, grid, block, shmem, stream, __VA_ARGS__);            \
     if (g_igmc_prof_on == 1) igmc_prof_end(stream);                        \
   } while (0)
+
+// The NEXT launch's workgroups wait for each other: the CPU emulation must run the cs members x, x + stride, .. of a cluster
+// together (inside blocks of `block` consecutive workgroups; hipemu::Runtime::co_cs).  The device needs no such request.
+static inline void igmc_emu_cluster(int cs, int stride, int block) {
+#ifdef IGMC_HIPEMU
+  hipemu::rt().co_cs = cs;
+  hipemu::rt().co_stride = stride;
+  hipemu::rt().co_block = block;
+#else
+  (void)cs; (void)stride; (void)block;
+#endif
+}
 
 // Runtime flags -> template arguments: igmc_dispatch([&](auto uf, auto tr) { ... k<uf(), tr()> ... }, use_flags, training) calls
 // the generic lambda with one std::bool_constant per flag, so a kernel templated on bools has ONE launch site per variant.

@@ -21,7 +21,7 @@
 //     organised for FEW launches: derived weight layouts are produced while staging into LDS (no prep
 //     kernel), the three Y products and the three weight-gradient products are batched into one launch
 //     each (blockIdx.y = layer), and loss / epoch-total / control-block tick ride in the Adam kernel.
-#include "model.h"
+#include "launch.h"      // StepHead, AdamHyper, AdamTail; the launch sequences are at the end of the file
 #include "g2_image.h"
 #include "fin_stash.h"      // layout of the weights-only stash (IGMC_STASH_*) and the role that fills it
 #include "g2_words.h"       // {f32, tag} words (the one-launch tail's hand-off)
@@ -1583,37 +1583,26 @@ __device__ __forceinline__ void loss_body(const BatchDev& b, const ModelDev& m, 
   }
 }
 
-// one Adam update (torch.optim.Adam semantics)
-__device__ __forceinline__ void adam_elem(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m1,
-                                          float* __restrict__ m2, int64_t i, float step_size, float inv_sqrt_bc2,
-                                          float beta1, float beta2, float eps, float wd) {
-  float gi = g[i];
-  const float pi = p[i];
-  if (wd != 0.f) gi += wd * pi;
-  const float a = beta1 * m1[i] + (1.f - beta1) * gi;
-  const float v = beta2 * m2[i] + (1.f - beta2) * gi * gi;
-  m1[i] = a;
-  m2[i] = v;
-  p[i] = pi - step_size * a / (sqrtf(v) * inv_sqrt_bc2 + eps);
+// The Adam scalars of a step under hipGraph replay live in HBM: in the control block, or (behind k_tail_ts / the stash role
+// of the subgraph kernel's launch) in the stash
+__device__ __forceinline__ AdamHyper adam_hyper_from_ctrl(const int64_t* ctrl) {
+  const double* d = (const double*)ctrl;
+  return {(float)d[IGMC_CTRL_STEP_SIZE], (float)d[IGMC_CTRL_INV_SQRT_BC2], (float)d[IGMC_CTRL_BETA1],
+          (float)d[IGMC_CTRL_BETA2], (float)d[IGMC_CTRL_EPS], (float)d[IGMC_CTRL_WD]};
+}
+__device__ __forceinline__ AdamHyper adam_hyper_from_stash(const float* stash) {
+  return {stash[IGMC_STASH_SCAL + 0], stash[IGMC_STASH_SCAL + 1], stash[IGMC_STASH_SCAL + 2],
+          stash[IGMC_STASH_SCAL + 3], stash[IGMC_STASH_SCAL + 4], stash[IGMC_STASH_SCAL + 5]};
 }
 
-// ... of an element whose gradient, parameter and moments are in registers already
-__device__ __forceinline__ void adam_store(float* p, float* m1, float* m2, int64_t i, float gi, float pv, float av, float vv,
-                                           float step_size, float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd) {
-  if (wd != 0.f) gi += wd * pv;
-  const float a = beta1 * av + (1.f - beta1) * gi;
-  const float v = beta2 * vv + (1.f - beta2) * gi * gi;
-  m1[i] = a;
-  m2[i] = v;
-  p[i] = pv - step_size * a / (sqrtf(v) * inv_sqrt_bc2 + eps);
-}
-
-// The same step with the two products of each moment rounded SEPARATELY (no fused multiply-add): the form of every walk over
+// One Adam update (torch.optim.Adam semantics) of an element whose gradient, parameter and moments are in registers already,
+// with the two products of each moment rounded SEPARATELY (no fused multiply-add): the form of every walk over
 // the lin parameters -- adam_range and the lin role of k_tail_fin, which visits the same elements in its own order.  Left to
 // the compiler, a * b + c * d becomes two packed multiplies and an add in one caller and an fma in another (it depends on the
 // unroll count): a last-bit difference in the moments between kernels that must leave the same bits.
 __device__ __forceinline__ void adam_store_sep(float* p, float* m1, float* m2, int64_t i, float gi, float pv, float av, float vv,
-                                               float step_size, float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd) {
+                                               const AdamHyper& h) {
+  const float step_size = h.step_size, inv_sqrt_bc2 = h.inv_sqrt_bc2, beta1 = h.beta1, beta2 = h.beta2, eps = h.eps, wd = h.wd;
   if (wd != 0.f) gi += wd * pv;
   float a, v;
   {
@@ -1631,8 +1620,7 @@ __device__ __forceinline__ void adam_store_sep(float* p, float* m1, float* m2, i
 // requesting element k + 1 early)
 template <int NB>
 __device__ __forceinline__ void adam_range(float* p, const float* g, float* m1, float* m2, int64_t lo, int64_t hi,
-                                           float step_size, float inv_sqrt_bc2, float beta1, float beta2, float eps,
-                                           float wd) {
+                                           const AdamHyper& h) {
   for (int64_t i0 = lo + threadIdx.x; i0 < hi; i0 += (int64_t)NB * IGMC_BLOCK) {
     float gv[NB], pv[NB], av[NB], vv[NB];
 #pragma unroll
@@ -1647,30 +1635,10 @@ __device__ __forceinline__ void adam_range(float* p, const float* g, float* m1, 
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
       const int64_t i = i0 + (int64_t)k * IGMC_BLOCK;
-      if (i < hi) adam_store_sep(p, m1, m2, i, gv[k], pv[k], av[k], vv[k], step_size, inv_sqrt_bc2, beta1, beta2, eps, wd);
+      if (i < hi) adam_store_sep(p, m1, m2, i, gv[k], pv[k], av[k], vv[k], h);
     }
   }
 }
-
-// optional optimiser tail of k_finalize (single-GPU fused step): Adam on the parameters whose gradient the
-// workgroup just produced (conv layers) / on a slice of the lin parameters (extra workgroups), then the LAST
-// workgroup to finish emits loss / epoch total and advances the control block.
-struct AdamTail {
-  int enabled;
-  float* p;
-  float* m1;
-  float* m2;
-  float step_size, inv_sqrt_bc2, beta1, beta2, eps, wd;
-  int64_t* ctrl;
-  int* done;
-  BatchDev b;
-  float ARR;
-  float* loss;
-  double* total;
-  int use_flags;      // the step ran under edge dropout (the tick then also checks the arena's dropout stamp)
-  const int* skip;    // data-parallel step: set by the gradient exchange when its sums did not arrive (StepExchange::failed);
-                      // the whole launch then returns at once -- no parameter, moment or counter is touched
-};
 
 // IGMC_FIN_NB workgroups per conv layer: turn the reduced partials into the flat gradient, add the
 // adjacent-rating-regulariser gradient (reference train_eval.py:167-174), emit the ARR value, and (AdamTail) update
@@ -1692,15 +1660,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_finalize(ModelDev m, const float
   __shared__ int s_lastl;
   __shared__ float sg10[4][10];
   __shared__ int s_last;
-  if (at.enabled && at.ctrl) {      // hipGraph replay: the Adam scalars live in HBM
-    const double* d = (const double*)at.ctrl;
-    at.step_size = (float)d[IGMC_CTRL_STEP_SIZE];
-    at.inv_sqrt_bc2 = (float)d[IGMC_CTRL_INV_SQRT_BC2];
-    at.beta1 = (float)d[IGMC_CTRL_BETA1];
-    at.beta2 = (float)d[IGMC_CTRL_BETA2];
-    at.eps = (float)d[IGMC_CTRL_EPS];
-    at.wd = (float)d[IGMC_CTRL_WD];
-  }
+  if (at.enabled && at.ctrl) at.h = adam_hyper_from_ctrl(at.ctrl);      // hipGraph replay
   auto finish = [&](int64_t i, float g) { grad[i] = g; };
   if (blockIdx.x >= 4 * IGMC_FIN_NB) {   // extra workgroups: Adam on lin1 / lin2 (their gradients are final already)
     const int64_t n_lin = m.n_params - m.off_l1w;
@@ -1708,7 +1668,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_finalize(ModelDev m, const float
     const int64_t chunk = (n_lin + nb - 1) / nb;
     const int64_t lo = m.off_l1w + (int64_t)(blockIdx.x - 4 * IGMC_FIN_NB) * chunk;
     const int64_t hi = (lo + chunk < m.n_params) ? lo + chunk : m.n_params;
-    adam_range<8>(at.p, grad, at.m1, at.m2, lo, hi, at.step_size, at.inv_sqrt_bc2, at.beta1, at.beta2, at.eps, at.wd);
+    adam_range<8>(at.p, grad, at.m1, at.m2, lo, hi, at.h);
   } else {
     const int l = blockIdx.x / IGMC_FIN_NB, part = blockIdx.x % IGMC_FIN_NB, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -1833,8 +1793,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_finalize(ModelDev m, const float
       __syncthreads();
       if (s_lastl) {
         __threadfence();
-        adam_range<12>(at.p, grad, at.m1, at.m2, m.off_basis[l], m.off_att[l] + na, at.step_size, at.inv_sqrt_bc2,
-                       at.beta1, at.beta2, at.eps, at.wd);
+        adam_range<12>(at.p, grad, at.m1, at.m2, m.off_basis[l], m.off_att[l] + na, at.h);
         if (tid == 0) at.done[1 + l] = 0;
       }
     }
@@ -1875,10 +1834,10 @@ __device__ __forceinline__ float fts_emit(float* __restrict__ grad, const AdamTa
   if (store) grad[i] = g;
   if (!at.enabled) return pold;
   float gi = g;
-  if (at.wd != 0.f) gi += at.wd * pold;
-  const float a = at.beta1 * m1old + (1.f - at.beta1) * gi;
-  const float v = at.beta2 * m2old + (1.f - at.beta2) * gi * gi;
-  const float pnew = pold - at.step_size * a / (sqrtf(v) * at.inv_sqrt_bc2 + at.eps);
+  if (at.h.wd != 0.f) gi += at.h.wd * pold;
+  const float a = at.h.beta1 * m1old + (1.f - at.h.beta1) * gi;
+  const float v = at.h.beta2 * m2old + (1.f - at.h.beta2) * gi * gi;
+  const float pnew = pold - at.h.step_size * a / (sqrtf(v) * at.h.inv_sqrt_bc2 + at.h.eps);
   if (store) {
     at.m1[i] = a;
     at.m2[i] = v;
@@ -1987,14 +1946,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_finalize_ts(ModelDev m, const fl
   __shared__ float smf[8];
   const int tid = threadIdx.x;
   const float* stash = m.fin_stash;
-  if (at.enabled && at.ctrl) {      // hipGraph replay: the Adam scalars of the step, stashed by k_tail_ts
-    at.step_size = stash[IGMC_STASH_SCAL + 0];
-    at.inv_sqrt_bc2 = stash[IGMC_STASH_SCAL + 1];
-    at.beta1 = stash[IGMC_STASH_SCAL + 2];
-    at.beta2 = stash[IGMC_STASH_SCAL + 3];
-    at.eps = stash[IGMC_STASH_SCAL + 4];
-    at.wd = stash[IGMC_STASH_SCAL + 5];
-  }
+  if (at.enabled && at.ctrl) at.h = adam_hyper_from_stash(stash);      // hipGraph replay: stashed by k_tail_ts
   if ((int)blockIdx.x < 4 * IGMC_FTS_NB) {
     const int l = blockIdx.x / IGMC_FTS_NB, part = blockIdx.x % IGMC_FTS_NB;
     const int fin = (l == 0) ? m.L : 32, nE = fin * 32, R = m.R, na = R * 4;
@@ -2194,7 +2146,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_finalize_ts(ModelDev m, const fl
     const int64_t chunk = (n_lin + nlin - 1) / nlin;
     const int64_t lo = m.off_l1w + (int64_t)(blockIdx.x - 4 * IGMC_FTS_NB) * chunk;
     const int64_t hi = (lo + chunk < m.n_params) ? lo + chunk : m.n_params;
-    adam_range<8>(at.p, grad, at.m1, at.m2, lo, hi, at.step_size, at.inv_sqrt_bc2, at.beta1, at.beta2, at.eps, at.wd);
+    adam_range<8>(at.p, grad, at.m1, at.m2, lo, hi, at.h);
   } else {                                                     // loss, epoch total, control-block tick
     loss_body(at.b, m, at.ARR, at.loss, at.total, smf);
     if (tid == 0 && at.ctrl) ctrl_check_and_advance(at.ctrl, at.b, at.use_flags);
@@ -2376,14 +2328,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m,
     TF_STAMP(blk == nprod_r + 1, 51);
     return;
   }
-  if (at.ctrl) {      // hipGraph replay: the Adam scalars of the step, stashed in the launch in front
-    at.step_size = stash[IGMC_STASH_SCAL + 0];
-    at.inv_sqrt_bc2 = stash[IGMC_STASH_SCAL + 1];
-    at.beta1 = stash[IGMC_STASH_SCAL + 2];
-    at.beta2 = stash[IGMC_STASH_SCAL + 3];
-    at.eps = stash[IGMC_STASH_SCAL + 4];
-    at.wd = stash[IGMC_STASH_SCAL + 5];
-  }
+  if (at.ctrl) at.h = adam_hyper_from_stash(stash);      // hipGraph replay: stashed in the launch in front
   const int mb = blk - nprod;
   if (mb < nconv) {
     const int l = mb < 96 ? 1 + (mb >> 5) : 0, c = mb < 96 ? (mb & 31) : mb - 96;
@@ -2570,8 +2515,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_tail_fin(BatchDev b, ModelDev m,
     }
 #pragma unroll
     for (int k = 0; k < 5; ++k)
-      if (okx[k]) adam_store_sep(at.p, at.m1, at.m2, ix[k], gv[k], pv[k], av[k], vv[k], at.step_size, at.inv_sqrt_bc2, at.beta1,
-                                 at.beta2, at.eps, at.wd);      // (adam_range's bits: k_finalize_ts's lin workgroups)
+      if (okx[k]) adam_store_sep(at.p, at.m1, at.m2, ix[k], gv[k], pv[k], av[k], vv[k], at.h);      // (adam_range's bits: k_finalize_ts's lin workgroups)
     TF_STAMP(mb == nconv, 18);
   } else {                                                     // loss, epoch total, control-block tick, sequence number
     if (bump_seq && tid == 0) m.gs_bar[1] += 1;               // (every workgroup of k_graph_step2 is done)
@@ -2654,20 +2598,15 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_adam(float* __restrict__ p, cons
                                                        float* __restrict__ m1, float* __restrict__ m2, int64_t n,
                                                        float step_size, float inv_sqrt_bc2, float beta1, float beta2,
                                                        float eps, float wd, int64_t* ctrl, int tick, FinishArgs fin) {
+  // (the six scalars of an AdamHyper stay six arguments: as one by-value block they are no longer loaded together with ctrl,
+  //  three scalar loads where one stands)
   __shared__ float smf[8];
-  if (ctrl) {      // hipGraph replay: the scalars live in HBM
-    const double* d = (const double*)ctrl;
-    step_size = (float)d[IGMC_CTRL_STEP_SIZE];
-    inv_sqrt_bc2 = (float)d[IGMC_CTRL_INV_SQRT_BC2];
-    beta1 = (float)d[IGMC_CTRL_BETA1];
-    beta2 = (float)d[IGMC_CTRL_BETA2];
-    eps = (float)d[IGMC_CTRL_EPS];
-    wd = (float)d[IGMC_CTRL_WD];
-  }
+  AdamHyper h = {step_size, inv_sqrt_bc2, beta1, beta2, eps, wd};
+  if (ctrl) h = adam_hyper_from_ctrl(ctrl);      // hipGraph replay
   {   // a contiguous slice per workgroup, eight elements a thread and round with all their loads in flight (adam_range)
     const int64_t chunk = ((n + gridDim.x - 1) / gridDim.x + IGMC_BLOCK - 1) / IGMC_BLOCK * IGMC_BLOCK;
     const int64_t lo = (int64_t)blockIdx.x * chunk, hi = (lo + chunk < n) ? lo + chunk : n;
-    if (lo < n) adam_range<8>(p, g, m1, m2, lo, hi, step_size, inv_sqrt_bc2, beta1, beta2, eps, wd);
+    if (lo < n) adam_range<8>(p, g, m1, m2, lo, hi, h);
   }
   if (fin.enabled && blockIdx.x == 0) loss_body(fin.b, fin.m, fin.ARR, fin.loss, fin.total, smf);
   if (ctrl && tick) {
@@ -2686,7 +2625,6 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_adam(float* __restrict__ p, cons
 }
 
 // =================================================================== host launch sequences
-#include "launch.h"
 
 // grid for row-parallel kernels: enough workgroups for the capacity, capped, and a multiple of 8 (>= 8) so
 // that every XCD residue owns workgroups (XCD-affine segments, see igmc_xcd_segment)
@@ -2717,6 +2655,14 @@ static inline int igmc_l0_grid(const ModelDev& m, int B) {
   return igmc_xcd_grid(m, B, rows, IGMC_GATHER_BLOCKS);
 }
 
+// k_rgcn_layer4's instantiations by their flags: the launches take their kernel from here, igmc_model_prepare walks all four
+using RgcnKernel = decltype(&k_rgcn_layer4<false, false>);
+static RgcnKernel rgcn_layer_kernel(bool use_flags, bool bwd) {
+  RgcnKernel k = nullptr;
+  igmc_dispatch([&](auto uf, auto bw) { k = k_rgcn_layer4<uf(), bw()>; }, use_flags, bwd);
+  return k;
+}
+
 // ---- the phases of a call, each written once; sp (launch.h: StepPlan) says which kernels take them
 
 // The four conv layers (h_0..h_3 left in HBM): all of them in ONE launch (k_dl_fwd; nothing follows that would advance its
@@ -2741,9 +2687,7 @@ static void launch_conv_fwd(const ModelDev& m, const BatchDev& b, const StepPlan
     // the top layer's launch also clears dPre_3 (only its target rows are written by the head backward)
     float* zo = (training && l == 3) ? m.dpre[3] : nullptr;
     if (sp.dl) igmc_launch_dl_layer(m, b, P, B, l, 0, use_flags, zo, stream);
-    else igmc_dispatch([&](auto uf) {
-      IGMC_PLAUNCH("k_rgcn_layer_fwd", (k_rgcn_layer4<uf(), false>), gt, IGMC_BLOCK, fsm4, stream, b, m, P, l, zo);
-    }, use_flags != 0);
+    else IGMC_PLAUNCH("k_rgcn_layer_fwd", rgcn_layer_kernel(use_flags != 0, false), gt, IGMC_BLOCK, fsm4, stream, b, m, P, l, zo);
   }
   if (training && sp.need_y)
     IGMC_PLAUNCH("k_dense_y_all", k_dense_y_all, dim3(igmc_rows_grid(m.node_cap, 64, 512), 3), IGMC_BLOCK,
@@ -2758,9 +2702,8 @@ static void launch_layers_bwd(const ModelDev& m, const BatchDev& b, const StepPl
   const size_t bsm4 = (size_t)(16 * IGMC_TP + 1024 + m.R * 4 + 16 * m.R * 4) * sizeof(float);
   for (int l = 3; l >= 1; --l) {
     if (sp.bwd_dense) igmc_launch_dl_layer(m, b, P, B, l, 1, use_flags, nullptr, stream, tables);
-    else igmc_dispatch([&](auto uf) {
-      IGMC_PLAUNCH("k_rgcn_layer_bwd", (k_rgcn_layer4<uf(), true>), gt, IGMC_BLOCK, bsm4, stream, b, m, P, l, (float*)nullptr);
-    }, use_flags != 0);
+    else IGMC_PLAUNCH("k_rgcn_layer_bwd", rgcn_layer_kernel(use_flags != 0, true), gt, IGMC_BLOCK, bsm4, stream, b, m, P, l,
+                      (float*)nullptr);
   }
 }
 
@@ -2798,12 +2741,10 @@ static void launch_tail_fin(const ModelDev& m, const BatchDev& b, const float* P
     const char* role = getenv("IGMC_EMU_FOLD_MUTE_ROLE");
     if (mute >= 0 && role) mute |= (!strcmp(role, "rows") ? 1 : !strcmp(role, "bias") ? 2 : 0) << 8;
   }
+#endif
   // the mains of a layer wait for each other's words and for producers: aligned groups of 32 consecutive workgroups run
   // together, one group after the other (layout: above k_tail_fin)
-  hipemu::rt().co_cs = 32;
-  hipemu::rt().co_stride = -1;
-  hipemu::rt().co_block = 0;
-#endif
+  igmc_emu_cluster(32, -1, 0);
   const int nconv = 96 + m.L, nsets = (8 * (m.R + 1) + 15) / 16, nprod = ((nsets - 1) * nconv + 4 + 31) & ~31;
   IGMC_PLAUNCH("k_tail_fin", k_tail_fin, nprod + nconv + nlin + 1, IGMC_BLOCK, (size_t)IGMC_TF_WORDS * sizeof(float), stream, b, m, P,
                grad_scale, mult, 2.f, grad, arr_coef, at, nlin, nparts, stride, B, bump_seq, mute, l3v);
@@ -2839,25 +2780,25 @@ static void launch_finalize(const ModelDev& m, const BatchDev& b, const float* P
 
 // ---- the public sequences
 
-void igmc_launch_forward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, const float* P, int B, int training,
-                         int use_flags, const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult,
-                         float* out, void* stream) {
-  if (sp.family == IGMC_FAM_G2) {      // (evaluation only: IGMC_CALL_EVAL)
-    igmc_launch_graph_step2(m, b, sp, P, B, 0, use_flags, nullptr, seed, step, mult, 0.f, out, stream);
+void igmc_launch_forward(const ModelDev& m, const BatchDev& b, const StepPlan& sp, int B, int training, int use_flags,
+                         const StepHead& hd, void* stream) {
+  if (sp.family == IGMC_FAM_G2) {      // (evaluation only: IGMC_CALL_EVAL -- no dropout mask, no loss gradient)
+    const StepHead ev = {hd.P, nullptr, hd.seed, hd.step, hd.mult, 0.f, hd.out};
+    igmc_launch_graph_step2(m, b, sp, B, 0, use_flags, ev, stream);
     return;
   }
-  launch_conv_fwd(m, b, sp, P, B, training, use_flags, stream);
+  launch_conv_fwd(m, b, sp, hd.P, B, training, use_flags, stream);
   const int hgrid = (B + IGMC_HG - 1) / IGMC_HG;
   const size_t fs = (size_t)IGMC_HG * m.D * sizeof(float);
   if (m.D % 16 == 0)
-    IGMC_PLAUNCH("k_head_fwd", k_head_fwd_mfma, (B + 15) / 16, 512, 0, stream, b, m, P, training, inj_mask, seed, step,
-                 mult, out);
+    IGMC_PLAUNCH("k_head_fwd", k_head_fwd_mfma, (B + 15) / 16, 512, 0, stream, b, m, hd.P, training, hd.inj_mask, hd.seed,
+                 hd.step, hd.mult, hd.out);
   else if (fs <= 48 * 1024)
-    IGMC_PLAUNCH("k_head_fwd", (k_head_fwd<true>), hgrid, 512, fs, stream, b, m, P, training, inj_mask, seed, step,
-                 mult, out);
+    IGMC_PLAUNCH("k_head_fwd", (k_head_fwd<true>), hgrid, 512, fs, stream, b, m, hd.P, training, hd.inj_mask, hd.seed,
+                 hd.step, hd.mult, hd.out);
   else
-    IGMC_PLAUNCH("k_head_fwd", (k_head_fwd<false>), hgrid, 512, 0, stream, b, m, P, training, inj_mask, seed, step,
-                 mult, out);
+    IGMC_PLAUNCH("k_head_fwd", (k_head_fwd<false>), hgrid, 512, 0, stream, b, m, hd.P, training, hd.inj_mask, hd.seed,
+                 hd.step, hd.mult, hd.out);
 }
 
 // The four conv layers alone, whatever the readout that follows (centre-node readout of IGMC: igmc_launch_forward; sort-pool
@@ -2915,10 +2856,9 @@ void igmc_launch_conv_backward(const ModelDev& m, const BatchDev& b, const StepP
 //   subgraph kernel:   k_graph_step (all of it down to per-workgroup tables), k_tail_ts, finalize
 //   dense + tables:    k_dl_fwd | layers, {head in k_dl_bwd | k_head_sub + k_dl_bwd | k_head_sub + 3 x layer_bwd}, k_tail_ts, finalize
 //   per layer:         l0_fwd, 3 x layer_fwd, {head fwd+bwd | Y}, 3 x layer_bwd, {weight grads | lin grads}, reduce, finalize
-int igmc_launch_loss_grad(const ModelDev& m_in, const BatchDev& b, const StepPlan& sp, float* P, int B, int use_flags,
-                          const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float ARR,
-                          float grad_scale, float arr_scale, float* out, float* grad, float* loss, const AdamTail* adam,
-                          void* stream, const StepExchange* xch, int* img_emitted) {
+int igmc_launch_loss_grad(const ModelDev& m_in, const BatchDev& b, const StepPlan& sp, int B, int use_flags, const StepHead& hd,
+                          float ARR, float arr_scale, float* grad, float* loss, const AdamTail* adam, void* stream,
+                          const StepExchange* xch, int* img_emitted) {
   ModelDev m = m_in;
   m.adam_m1 = adam ? adam->m1 : nullptr;       // (the stash roles keep att's moments of before the step)
   m.adam_m2 = adam ? adam->m2 : nullptr;
@@ -2927,7 +2867,8 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const BatchDev& b, const StepPla
   // the gradient / Adam kernel also leaves the weight images of the updated parameters
   const int img = adam && m.g2_w && m.R <= G2_NR * G2_NG_MAX && rows0 <= (g2_t0_rows(m.R, m.L) == 32 ? 32 : 48);
   const int ny = (m.D / 16 + 3) / 4;
-  const float* Pc = P;
+  const float* Pc = hd.P;
+  const float grad_scale = hd.grad_scale, mult = hd.mult;
   AdamTail at;
   memset(&at, 0, sizeof(at));
   if (adam) {
@@ -2940,11 +2881,10 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const BatchDev& b, const StepPla
   at.skip = xch ? xch->failed : nullptr;
   const int64_t* ctrl = adam ? at.ctrl : nullptr;
   if (!sp.fast_head) {      // generic sequence
-    igmc_launch_forward(m, b, sp, Pc, B, 1, use_flags, inj_mask, seed, step, mult, out, stream);
+    igmc_launch_forward(m, b, sp, B, 1, use_flags, hd, stream);
     igmc_launch_backward(m, b, sp, Pc, B, use_flags, nullptr, 1, grad_scale, mult, 2.f, ARR * arr_scale, grad, stream);
     if (adam) {
-      igmc_launch_finish(m, b, at.p, grad, at.m1, at.m2, at.step_size, at.inv_sqrt_bc2, at.beta1, at.beta2, at.eps, at.wd,
-                         at.ctrl, ARR, at.loss, at.total, use_flags, stream);
+      igmc_launch_finish(m, b, at.p, grad, at.m1, at.m2, at.h, at.ctrl, ARR, at.loss, at.total, use_flags, stream);
     } else if (loss) {
       igmc_launch_loss(m, b, ARR, loss, stream);
     }
@@ -2958,8 +2898,7 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const BatchDev& b, const StepPla
     // kernel, whose launch then carries the stash role (four more workgroups)
     const int fold = sp.tail_fold && tables && adam && at.enabled && img && !xch;
     const int stride = (sp.cs > 1) ? ((B + 7) & ~7) : IGMC_TS_BLOCKS;
-    const int bump_seq = igmc_launch_graph_step2(m, b, sp, Pc, B, 1, use_flags, inj_mask, seed, step, mult, grad_scale, out, stream,
-                                                 fold ? 4 : 0, ctrl);
+    const int bump_seq = igmc_launch_graph_step2(m, b, sp, B, 1, use_flags, hd, stream, fold ? 4 : 0, ctrl);
     if (fold) {
       launch_tail_fin(m, b, Pc, B, grad_scale, mult, grad, ARR * arr_scale, at, 8 * ny, sp.grid, stride, bump_seq, sp.l3_vec, stream);
       if (img_emitted) *img_emitted = 1;
@@ -2972,9 +2911,8 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const BatchDev& b, const StepPla
     if (sp.dlts) {
       // the head: in the set-up of the one-launch backward (side features included), or one workgroup per subgraph in front of
       // the backward -- one launch, or one per layer
-      const DlHead hd = {Pc, inj_mask, seed, step, mult, grad_scale, out};
       const int inside = sp.dlb && sp.head_inside;
-      if (!inside) igmc_launch_head_sub(m, b, Pc, B, inj_mask, seed, step, mult, grad_scale, out, stream);
+      if (!inside) igmc_launch_head_sub(m, b, B, hd, stream);
       if (sp.dlb) igmc_launch_dl_bwd(m, b, sp, B, use_flags, stream, inside ? &hd : nullptr);
       else launch_layers_bwd(m, b, sp, Pc, B, use_flags, 1, stream);
       const int gstride = (B + 7) & ~7;
@@ -2982,7 +2920,7 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const BatchDev& b, const StepPla
     } else {
       const int gy = igmc_rows_grid(m.node_cap, 128, 512), hb = (B + 15) / 16, nsl = rows0 <= 32 ? 4 : 3;
       IGMC_PLAUNCH("k_head_train", k_head_train, dim3(hb > gy ? hb : gy, 4), 512, (size_t)32 * (128 + 4) * sizeof(float), stream,
-                   b, m, Pc, inj_mask, seed, step, mult, grad_scale, out);
+                   b, m, Pc, hd.inj_mask, hd.seed, hd.step, mult, grad_scale, hd.out);
       launch_layers_bwd(m, b, sp, Pc, B, use_flags, 0, stream);
       IGMC_PLAUNCH("k_wgrad_head", k_wgrad_head, dim3(IGMC_WG_BLOCKS, nsl + 1), IGMC_BLOCK, 0, stream, b, m, Pc,
                    (const float*)nullptr, 1, grad_scale, mult, 2.f, grad, nsl);
@@ -2993,21 +2931,6 @@ int igmc_launch_loss_grad(const ModelDev& m_in, const BatchDev& b, const StepPla
   if (const int rc = launch_exchange(m, sp.tail, xch, grad, stream)) return rc;
   launch_finalize(m, b, Pc, grad, ARR * arr_scale, sp.tail, sp.family == IGMC_FAM_G2, at, img, ARR, loss, img_emitted, stream);
   return 0;
-}
-
-int igmc_launch_train_step(const ModelDev& m, const BatchDev& b, const StepPlan& sp, float* P, int B, int use_flags,
-                           const uint8_t* inj_mask, uint64_t seed, uint64_t step, float mult, float ARR, float* out,
-                           float* grad, float* m1, float* m2, float step_size, float inv_sqrt_bc2, float beta1,
-                           float beta2, float eps, float wd, int64_t* ctrl, int* done, float* loss, double* total,
-                           void* stream, float grad_scale, const StepExchange* xch, int* img_emitted) {
-  AdamTail at;
-  memset(&at, 0, sizeof(at));
-  at.p = P; at.m1 = m1; at.m2 = m2;
-  at.step_size = step_size; at.inv_sqrt_bc2 = inv_sqrt_bc2; at.beta1 = beta1; at.beta2 = beta2; at.eps = eps; at.wd = wd;
-  at.ctrl = ctrl; at.done = done; at.loss = loss; at.total = total;
-  return igmc_launch_loss_grad(m, b, sp, P, B, use_flags, inj_mask, seed, step, mult, ARR,
-                               grad_scale != 0.f ? grad_scale : 1.0f / (float)B, 1.0f, out, grad, nullptr, &at, stream, xch,
-                               img_emitted);
 }
 
 void igmc_launch_loss(const ModelDev& m, const BatchDev& b, float ARR, float* loss, void* stream) {
@@ -3035,18 +2958,16 @@ static int adam_grid(int64_t n) {
   return grid < 1 ? 1 : grid;
 }
 
-void igmc_launch_adam(float* p, const float* g, float* m1, float* m2, int64_t n, float step_size,
-                      float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd, int64_t* ctrl, int tick,
+void igmc_launch_adam(float* p, const float* g, float* m1, float* m2, int64_t n, const AdamHyper& h, int64_t* ctrl, int tick,
                       void* stream) {
   FinishArgs fin;
   memset(&fin, 0, sizeof(fin));
-  IGMC_PLAUNCH("k_adam", k_adam, adam_grid(n), IGMC_BLOCK, 0, stream, p, g, m1, m2, n, step_size, inv_sqrt_bc2, beta1,
-               beta2, eps, wd, ctrl, tick, fin);
+  IGMC_PLAUNCH("k_adam", k_adam, adam_grid(n), IGMC_BLOCK, 0, stream, p, g, m1, m2, n, h.step_size, h.inv_sqrt_bc2, h.beta1, h.beta2,
+               h.eps, h.wd, ctrl, tick, fin);
 }
 
 // Adam + loss + epoch total (+ control-block tick) in ONE launch
-void igmc_launch_finish(const ModelDev& m, const BatchDev& b, float* p, const float* g, float* m1, float* m2,
-                        float step_size, float inv_sqrt_bc2, float beta1, float beta2, float eps, float wd,
+void igmc_launch_finish(const ModelDev& m, const BatchDev& b, float* p, const float* g, float* m1, float* m2, const AdamHyper& h,
                         int64_t* ctrl, float ARR, float* loss, double* total, int use_flags, void* stream) {
   FinishArgs fin;
   fin.enabled = 1;
@@ -3057,7 +2978,7 @@ void igmc_launch_finish(const ModelDev& m, const BatchDev& b, float* p, const fl
   fin.loss = loss;
   fin.total = total;
   IGMC_PLAUNCH("k_step_finish", k_adam, adam_grid(m.n_params), IGMC_BLOCK, 0, stream, p, g, m1, m2,
-               (int64_t)m.n_params, step_size, inv_sqrt_bc2, beta1, beta2, eps, wd, ctrl, ctrl ? 1 : 0, fin);
+               (int64_t)m.n_params, h.step_size, h.inv_sqrt_bc2, h.beta1, h.beta2, h.eps, h.wd, ctrl, ctrl ? 1 : 0, fin);
 }
 
 int igmc_model_prepare(const ModelDev& m) {
@@ -3066,8 +2987,8 @@ int igmc_model_prepare(const ModelDev& m) {
   const int bsm4 = (int)((size_t)(16 * IGMC_TP + 1024 + m.R * 4 + 16 * m.R * 4) * sizeof(float));
   if (bsm4 > 48 * 1024) {
     if (bsm4 > 150 * 1024) return 1;
-    if (hipFuncSetAttribute((const void*)k_rgcn_layer4<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bsm4) != hipSuccess) return 1;
-    if (hipFuncSetAttribute((const void*)k_rgcn_layer4<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bsm4) != hipSuccess) return 1;
+    for (int v = 0; v < 4; ++v)      // (the backward's size: the forward's is smaller)
+      if (hipFuncSetAttribute((const void*)rgcn_layer_kernel(v & 1, v & 2), hipFuncAttributeMaxDynamicSharedMemorySize, bsm4) != hipSuccess) return 1;
   }
 #endif
   (void)m;

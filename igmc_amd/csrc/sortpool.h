@@ -1,6 +1,6 @@
 // sortpool.h -- device view + launchers of the sort-pool readout (sortpool.hip; reference models.py:63-167)
 #pragma once
-#include "model.h"
+#include "launch.h"      // StepHead
 
 struct SpDev {
   int k, Q1, Q2, dense;     // pooled rows, rows after MaxPool1d(2,2), after Conv1d(16,32,5), flattened width 32 * Q2
@@ -27,8 +27,9 @@ struct SpDev {
 int igmc_sp_lds_ok(const SpDev& sp);
 int igmc_sp_prepare(const SpDev& sp);
 void igmc_launch_sp_pack(const ModelDev& m, const SpDev& sp, const float* Pd, float* pe, void* stream);
-void igmc_launch_sp_forward(const ModelDev& m, const SpDev& sp, const BatchDev& b, const float* Pd, int B, int training,
-                            const uint8_t* inj_mask, uint64_t seed, uint64_t step, float* out, void* stream);
+// (hd: P = the true parameters, inj_mask / seed / step / out; mult and grad_scale are not read)
+void igmc_launch_sp_forward(const ModelDev& m, const SpDev& sp, const BatchDev& b, int B, int training, const StepHead& hd,
+                            void* stream);
 void igmc_launch_sp_backward(const ModelDev& m, const SpDev& sp, const BatchDev& b, const float* Pd, int B, float grad_scale,
                              void* stream);
 void igmc_launch_sp_wgrad(const ModelDev& m, const SpDev& sp, const BatchDev& b, int B, const float* ge, float* Gd,

@@ -659,12 +659,20 @@ static size_t sp_bwd_lds(const SpDev& sp) {
 
 int igmc_sp_lds_ok(const SpDev& sp) { return sp_fwd_lds(sp) <= 160 * 1024 && sp_bwd_lds(sp) <= 160 * 1024; }
 
+// k_sp_fwd's instantiations by their flag: the launch takes its kernel from here, igmc_sp_prepare walks both
+using SpFwdKernel = decltype(&k_sp_fwd<true>);
+static SpFwdKernel sp_fwd_kernel(bool training) {
+  SpFwdKernel k = nullptr;
+  igmc_dispatch([&](auto tr) { k = k_sp_fwd<tr()>; }, training);
+  return k;
+}
+
 int igmc_sp_prepare(const SpDev& sp) {
 #ifndef IGMC_HIPEMU
-  const int fw = (int)sp_fwd_lds(sp), bw = (int)sp_bwd_lds(sp);
-  if (hipFuncSetAttribute((const void*)k_sp_fwd<true>, hipFuncAttributeMaxDynamicSharedMemorySize, fw) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_sp_fwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, fw) != hipSuccess) return 1;
-  if (hipFuncSetAttribute((const void*)k_sp_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, bw) != hipSuccess) return 1;
+  const void* fns[3] = {(const void*)sp_fwd_kernel(false), (const void*)sp_fwd_kernel(true), (const void*)k_sp_bwd};
+  for (int i = 0; i < 3; ++i)
+    if (hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)(i < 2 ? sp_fwd_lds(sp) : sp_bwd_lds(sp))) != hipSuccess)
+      return 1;
 #else
   (void)sp;
 #endif
@@ -675,16 +683,14 @@ void igmc_launch_sp_pack(const ModelDev& m, const SpDev& sp, const float* Pd, fl
   IGMC_PLAUNCH("k_sp_pack", k_sp_pack, 64, SP_THREADS, 0, stream, m, sp, Pd, pe);
 }
 
-void igmc_launch_sp_forward(const ModelDev& m, const SpDev& sp, const BatchDev& b, const float* Pd, int B, int training,
-                            const uint8_t* inj_mask, uint64_t seed, uint64_t step, float* out, void* stream) {
-  const size_t sm = sp_fwd_lds(sp);
-  if (training) {
-    IGMC_PLAUNCH("k_sp_fwd", (k_sp_fwd<true>), B, SP_WG, sm, stream, b, m, sp, Pd, inj_mask, seed, step, out);
-    IGMC_PLAUNCH("k_sp_lin_fwd", (k_sp_lin_fwd<true>), dim3((B + 15) / 16, 8), SP_THREADS, 0, stream, b, m, sp, Pd, inj_mask, seed, step, out);
-  } else {
-    IGMC_PLAUNCH("k_sp_fwd", (k_sp_fwd<false>), B, SP_WG, sm, stream, b, m, sp, Pd, inj_mask, seed, step, out);
-    IGMC_PLAUNCH("k_sp_lin_fwd", (k_sp_lin_fwd<false>), dim3((B + 15) / 16, 8), SP_THREADS, 0, stream, b, m, sp, Pd, inj_mask, seed, step, out);
-  }
+void igmc_launch_sp_forward(const ModelDev& m, const SpDev& sp, const BatchDev& b, int B, int training, const StepHead& hd,
+                            void* stream) {
+  IGMC_PLAUNCH("k_sp_fwd", sp_fwd_kernel(training != 0), B, SP_WG, sp_fwd_lds(sp), stream, b, m, sp, hd.P, hd.inj_mask, hd.seed,
+               hd.step, hd.out);
+  igmc_dispatch([&](auto tr) {
+    IGMC_PLAUNCH("k_sp_lin_fwd", (k_sp_lin_fwd<tr()>), dim3((B + 15) / 16, 8), SP_THREADS, 0, stream, b, m, sp, hd.P, hd.inj_mask,
+                 hd.seed, hd.step, hd.out);
+  }, training != 0);
 }
 
 void igmc_launch_sp_backward(const ModelDev& m, const SpDev& sp, const BatchDev& b, const float* Pd, int B, float grad_scale,

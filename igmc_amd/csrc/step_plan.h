@@ -78,10 +78,6 @@ static int g2_eligible(const StepHooks& hk, const ModelDev& m, const BatchDev& b
 }
 
 // ---- the dense-layer kernels
-static int dl_kp(const BatchDev& b) {
-  const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
-  return 32 * ((cmax + 31) >> 5) + 8;
-}
 // 1 = the dense per-layer kernels take the conv layers of this arena
 static int dl_base_ok(const StepHooks& hk, const ModelDev& m, const BatchDev& b, int B, int wide) {
   if (hk.dl == 0) return 0;
