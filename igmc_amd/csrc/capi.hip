@@ -966,6 +966,7 @@ extern "C" int igmc_model_create(int device, int num_relations, int num_bases, i
   if (d.R <= 128) fail |= M.get(&d.fin_stash, (size_t)4 * IGMC_STASH_LAYER + 16);     // weights-only stash of k_finalize_ts (both modes)
   d.g2_ex = nullptr;
   d.g2_fx = nullptr;
+  d.g2_tw = nullptr;
   d.g2_px = nullptr;
   d.g2_px_stride = 0;
   d.g2_w = nullptr;
@@ -985,6 +986,7 @@ extern "C" int igmc_model_create(int device, int num_relations, int num_bases, i
     if (d.R <= G2_NR && Bc <= 1024) {
       d.g2_px_stride = (size_t)Bc * 2 * 32768;
       fail |= M.get(&d.g2_px, 5 * d.g2_px_stride);
+      fail |= M.get(&d.g2_tw, Bc * IGMC_G2_TW_WORDS);      // centre-sum words of layer 3's forward (20 KB per subgraph slot)
     } else if (d.R <= G2_NR) {
       static bool told = false;
       if (!told) fprintf(stderr, "[igmc] batches of more than 1024 subgraphs: no plane-exchange regions -- the dense-layer / per-layer kernels take the steps, not the subgraph kernel\n");
@@ -1036,6 +1038,7 @@ extern "C" int igmc_model_create(int device, int num_relations, int num_bases, i
     HIPCHECK(hipMemset(m->d.g2_ex, 0, 5 * m->d.g2_ex_stride * sizeof(unsigned long long)));
     HIPCHECK(hipMemset(m->d.g2_fx, 0, (size_t)max_graphs * 256 * sizeof(unsigned long long)));
     if (m->d.g2_px) HIPCHECK(hipMemset(m->d.g2_px, 0, 5 * m->d.g2_px_stride));      // flags 0 (never a launch's tag), planes finite
+    if (m->d.g2_tw) HIPCHECK(hipMemset(m->d.g2_tw, 0, (size_t)max_graphs * IGMC_G2_TW_WORDS * sizeof(unsigned long long)));
   }
   if (igmc_model_prepare(d)) {
     M.release();
@@ -1065,6 +1068,32 @@ extern "C" int igmc_debug_head_array(const igmc_model* m, int which, float* h_ou
   if (n < 0 || n > (int64_t)m->d.graph_cap * (which < 2 ? 128 : m->d.D)) IGMC_FAIL("size out of range");
   HIPCHECK(hipDeviceSynchronize());
   HIPCHECK(hipMemcpy(h_out, src, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// debug aid (tests): host copy of what the last TRAINING launch of the subgraph kernel left of conv layer 3's centre rows -- which = 0:
+// the centre vectors ModelDev::l3_vec [graphs][2 sides][G2_NR + 2][32] (rows r < R: the summed T_r[centre]; clustered steps under
+// StepPlan::l3_vec), 1: the h_2 rows the kernel stored for its backward, which the sums were formed from, per subgraph slot of the
+// arena `b` as [graphs][2 sides][128 rows][32] (rows past a side's capacity are left as the caller set them).  n floats: a whole
+// number of subgraphs.  Synchronises the device.
+extern "C" int igmc_debug_l3_sums(const igmc_model* m, const igmc_batch* b, int which, float* h_out, int64_t n) {
+  if (!m || !b || !h_out) IGMC_FAIL("null argument");
+  if (which < 0 || which > 1) IGMC_FAIL("no such array");
+  const int64_t per = which == 0 ? 2 * (G2_NR + 2) * 32 : 2 * 128 * 32;
+  if (n < 0 || n % per != 0 || n / per > (int64_t)m->d.graph_cap || n / per > (int64_t)b->d.graph_cap) IGMC_FAIL("size out of range");
+  HIPCHECK(hipDeviceSynchronize());
+  if (which == 0) {
+    if (!m->d.l3_vec) IGMC_FAIL("array not allocated");
+    HIPCHECK(hipMemcpy(h_out, m->d.l3_vec, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+  }
+  if ((int64_t)b->d.graph_cap * b->d.slot > (int64_t)m->d.node_cap) IGMC_FAIL("the arena's slots exceed the workspace");
+  for (int64_t g = 0; g < n / per; ++g)
+    for (int sd = 0; sd < 2; ++sd) {
+      const int rows = std::min(sd ? b->d.cap_v : b->d.cap_u, 128);
+      HIPCHECK(hipMemcpy(h_out + (g * 2 + sd) * 128 * 32, m->d.h[2] + ((size_t)g * b->d.slot + (sd ? b->d.cap_u : 0)) * 32,
+                         (size_t)rows * 32 * sizeof(float), hipMemcpyDeviceToHost));
+    }
   return 0;
 }
 
@@ -1707,6 +1736,7 @@ extern "C" int igmc_model_reset_exchange(igmc_model* m, void* stream) {
     HIPCHECK(hipMemsetAsync(m->d.g2_ex, 0, 5 * m->d.g2_ex_stride * sizeof(unsigned long long), st));
     HIPCHECK(hipMemsetAsync(m->d.g2_fx, 0, (size_t)m->d.g2_graphs * 256 * sizeof(unsigned long long), st));
     if (m->d.g2_px) HIPCHECK(hipMemsetAsync(m->d.g2_px, 0, 5 * m->d.g2_px_stride, st));
+    if (m->d.g2_tw) HIPCHECK(hipMemsetAsync(m->d.g2_tw, 0, (size_t)m->d.g2_graphs * IGMC_G2_TW_WORDS * sizeof(unsigned long long), st));
   }
   return 0;
 }

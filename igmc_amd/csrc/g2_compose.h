@@ -93,7 +93,7 @@ __global__ __launch_bounds__(G2C_THREADS) void k_g2_compose(ModelDev m, const fl
 // LDS plan + eligibility for a batch arena / cluster size
 static int igmc_g2_layout(const ModelDev& m, const BatchDev& b, int cs, G2Layout* lay) {
   const int RL = m.R * m.L;
-  if (m.S != 0 || m.D != 256 || m.R > G2_NR || m.L > 8 || RL + m.L + 1 > 32 || !m.ts_part || !m.g2_px || !m.g2_fx || !m.g2_w || !b.relm) return 0;
+  if (m.S != 0 || m.D != 256 || m.R > G2_NR || m.L > 8 || RL + m.L + 1 > 32 || !m.ts_part || !m.g2_px || !m.g2_fx || !m.g2_tw || !m.g2_w || !b.relm) return 0;
   const int half = 2 * cs;
   const int cmax = b.cap_u > b.cap_v ? b.cap_u : b.cap_v;
   if (cmax > 16 * half || cmax > 128) return 0;
@@ -190,7 +190,7 @@ int igmc_launch_graph_step2(const ModelDev& m, const BatchDev& b, const StepPlan
     a.off_bias[l] = (int)m.off_bias[l];
   }
   a.l3_vec = (training && cs > 1 && sp.l3_vec) ? m.l3_vec : nullptr;
-  a.ts_part = m.ts_part; a.g2_px = m.g2_px; a.g2_fx = m.g2_fx; a.g2_px_stride = m.g2_px_stride; a.g2_w = m.g2_w;
+  a.ts_part = m.ts_part; a.g2_px = m.g2_px; a.g2_fx = m.g2_fx; a.g2_tw = m.g2_tw; a.g2_px_stride = m.g2_px_stride; a.g2_w = m.g2_w;
   a.gs_bar = m.gs_bar; a.gs_err = m.gs_err; a.a1 = m.a1; a.dz = m.dz; a.feat = m.feat; a.gfeat = m.gfeat; a.err = m.err;
   a.lmask = m.lmask; a.ctrl = m.ctrl;
   a.off_basis3 = (int)m.off_basis[3]; a.off_att3 = (int)m.off_att[3]; a.off_root3 = (int)m.off_root[3];

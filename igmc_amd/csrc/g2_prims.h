@@ -116,6 +116,13 @@ __device__ __forceinline__ void g2_glds16(const float4* src_wave, float4* lds_wa
 
 #include "g2_words.h"      // the 8-byte {f32, tag} words: g2_pub_f32 / g2_poll_f32
 
+// ---- centre-sum words of the subgraph kernel (ModelDev::g2_tw; layer 3's forward, g2_subgraph.h) ------------------------
+// Region of one subgraph: [centre side][bundle of the OPPOSITE side <= G2_TW_BUN][G2_NR][32 features] {f32, tag} words, written
+// like the readout words (g2_pub_f32: writer and readers on one XCD) under the launch's readout tag, by the waves that form h_2.
+#define G2_TW_BUN IGMC_G2_TW_BUN
+#define G2_TW_WORDS IGMC_G2_TW_WORDS
+static_assert(G2_TW_WORDS == 2 * G2_TW_BUN * G2_NR * 32, "a slot holds every (side, bundle, relation, feature) word");
+
 // ---- plane exchange of the subgraph kernel (k_graph_step2) ------------------------------------------------------------
 // The members of a cluster sit on ONE XCD (graphstep2.hip: workgroup -> (subgraph, member)), so the rows they exchange can
 // stay in that XCD's L2: the producer writes bf16 term planes [term][feature][node] -- the very image the gather reads from

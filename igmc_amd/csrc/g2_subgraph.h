@@ -21,6 +21,7 @@ struct G2Args {
                                // (NULL: as a table in every workgroup's slot of ts_part)
   unsigned char* g2_px;       // plane exchange regions [5 exchanges][graphs][2 sides][G2_PX_BYTES] (g2_prims.h)
   unsigned long long* g2_fx;
+  unsigned long long* g2_tw;   // centre-sum words [graphs][G2_TW_WORDS] (g2_prims.h): layer 3's forward
   size_t g2_px_stride;         // bytes per exchange
   const float* g2_w;
   int* gs_bar;
@@ -82,8 +83,12 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
   float* misc = sred + 512;               // [16]
   // layer 3 only feeds the readout, so dPre_3 lives on the two centre rows and its backward is a closed form (TRAIN):
   float* D3 = sred + 256;                 // [2 sides][32] dPre_3 of the side's centre row (upper half of sred: free behind the head)
-  float* TC = TILES + (G2_THREADS / 64) * 256;      // [2 sides][G2_NR][32] T_r of the centre row, left by layer 3's forward gather
+  float* TC = TILES + (G2_THREADS / 64) * 256;      // [2 sides][G2_NR][32] T_r of the centre row, summed from the centre-sum words
                                           // (behind the head's d feat partials; T' tiles are not written before backward layer 2)
+  // layer 3's forward in closed form (every member, both centres): operands and partials of its 2 x 5 matvecs, in the pair
+  // partials' region (dead between layer 2's epilogue -- the barrier behind the poll -- and backward layer 2)
+  float* UB = PXA;                        // [2 sides][4 bases + root][32] U_b = sum_r att[r,b] T_r[c], then h_2[c]
+  float* PV = PXA + 2 * 5 * 32;           // [2 sides][4 bases + root][32] U_b @ basis_b, h_2[c] @ root
   float* QV = HSS;                        // [2 sides][4 bases + root][32] basis_b . dPre_3, root . dPre_3 (h tiles: dead until backward layer 2)
   float* ATT3 = S + lay.att;              // [R][4] att of layer 3
   const int R = a.R, L = a.L, RL = R * L;
@@ -298,6 +303,26 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
         }
       }
     }
+    // relation of the kept edge  row -> c_opp (the opposite side's centre): byte 0 of k-step 0, held -- masked by the row's
+    // validity, `active` and n_opp like every fragment -- by lane (row, kq = 0); keep bit of the direction own -> opposite, as
+    // in frag_b.  Layer 2's epilogue (the centre-row sums of layer 3's forward) and backward layer 3 read this one value -- as
+    // relq, the relations of the lane's OWN four rows 4 kq + rr of both epilogues (byte rr; 0xFF: no kept edge): the four
+    // cross-lane reads leave together, here, under the set-up's latencies, not one round trip each inside the epilogues.
+    uint32_t relq = 0u;
+    {
+      int relv = -1;
+      if constexpr (FLAGS) {
+        const uint32_t b0 = RB[0][0] & 0xFFu, code = b0 & IGMC_RELM_CODE;
+        if (code >= 1u && code <= (uint32_t)R && ((b0 >> kb) & 1u)) relv = (int)code - 1;
+      } else {
+#pragma unroll
+        for (int r = 0; r < G2_NR; ++r)
+          if (r < R && (AM[r][0][0] & 0xFFu)) relv = r;
+      }
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) relq |= ((uint32_t)__shfl(relv, 4 * kq + rr) & 0xFFu) << (8 * rr);
+    }
+    auto rel_of = [&](int rr) { return (int)(int8_t)(relq >> (8 * rr)); };      // -1: none
     // (opaque copies: the compiler would otherwise form all 20 fragments once and keep them -- the 80 registers again)
     auto frag_f = [&](int r, int s) {
       uint32_t m0 = AM[r][s][0], m1 = AM[r][s][1];
@@ -344,17 +369,38 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
       }
       // the planes and their flag FIRST (what the other side waits for: the flag's wait covers three 8-byte stores only);
       // the wave's own copies -- LDS tile, h_l rows for the backward, the readout word -- go out behind it
-      if (l < 3) {
+      // (h_2 crosses no workgroup as planes: its only reader was layer 3's gather -- exchange region 2 stays unused)
+      if (l < 2) {
         g2_publish_planes(px_of(l, side), kp, 16 * nt + li, row0 + 4 * kq, v);
         g2_flag_raise(px_of(l, side), 2 * bi + hf, xtag(l), lane);
-      }
-      // (h_3 is read by the readout alone, on the centre rows, which travel in the readout words: no tile, no a.h[3])
-      if (l < 3) {
+      } else {
+        // Layer 3 feeds the readout alone, on the two centre rows: its aggregate T_r[c_opp] = sum of h_2[j] over the rows j whose
+        // kept edge j -> c_opp has relation r is summed HERE, where h_2 is formed -- the lane's four rows, then the four row
+        // groups (kq), a fixed order -- and leaves as the bundle's {f32, tag} words [centre side][bundle][r][feature]; the
+        // consumers (every member, in front of the head) add the bundles in index order.  A bundle none of whose rows reaches
+        // the centre publishes zeros; an inactive bundle never gets here and is not read.
+        // (all G2_NR sums take each step together -- no branch between them, so the cross-lane reads of a step share one round
+        //  trip; the sums of absent relations r >= R are zeros that nobody stores)
+        float s[G2_NR];
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          xo[rr * G2_XP + 16 * nt] = v[rr];
-          if (TRAIN && row0 + 4 * kq + rr < n_own) hrow[rr * 32 + 16 * nt] = v[rr];
+        for (int r = 0; r < G2_NR; ++r)
+          s[r] = ((rel_of(0) == r ? v[0] : 0.f) + (rel_of(1) == r ? v[1] : 0.f)) + ((rel_of(2) == r ? v[2] : 0.f) + (rel_of(3) == r ? v[3] : 0.f));
+#pragma unroll
+        for (int r = 0; r < G2_NR; ++r) s[r] += __shfl_xor(s[r], 16);
+#pragma unroll
+        for (int r = 0; r < G2_NR; ++r) s[r] += __shfl_xor(s[r], 32);
+        if (kq == 0) {
+          unsigned long long* tw = a.g2_tw + (size_t)g * G2_TW_WORDS + (size_t)(((1 - side) * G2_TW_BUN + bi) * G2_NR) * 32 + 16 * nt + li;
+#pragma unroll
+          for (int r = 0; r < G2_NR; ++r)
+            if (r < R) g2_pub_f32(tw + r * 32, s[r], tag0 + G2_FXTAG);
         }
+      }
+      // (h_3 is read by the readout alone, on the centre rows, and formed by every member from the words above: no tile, no a.h[3])
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        xo[rr * G2_XP + 16 * nt] = v[rr];
+        if (TRAIN && row0 + 4 * kq + rr < n_own) hrow[rr * 32 + 16 * nt] = v[rr];
       }
       if (bi == 0 && kq == 0) g2_pub_f32(fx + side * 128 + l * 32 + 16 * nt + li, v[0], tag0 + G2_FXTAG);
     };
@@ -417,51 +463,54 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
     }
     G2_STAMP(5);
 
-    // ================================================================ conv layers 1..3, forward
+    // (the wave's sixteen lin1 rows of the head stay in registers: d feat = dz @ lin1.weight needs exactly these rows and columns
+    //  again -- a second round trip to the weights, behind a data-dependent row selection, was 2 k cycles of the chain.)
+    // Nothing of lin1 depends on the readout, and its 128 KB a workgroup are 2 k cycles of the CU's vector-memory path alone
+    // (64 bytes a clock), whoever waits for them: the straight-line variants request the rows in front of layer 2's PAIR BARRIER,
+    // where a wave idles ~1.5 k cycles for the other wave of its SIMD and the registers of gather and transform are free again --
+    // they stream under that wait, layer 2's epilogue and the poll of layer 3.  (In front of the poll, behind the epilogue, the
+    // poll's own words queue up behind them: measured, no gain.  The looping variants hold the loop's state in registers as
+    // well and spill with the rows live that long: they request them behind the closed form's products.)
+    float4 w4[16];
+    auto lin1_rows = [&]() {
+      const float* wrow = P + a.off_l1w + (int64_t)(16 * wave) * 256 + 4 * lane;
 #pragma unroll
-    for (int l = 1; l < 4; ++l) {
+      for (int q = 0; q < 16; ++q) w4[q] = *(const float4*)(wrow + q * 256);
+    };
+    // ================================================================ conv layers 1..2, forward
+    // (layer 3 feeds the readout alone, on the two centre rows: it runs in closed form in front of the head, below)
+#pragma unroll
+    for (int l = 1; l < 3; ++l) {
       float* XOc = (l & 1) ? XO0 : XO1;             // x of the bundle's own rows (h_{l-1})
       float* XOn = (l & 1) ? XO1 : XO0;             // h_l
       G2_STAMP(6 + 3 * (l - 1));
-      // Layer 3 runs on the centre bundles only: the readout takes h_3 of the two target rows and nothing else reads it.  A
-      // workgroup without a centre bundle skips the layer as a whole (uniform: its barriers go with it; what they ordered --
-      // the pair's halves of h_2, the reuse of PX -- is ordered by the barrier behind the readout poll).
-      const bool lrun = l < 3 || wg_centre;
-      const bool act = active && (l < 3 || bi == 0);
-      float bias0 = 0.f;
-      if (lrun) {
-        bias0 = P[a.off_bias[l] + 16 * hf + li];
-        // the opposite side's h_{l-1} as bf16 planes, and the layer's weight image (the previous one died at the previous
-        // layer's barrier): both global -> LDS, landed by the barrier below
-        fetch(l - 1);
-        if (l > 1) wload(l, 0);
-        __syncthreads();
-      }
+      float bias0 = P[a.off_bias[l] + 16 * hf + li];
+      // the opposite side's h_{l-1} as bf16 planes, and the layer's weight image (the previous one died at the previous
+      // layer's barrier): both global -> LDS, landed by the barrier below
+      fetch(l - 1);
+      if (l > 1) wload(l, 0);
+      __syncthreads();
       G2_STAMP(7 + 3 * (l - 1));
-      if (lrun) {
+      {
         float bias0_ = bias0;                       // landed: no wait for it is left inside the epilogue (a wait there
         G2_OPAQUE(bias0_);                          // would also drain the epilogue's own stores, one round trip each)
         f32x4 o[2];
-        if (act) {
+        if (active) {
           int lane_ = lane;
           G2_OPAQUE(lane_);
           const int li_ = lane_ & 15, kq_ = lane_ >> 4;
           f32x4 acc[G2_NR];
           g2_gather_h(pl, kp, nks, frag_f, li_, kq_, hf, acc);
           if (l == 2) G2_STAMP(40);
-          if (TRAIN && l == 3 && li_ == 0) {
-            // T_r of the centre row (features 16 hf + 4 kq ..): the layer-3 weight gradient is its outer product with dPre_3
-#pragma unroll
-            for (int r = 0; r < G2_NR; ++r)
-              *(float4*)(TC + side * (G2_NR * 32) + r * 32 + 16 * hf + 4 * kq_) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
-          }
           g2_transform_h(acc, XOc, (const uint32_t*)sW2, li_, kq_, hf, o);
           if (l == 2) G2_STAMP(41);
           *PXo = hf ? o[0] : o[1];                    // the partner's tile: this wave's half of its K
         }
+        if constexpr (ONCE)
+          if (l == 2) lin1_rows();                    // (every wave, idle bundles' too: the head is computed by all of them)
         __syncthreads();                              // the pair's partials are exchanged (planes / sW2 are dead as well)
         if (l == 2) G2_STAMP(42);
-        if (act) {
+        if (active) {
           const f32x4 po = *PXi;
           f32x4 of;
 #pragma unroll
@@ -474,7 +523,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
       //  is next read behind a fetch that copies all of it)
       G2_STAMP(36 + (l - 1));
       // (no barrier here: planes / sW2 were dead at the barrier above; the pair's two halves of h_l in XOn and the reuse of
-      //  PX are ordered by the next phase's barrier -- behind the next layer's reload, or the readout poll)
+      //  PX are ordered by the next phase's barrier -- behind the next layer's reload, or the poll in front of the head)
       G2_STAMP(8 + 3 * (l - 1));
     }
 
@@ -486,11 +535,12 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
     const int ju_h = 16 * wave + ((lane >> 1) & 15);
     float hd_l1b = P[a.off_l1b + ju_h], hd_l2w = P[a.off_l2w + ju_h], hd_l2b = P[a.off_l2b], hd_y = a.y[g];
     float hd_l2wt = TRAIN ? P[a.off_l2w + (tid & 127)] : 0.f;
-    float hd_att3 = (TRAIN && tid < 4 * R) ? P[a.off_att3 + tid] : 0.f;
-    if (TRAIN) {
-      // layer 3's bases and root in f32, global -> LDS into the weight region (its last image died at the last pair barrier this
-      // workgroup ran; the next one is requested behind the closed-form backward of layer 3): 16 + 4 pieces of 1 KB, landed
-      // by the head's barriers
+    float hd_att3 = (tid < 4 * R) ? P[a.off_att3 + tid] : 0.f;
+    float hd_b3 = (tid < 64) ? P[a.off_bias[3] + (tid & 31)] : 0.f;
+    {
+      // layer 3's bases and root in f32, global -> LDS into the weight region (its last image died at layer 2's pair barrier;
+      // TRAIN: the next one is requested behind the closed-form backward of layer 3): 16 + 4 pieces of 1 KB, landed by the
+      // barrier behind the poll.  Forward (below) and backward of layer 3 read them.
 #pragma unroll
       for (int j = 0; j < 3; ++j) {
         const int c = wave + j * (G2_THREADS / 64);
@@ -498,17 +548,101 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
                               (float4*)sW2 + c * 64, lane);
       }
     }
-    if (tid < 256) sfeat[tid] = g2_poll_f32(fx + tid, tag0 + G2_FXTAG, a.gs_err);
-    __syncthreads();
-    G2_OPAQUE(hd_l1b); G2_OPAQUE(hd_l2w); G2_OPAQUE(hd_l2b); G2_OPAQUE(hd_y); G2_OPAQUE(hd_l2wt);      // (landed with the poll)
-    if (TRAIN) {
-      G2_OPAQUE(hd_att3);
-      if (tid < 4 * R) ATT3[tid] = hd_att3;
+    G2_STAMP(12);
+    // ================================================================ conv layer 3, forward, in closed form: every member forms
+    // h_3 of BOTH centre rows -- all the readout takes of the layer -- from the centre-row sums the producers of h_2 left:
+    //     T_r[c] = sum over the opposite side's active bundles, in index order, of the bundle's word   (2 x G2_NR x 32 sums)
+    //     h_3[c] = tanh(sum_b (sum_r att[r,b] T_r[c]) @ basis_b + h_2[c] @ root + bias)              (2 x 5 matvecs 32 x 32)
+    // ONE bounded poll: a thread requests the <= 8 bundle words of its sum and its readout word (h_0 .. h_2 of the centres)
+    // together and looks again at those whose tag is not this launch's.  It waits for exactly the waves whose flags layer 3's
+    // plane fetch waited for, and those publish before they wait for anything further.
+    {
+      const int sdc = (tid >= G2_NR * 32) ? 1 : 0, rt = (tid - sdc * (G2_NR * 32)) >> 5;      // (tid < 2 * G2_NR * 32: centre side, relation)
+      const int nb = (tid < 2 * G2_NR * 32 && rt < R) ? (((sdc ? cu : cv) + 15) >> 4) : 0;      // active bundles of the OPPOSITE side
+      const bool has_rd = tid < 256 && (tid & 127) < 96;
+      const unsigned long long* tp = a.g2_tw + (size_t)g * G2_TW_WORDS + (size_t)(sdc * G2_TW_BUN * G2_NR * 32) + (tid - sdc * (G2_NR * 32));
+      const uint32_t tg = tag0 + G2_FXTAG;
+      unsigned long long wd[G2_TW_BUN], wr = 0ull;
+      uint32_t pend = (has_rd ? (1u << G2_TW_BUN) : 0u) | ((1u << nb) - 1u);
+#pragma unroll
+      for (int b2 = 0; b2 < G2_TW_BUN; ++b2) wd[b2] = 0ull;
+      for (long it = 0; pend; ++it) {
+#pragma unroll
+        for (int b2 = 0; b2 < G2_TW_BUN; ++b2)
+          if ((pend >> b2) & 1u) wd[b2] = g2_ld_word(tp + b2 * (G2_NR * 32));
+        if ((pend >> G2_TW_BUN) & 1u) wr = g2_ld_word(fx + tid);
+#pragma unroll
+        for (int b2 = 0; b2 < G2_TW_BUN; ++b2)
+          if (((pend >> b2) & 1u) && (uint32_t)(wd[b2] >> 32) == tg) pend &= ~(1u << b2);
+        if (((pend >> G2_TW_BUN) & 1u) && (uint32_t)(wr >> 32) == tg) pend &= ~(1u << G2_TW_BUN);
+        if (!pend) break;
+        if (it > (1L << 22)) {      // (the backstop of every exchange: StepGraph.check() reports it; what did not arrive counts as zero)
+          *a.gs_err = 1;
+#pragma unroll
+          for (int b2 = 0; b2 < G2_TW_BUN; ++b2)
+            if ((pend >> b2) & 1u) wd[b2] = 0ull;
+          if ((pend >> G2_TW_BUN) & 1u) wr = 0ull;
+          break;
+        }
+        g2_poll_pause();
+      }
+      if (tid < 2 * G2_NR * 32) {
+        float tsum = 0.f;
+#pragma unroll
+        for (int b2 = 0; b2 < G2_TW_BUN; ++b2)
+          if (b2 < nb) tsum += __uint_as_float((uint32_t)wd[b2]);
+        TC[tid] = tsum;             // [side][r][feature]; rows r >= R, and a centre without neighbours: exact zeros
+      }
+      if (has_rd) sfeat[tid] = __uint_as_float((uint32_t)wr);
+      if (tid < 4 * R) ATT3[tid] = hd_att3;      // (requested in front of the poll's words: landed with them)
     }
+    __syncthreads();
+    G2_OPAQUE(hd_l1b); G2_OPAQUE(hd_l2w); G2_OPAQUE(hd_l2b); G2_OPAQUE(hd_y); G2_OPAQUE(hd_l2wt); G2_OPAQUE(hd_b3);      // (landed with the poll)
+    G2_STAMP(13);
+    if (tid < 2 * 4 * 32) {
+      // U_b = sum_r att[r,b] T_r[c], in relation order
+      const int sd = tid >> 7, b = (tid >> 5) & 3, k = tid & 31;
+      float u = 0.f;
+#pragma unroll
+      for (int r = 0; r < G2_NR; ++r)
+        if (r < R) u = fmaf(ATT3[4 * r + b], TC[sd * (G2_NR * 32) + r * 32 + k], u);
+      UB[sd * 160 + b * 32 + k] = u;
+    } else if (tid < 2 * 5 * 32) {
+      const int sd = (tid - 256) >> 5, k = tid & 31;
+      UB[sd * 160 + 128 + k] = sfeat[sd * 128 + 64 + k];      // h_2[c]: root's operand
+    }
+    __syncthreads();
+    if (tid < 2 * 5 * 32) {
+      // one output of one matvec per thread, x @ M: the matrices are [in][out], so consecutive threads read consecutive words
+      // of a row -- no bank conflict, no rotation; x is a broadcast.  Every operand is read in front of the first product, as in
+      // the backward's q phase (an asm statement is a scheduling barrier: reads left at their products are a round trip each)
+      const int sd = tid / 160, mi = tid - sd * 160;
+      const float* wc = (const float*)sW2 + (mi >> 5) * 1024 + (mi & 31);
+      const float* xr = UB + sd * 160 + (mi >> 5) * 32;
+      float wv[32], xv[32];
+#pragma unroll
+      for (int i = 0; i < 32; ++i) {
+        wv[i] = wc[i * 32];
+        xv[i] = xr[i];
+      }
+      G2_SCHED_BARRIER();
+      float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+      for (int i = 0; i < 32; i += 2) {
+        DL_FMAC(s0, wv[i], xv[i]);
+        DL_FMAC(s1, wv[i + 1], xv[i + 1]);
+      }
+      PV[tid] = s0 + s1;
+    }
+    if constexpr (!ONCE) lin1_rows();
+    __syncthreads();
+    G2_STAMP(14);
+    if (tid < 64) {
+      const float* pv = PV + (tid >> 5) * 160 + (tid & 31);
+      sfeat[(tid >> 5) * 128 + 96 + (tid & 31)] = g2_tanh((((pv[0] + pv[32]) + (pv[64] + pv[96])) + pv[128]) + hd_b3);
+    }
+    __syncthreads();
     G2_STAMP(15);
-    // (the wave's sixteen lin1 rows stay in registers: d feat = dz @ lin1.weight below needs exactly these rows and columns
-    //  again -- a second round trip to the weights, behind a data-dependent row selection, was 2 k cycles of the chain)
-    float4 w4[16];
     {
       // lin1 (256 -> 128): wave w takes hidden units 16 w .. 16 w + 15.  One weight row (1 KB, 8 cache lines) per load
       // instruction, lane = 4 consecutive fan-in columns; the 16 per-lane partial dot products are then reduced over the
@@ -517,11 +651,8 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
       // cache lines per load instruction -- kept the head at ~10 k cycles.)
       const int ju = 16 * wave + ((lane >> 1) & 15), part = (lane & 1) | (lane >> 5);     // hidden unit of this lane; part 0 stores
       const float4 f4 = *(const float4*)(sfeat + 4 * lane);
-      const float* wrow = P + a.off_l1w + (int64_t)(16 * wave) * 256 + 4 * lane;
       float v[16];
-      {                                      // 16 rows: all 16 requests leave before the first use
-#pragma unroll
-        for (int q = 0; q < 16; ++q) w4[q] = *(const float4*)(wrow + q * 256);
+      {                                      // (the 16 rows were requested in front of the poll)
         G2_SCHED_BARRIER();
 #pragma unroll
         for (int q = 0; q < 16; ++q) v[q] = (w4[q].x * f4.x + w4[q].y * f4.y) + (w4[q].z * f4.z + w4[q].w * f4.w);
@@ -710,24 +841,14 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
           float v[4];
           f32x4 dx;
           if (l == 3) {
-            // relation of the kept edge  row -> c_opp: byte 0 of k-step 0, held (masked by the row's validity, `active` and
-            // n_opp like every fragment) by lane (row, kq = 0); keep bit of the direction own -> opposite, as in frag_b
-            int relv = -1;
-            if constexpr (FLAGS) {
-              const uint32_t b0 = RB[0][0] & 0xFFu, code = b0 & IGMC_RELM_CODE;
-              if (code >= 1u && code <= (uint32_t)R && ((b0 >> kb) & 1u)) relv = (int)code - 1;
-            } else {
-#pragma unroll
-              for (int r = 0; r < G2_NR; ++r)
-                if (r < R && (AM[r][0][0] & 0xFFu)) relv = r;
-            }
+            // (rel_of: the relation of the kept edge  row -> c_opp, formed in the set-up)
             const float* qo = QV + (1 - side) * 160 + f;
             const float q0 = qo[0], q1 = qo[32], q2 = qo[64], q3 = qo[96];
             const float rootc = QV[side * 160 + 128 + f];
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
               const int row = 4 * kq + rr;
-              const int rl = __shfl(relv, row);
+              const int rl = rel_of(rr);
               float d = 0.f;
               if (rl >= 0) {
                 const float4 a4 = *(const float4*)(ATT3 + 4 * rl);

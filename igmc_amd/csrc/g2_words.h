@@ -37,6 +37,15 @@ __device__ __forceinline__ unsigned long long g2_ld_word(const unsigned long lon
 #endif
 }
 
+// between two looks of a polling loop that holds several words
+__device__ __forceinline__ void g2_poll_pause() {
+#ifndef IGMC_HIPEMU
+  __builtin_amdgcn_s_sleep(2);
+#else
+  hipemu::yield();
+#endif
+}
+
 // one 8-byte {f32, tag} word, polled
 __device__ __forceinline__ float g2_poll_f32(const unsigned long long* p, uint32_t tag, int* err) {
   for (long it = 0;; ++it) {

@@ -27,9 +27,9 @@
 // XCD's L2 -- ORDINARY stores of the planes into the exchange region of (exchange, subgraph, side), a wait for their
 // acknowledgement, ONE flag word per wave; the consumer polls the flags of the opposite side's bundles (sc1 loads) and copies
 // the planes global -> LDS directly (global_load_lds).  No tagged data words, no sc1 stores, no tag wrap.  dPre_3 is non-zero
-// on the two target rows only and is formed locally from the head's d feat -- layer 3 runs forward on the centre bundles only
-// and backward in closed form (g2_subgraph.h) --: 5 exchanges per launch (h_0, h_1, h_2, dPre_2, dPre_1) + the 256-float
-// centre-node readout (8-byte {f32, tag} words, polled).
+// on the two target rows only and is formed locally from the head's d feat -- layer 3 runs forward and backward in closed form
+// on the two centre rows (g2_subgraph.h) --: 4 plane exchanges per launch (h_0, h_1, dPre_2, dPre_1; region 2, once h_2's, is
+// unused) + the centre-node readout of h_0 .. h_2 and layer 3's centre-row sums (8-byte {f32, tag} words, polled).
 //
 // This translation unit in five files: graphstep2.hip (this one: the shared gather / transform steps),
 // g2_subgraph.h (k_graph_step2), g2_compose.h (k_g2_compose, layout and launch of the subgraph kernel),

@@ -13,7 +13,10 @@
 #define IGMC_FOLD_O_ROWS (4 * 32 * IGMC_FOLD_NA)
 #define IGMC_FOLD_O_BIAS (IGMC_FOLD_O_ROWS + 4 * 32 * IGMC_FOLD_PSETS * 64)
 #define IGMC_FOLD_WORDS (IGMC_FOLD_O_BIAS + 4 * 32)
-#define IGMC_TS_BLOCKS 256   // partial slots of the relation-space tables (one per workgroup of k_graph_step)
+// the centre-sum words of the subgraph kernel (ModelDev::g2_tw): bundles a side (16 rows each, <= 128 rows), words a subgraph slot
+#define IGMC_G2_TW_BUN 8
+#define IGMC_G2_TW_WORDS (2 * IGMC_G2_TW_BUN * 5 * 32)
+#define IGMC_TS_BLOCKS 256  // partial slots of the relation-space tables (one per workgroup of k_graph_step)
 #define IGMC_GATHER_BLOCKS 4096   // max grid of the row-walker kernels (4 rows = 4 waves per block)
 // The basis-space mode of the gradient / Adam tail (k_finalize_ts) is correct up to 128 relations (the stash holds them) but only pays up to 32: its per-relation
 // loops (ARR matrix and value in the stash role, layer 0's d att) are serial in R -- yahoo_music's 71 relations measured
@@ -67,6 +70,9 @@ struct ModelDev {
   unsigned long long* g2_ex;   // graphstep2: [5 exchanges][g2_graphs][2 sides][32 features][128 nodes] {hi, mid, lo, tag} words
   size_t g2_ex_stride;         // words per exchange
   unsigned long long* g2_fx;   // [g2_graphs][256] {f32, tag} words of the centre-node readout
+  unsigned long long* g2_tw;   // [g2_graphs][IGMC_G2_TW_WORDS] {f32, tag} words of layer 3's centre-row sums: [centre side][bundle of the
+                               // opposite side][5 relations][32] -- the bundle's sum of h_2 over its rows whose kept edge to the centre
+                               // has the relation (g2_subgraph.h: layer 2's epilogue writes, every member reads); tag 0: never a launch's
   unsigned char* g2_px;        // k_graph_step2's plane exchange: [5 exchanges][g2_graphs][2 sides][32 KB] (g2_prims.h); null: not allocated
   size_t g2_px_stride;         // bytes per exchange
   int g2_graphs;               // subgraph slots of the two buffers above (0: not allocated)

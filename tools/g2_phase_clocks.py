@@ -20,7 +20,8 @@ from igmc_amd.util_functions import MyDynamicDataset  # noqa: E402
 
 NAMES = {1: 'T0 table staged', 2: 'labels + zero fills', 3: 'relm staged + one-hot planes', 4: 'A fragments built', 5: 'layer 0',
          6: 'L1 stage W', 7: 'L1 reload h0', 8: 'L1 compute + sync', 9: 'L2 stage W', 10: 'L2 reload h1', 11: 'L2 compute + sync',
-         12: 'L3 stage W', 13: 'L3 reload h2 (centre wg)', 14: 'L3 centre bundle + sync', 15: 'readout polled', 16: 'head forward',
+         12: 'L3 bases + lin1 rows asked', 13: 'L3 sums + readout polled', 14: 'L3 U_b + ten matvecs', 15: 'L3 h_3 + sync',
+         16: 'head forward',
          17: 'd feat + dPre3 centre rows', 18: 'B3 q = basis,root . dPre3', 19: 'B3 layer start', 20: 'B3 sync + closed-form dX',
          21: 'B3 (no phase)', 22: 'B3 rank-1 tables', 23: 'B3 reload dPre2',
          24: 'B2 layer start', 25: 'B2 wave compute + d bias1', 26: 'B2 sync', 27: 'B2 table product', 28: 'B2 reload dPre1',
@@ -32,6 +33,10 @@ NAMES = {1: 'T0 table staged', 2: 'labels + zero fills', 3: 'relm staged + one-h
 #  and a library from before that change shows its own phases under these lines: 18 = dPre3 centre rows + d bias3, 20 = B3 wave
 #  compute (gather, tiles, transform) + d bias2, 22 = B3 table product.  Stamp 22 keeps its label where layer 3 leaves centre
 #  vectors instead of tables (StepPlan::l3_vec): the phase is then the next image's request + 56 stores in a centre member)
+#  Layer 3's forward runs in closed form in every member: stamps 12..15 are its phases -- requests issued, the one poll (centre-sum
+#  and readout words) + barrier, U_b and the matvecs, h_3 -- and a library from before that change shows under these lines its own
+#  12 = L3 stage W, 13 = L3 reload h2 (centre workgroups), 14 = L3 centre bundle + sync, 15 = readout polled.  The lin1 rows are
+#  requested in phase 12 now, so 'head forward' no longer holds their round trip.)
 ORDER = [k for k in range(1, 36) if k not in (19, 24, 29)]
 
 
@@ -71,7 +76,7 @@ def main():
         a2 = c[64 + k] - c[64 + p]
         print('%-28s %8d | %8d' % (NAMES[k], a0, a2))
     print('total                        %8d | %8d' % (c[35] - c[0], c[99] - c[64]))
-    for l in (1, 2, 3):
+    for l in (1, 2, 3) if c[38] else (1, 2):      # (stamp 38: a library whose layer 3 still runs a centre bundle)
         print('L%d fwd: wave 0 compute alone %d | %d' % (l, c[36 + l - 1] - c[7 + 3 * (l - 1)], c[100 + l - 1] - c[71 + 3 * (l - 1)]))
     fine(c)
     if c[55] and c[56] >= c[55]:          # (a library with the deferred tail: the wait for the previous step's tail)
