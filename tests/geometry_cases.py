@@ -1,7 +1,10 @@
-"""The launch geometries of a training step (``igmc_model_step_geometry``) that the batch size, the slot capacities, the
-relation count, the hop count and the side-feature width select -- one row on each side of every threshold of
-``gs_cluster`` / ``igmc_g2_layout`` (step_plan.h, g2_compose.h), ``dl_split`` (dl_kernels.h) / ``dl_*_eligible`` /
-``dl_wide`` / ``dl_gsplit`` (step_plan.h) and the dense block of ``igmc_batch_create`` (capi.hip).
+"""The launch geometries of a training step (``igmc_model_step_geometry``) that the batch size, the slot capacities and the
+side-feature width select -- one row on each side of every threshold that B and the slot extents cross in ``gs_cluster`` /
+``igmc_g2_layout`` (step_plan.h, g2_compose.h), ``dl_split`` (dl_kernels.h) / ``dl_*_eligible`` / ``dl_wide`` /
+``dl_gsplit`` (step_plan.h) and the dense block of ``igmc_batch_create`` (capi.hip).  The relation count is 5 or 10 and the
+label count 4 throughout, but for one two-hop row at R = 5 (a 37-row layer-0 table): the thresholds the relation and label
+counts cross -- the (R, L) plane -- are the rows of tests/relation_label_checks.py (tests/test_emu_relation_labels.py,
+tests/test_gpu_relation_labels.py).
 
 tests/test_gpu_geometry.py runs every row against the oracle on an MI355X; tests/test_emu_geometry.py checks the query's
 answer for every row on the CPU (the emulator picks the clusters an MI355X picks when ``IGMC_GS_CLUSTER=4``)."""
@@ -75,7 +78,8 @@ FAMILIES = ('rows', 'subgraph', 'dense_fused', 'dense_layer')
 
 def geometry_kinds(geometries):
     """What a set of geometries covers: kernel families, subgraph-kernel forms (workgroups per subgraph, looping grid),
-    dense splits with and without tables, relation groups with and without the split."""
+    dense splits with and without tables (``dense_fused_tables0``: the one-launch forward whose backward leaves no tables),
+    relation groups with and without the split."""
     kinds = set()
     for g, B in geometries:
         kinds.add(g['family'])
