@@ -103,6 +103,16 @@ def build_parser():
                         'the device; the user\'s other held-out items stay in the list) instead of among all of them')
     p.add_argument('--rank-draw', type=int, default=0, metavar='D',
                    help='--rank-negatives: which draw of the negatives (default 0); another D gives another sample')
+    p.add_argument('--cold-start', default=None, metavar='K[,K...]',
+                   help='--rank-eval: the Given-K cold-start evaluation instead -- per level K every chosen user is cut down to '
+                        'K ratings ON THE DEVICE (a uniform K-subset of the row stays), the removed ratings and the held-out '
+                        'links are ranked over the reduced graph; writes coldstart_<data>.tsv; users with no more than max(K) '
+                        'ratings are skipped.  1 to 8 levels >= 0.  Not with --new-ratings')
+    p.add_argument('--cold-users', default=None, metavar='K|FILE',
+                   help='--cold-start: the users that go cold, as --recommend-users names users (default: all -- "a cold '
+                        'system"; a few -- "a cold user in a warm system")')
+    p.add_argument('--cold-draw', type=int, default=0, metavar='D',
+                   help='--cold-start: which draw of the kept subsets (default 0); another D gives another split')
     p.add_argument('--shortlist', type=int, default=None, metavar='M',
                    help='--recommend / --rank-eval / --explain of the recommended pairs: score only every user\'s M unseen items '
                         'with the most co-rating votes ("people who liked what you liked also liked", counted on the device) '
@@ -393,6 +403,69 @@ def write_ranking(model, train_graphs, heldout_graphs, args):
     return path
 
 
+def cold_start_levels(spec):
+    """``--cold-start 1,2,5``: the given levels, 1 to 8 distinct integers >= 0; None where ``spec`` is malformed."""
+    try:
+        levels = [int(x) for x in spec.split(',')]
+    except (ValueError, AttributeError):
+        return None
+    if not 1 <= len(levels) <= 8 or min(levels) < 0 or len(set(levels)) != len(levels):
+        return None
+    return levels
+
+
+def cold_start_flag_error(cold_start, cold_users, cold_draw, rank_eval, new_ratings):
+    """The argument error of ``--cold-start`` / ``--cold-users`` / ``--cold-draw`` in this combination of flags, or None."""
+    if cold_start is None:
+        if cold_users is not None:
+            return '--cold-users names the users of --cold-start K[,K...]: give its levels'
+        if cold_draw:
+            return '--cold-draw names the draw of --cold-start K[,K...]: give its levels'
+        return None
+    if cold_start_levels(cold_start) is None:
+        return '--cold-start takes 1 to 8 distinct comma-separated levels K >= 0, e.g. 1,2,5,10'
+    if cold_draw < 0:
+        return '--cold-draw takes D >= 0'
+    if not rank_eval:
+        return '--cold-start ranks at the cut-offs of --rank-eval K[,K...]: give them'
+    if new_ratings:
+        return '--cold-start and --new-ratings exclude one another: the split removes ratings from the training graph itself'
+    return None
+
+
+def write_cold_start(model, train_graphs, heldout_graphs, args):
+    """``--cold-start``: ``<res_dir>/coldstart_<data_name>.tsv`` with lines ``given\tblock\tmetric\tvalue`` -- ``given`` a level
+    or ``full``; block ``heldout``: the removed ratings and the held-out links of the level's users ranked over the reduced
+    graph, ``extra``: the same ranks with the held-out links alone counted (``full``: over the unreduced graph, what
+    ``--rank-eval`` reports for those users) -- (``igmc_amd/rank_eval.py``: ``cold_start_eval`` and its two caveats)."""
+    from igmc_amd.rank_eval import cold_start_eval, metric_names
+    ks = rank_eval_ks(args.rank_eval)
+    levels = cold_start_levels(args.cold_start)
+    users = recommend_users(args.cold_users, train_graphs.graph.n_users)
+    kw = shortlist_kwargs(args)
+    if args.rank_negatives is not None:
+        kw.update(negatives=args.rank_negatives, negatives_draw=args.rank_draw)
+    stats = {}
+    res = cold_start_eval(model, train_graphs, given=levels, users=users, extra=heldout_graphs, ks=ks, draw=args.cold_draw,
+                          min_rating=args.rank_min_rating, stats=stats, batch_size=args.batch_size, **kw)
+    names = metric_names(ks)
+    path = os.path.join(args.res_dir, 'coldstart_{}.tsv'.format(args.data_name))
+    with open(path, 'w') as f:
+        for given in levels + ['full']:
+            for block in ('heldout', 'extra'):
+                if block in res[given]:
+                    for k in names:
+                        f.write('%s\t%s\t%s\t%.6f\n' % (given, block, k, res[given][block][k]))
+    print('Cold start: {} users with more than {} ratings ({} skipped)'.format(stats['users'], max(levels), stats['users_skipped']))
+    for given in levels + ['full']:
+        print('Given {}: {}'.format(given, '; '.join(
+            '{} (means over {} users) {}'.format(block, res[given][block]['users_evaluated'],
+                                                 ', '.join('%s %.4f' % (k, res[given][block][k]) for k in names))
+            for block in ('heldout', 'extra') if block in res[given])))
+    print('wrote {}'.format(path))
+    return path
+
+
 def apply_new_ratings(train_graphs, class_values, args):
     """``--new-ratings FILE``: the training set's extraction settings over its rating graph after the file's changes
     (``engine.Graph.updated``: built on the device, the training graph itself stays as it is)."""
@@ -426,6 +499,9 @@ def main(argv=None):
     if args.rank_draw < 0:
         parser.error('--rank-draw takes D >= 0')
     bad = shortlist_flag_error(args.shortlist, args.shortlist_min_rating, args.rank_negatives, args.recommend > 0 or args.rank_eval)
+    if bad:
+        parser.error(bad)
+    bad = cold_start_flag_error(args.cold_start, args.cold_users, args.cold_draw, args.rank_eval, args.new_ratings)
     if bad:
         parser.error(bad)
     if args.explain < 0 or args.explain > 64:
@@ -611,7 +687,9 @@ def main(argv=None):
             over = apply_new_ratings(train_graphs, class_values, args) if args.new_ratings else train_graphs
             if args.recommend > 0:
                 write_recommendations(model, over, args)
-            if args.rank_eval:
+            if args.rank_eval and args.cold_start:
+                write_cold_start(model, over, test_graphs, args)
+            elif args.rank_eval:
                 write_ranking(model, over, test_graphs, args)
             if args.explain > 0:
                 write_explanations(model, over, class_values, args)

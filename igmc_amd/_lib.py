@@ -79,6 +79,8 @@ SIGNATURES = {
     'igmc_candidates_fill': (i32, [vp, vp, i32, vp, i32, vp, vp, vp, i64, vp, vp]),
     'igmc_candidates_sample_count': (i32, [vp, vp, i32, vp, i32, vp, vp, i64, i64, vp, vp, vp]),
     'igmc_candidates_sample_fill': (i32, [vp, vp, i32, vp, i32, vp, vp, i64, i64, u64, u64, vp, vp, vp, vp, i64, vp, vp]),
+    'igmc_holdout_count': (i32, [vp, vp, i32, i64, i64, vp, vp, vp]),
+    'igmc_holdout_fill': (i32, [vp, vp, i32, i64, i64, u64, u64, vp, vp, vp, vp, i64, vp, vp]),
     'igmc_pair_negatives': (i32, [vp, vp, vp, i64, vp, u64, u64, vp, vp, vp, vp, vp]),
     'igmc_pair_negatives_shortlist': (i32, [vp, vp, vp, i64, vp, u64, u64, vp, vp, i64, f64, vp, vp, vp, vp, vp]),
     'igmc_pair_kind_stats': (i32, [vp, vp, i32, vp, vp]),

@@ -1420,6 +1420,49 @@ extern "C" int igmc_candidates_sample_fill(const igmc_graph* g, const int32_t* d
   return 0;
 }
 
+// ------------------------------------------------------------------ the Given-k split (holdout.hip)
+// what both entry points take; returns the refusal, or null
+static const char* hold_args(HoldArgs* a, const igmc_graph* g, const int32_t* d_users, int nq, int64_t keep, int64_t hold,
+                             int32_t* d_err) {
+  if (!g || !d_users || !d_err) return "null argument";
+  if (nq < 0) return "nq must be at least 0";
+  if (keep < 0) return "keep must be at least 0";
+  if (hold < 0) return "hold must be at least 0";
+  *a = HoldArgs{g->d, d_users, nq, keep, hold};
+  a->err = d_err;
+  return nullptr;
+}
+extern "C" int igmc_holdout_count(const igmc_graph* g, const int32_t* d_users, int nq, int64_t keep, int64_t hold,
+                                  int64_t* d_counts, int32_t* d_err, void* stream) {
+  HoldArgs a;
+  const char* bad = hold_args(&a, g, d_users, nq, keep, hold, d_err);
+  if (bad) IGMC_FAIL(bad);
+  if (!d_counts) IGMC_FAIL("null argument");
+  a.counts = d_counts;
+  igmc_launch_holdout(a, 0, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int igmc_holdout_fill(const igmc_graph* g, const int32_t* d_users, int nq, int64_t keep, int64_t hold, uint64_t seed,
+                                 uint64_t draw, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v,
+                                 uint8_t* d_rating, int64_t capacity, int32_t* d_err, void* stream) {
+  HoldArgs a;
+  const char* bad = hold_args(&a, g, d_users, nq, keep, hold, d_err);
+  if (bad) IGMC_FAIL(bad);
+  if (!d_offsets || !d_link_u || !d_link_v || !d_rating) IGMC_FAIL("null argument");
+  if (capacity < 0) IGMC_FAIL("capacity must be at least 0");
+  a.seed = seed;
+  a.draw = draw;
+  a.off = d_offsets;
+  a.link_u = d_link_u;
+  a.link_v = d_link_v;
+  a.rating = d_rating;
+  a.capacity = capacity;
+  igmc_launch_holdout(a, 1, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
 // ------------------------------------------------------------------ pair training (pairs.hip)
 static int pair_tries() {
   int tries = IGMC_PAIR_TRIES;

@@ -1,5 +1,6 @@
 // kth_key.h -- THE k-th smallest 32-bit key of a set spread over the workgroup, by byte histograms in LDS, as steps the callers
-// compose: extract.hip (sample_fringe: the per-hop cap), candidates.hip (the sampled fill) and shortlist.hip (the vote order).
+// compose: extract.hip (sample_fringe: the per-hop cap), candidates.hip (the sampled fill), shortlist.hip (the vote order) and
+// holdout.hip (the kept subset of a row).
 //   walk(f)   the caller's lambda: f(key) for every key of the set, each key in one thread.  Nothing it reads is written by
 //             these steps, so it needs no barriers of its own beyond those of the tile rebuilds it may contain.
 //   hist      256 ints of LDS, one bin per thread;  sm: the 16 ints igmc_block_scan_excl shares with the mailbox below.

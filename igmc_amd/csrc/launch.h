@@ -147,6 +147,23 @@ void igmc_launch_candidates(const CandArgs& a, int fill, int sampled, void* stre
 int igmc_segsel_default_split(int ns);
 void igmc_launch_select_segments(const float* keys, const int64_t* seg_off, int ns, int num, int k, void* scratch,
                                  int32_t* idx_out, float* key_out, int32_t* count, void* stream);
+// holdout.hip: the Given-k split of a set of users -- per user a uniform `kept`-subset of the row stays, the rest is written as
+// held-out links in the row's own order (count, then fill at the offsets of the counts): k_holdout<fill>
+struct HoldArgs {
+  GraphDev g;
+  const int32_t* users;
+  int nq;
+  int64_t keep, hold;
+  uint64_t seed, draw;          // fill
+  int64_t* counts;              // count
+  const int64_t* off;           // fill
+  int32_t* link_u;
+  int32_t* link_v;
+  uint8_t* rating;
+  int64_t capacity;
+  int32_t* err;
+};
+void igmc_launch_holdout(const HoldArgs& a, int fill, void* stream);
 // pairs.hip: pair training -- one negative per positive link and epoch drawn into a link list of (positive, negative) slots, and
 // the pair loss of a batch of such slots with its gradient w.r.t. the outputs
 #define IGMC_PAIR_TRIES 256             // hashed candidates tried before the cyclic scan decides (IGMC_PAIR_TRIES: test hook)

@@ -535,6 +535,42 @@ def candidates_fill(graph, users, mask, exclude_seen, offsets, link_u, link_v, e
     graph.lib.call(name + '_fill', *(args + out + (link_u.numel(), _p(err.data_ptr()), _p(st))))
 
 
+HOLD_ALL = 2 ** 63 - 1      # ``hold``: no limit on the entries a split holds out
+
+
+def _holdout_head(graph, users, keep, hold):
+    hold = HOLD_ALL if hold is None else int(hold)
+    if int(keep) < 0 or not 0 <= hold <= HOLD_ALL:
+        raise ValueError('keep and hold must be at least 0')
+    return graph.handle, _p(users.data_ptr()), users.numel(), int(keep), hold
+
+
+def holdout_count(graph, users, keep, hold=None, stream=None):
+    """How many entries the Given-k split holds out of the row of every user of ``users`` (device int32):
+    ``min(hold, max(0, d - keep))`` (``igmc_holdout_count``; ``hold=None``: no limit; no reference counterpart).  Returns
+    device tensors ``(counts int64 [nq], err int32 [1])``; the error word is left to the caller to read."""
+    import torch
+    counts = torch.zeros(users.numel(), dtype=torch.int64, device=users.device)
+    err = torch.zeros(1, dtype=torch.int32, device=users.device)
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    graph.lib.call('igmc_holdout_count', *(_holdout_head(graph, users, keep, hold) + (_p(counts.data_ptr()), _p(err.data_ptr()),
+                                                                                      _p(st))))
+    return counts, err
+
+
+def holdout_fill(graph, users, keep, hold, offsets, link_u, link_v, rating, err, seed=0, draw=0, stream=None):
+    """The held-out links of ``users`` written at ``offsets`` (device int64 ``[nq + 1]``: the prefix sums of
+    :func:`holdout_count` under the same arguments) into the device buffers ``link_u`` / ``link_v`` (int32) and ``rating``
+    (uint8: relation + 1), every user's in its row's own order (``igmc_holdout_fill``; ``include/igmc_hip.h`` states the
+    definition): per user the ``d - held`` entries with the smallest hash key under ``(seed, draw, user id)`` stay.  ``err``
+    collects the error bits and is left to the caller."""
+    import torch
+    st = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    graph.lib.call('igmc_holdout_fill', *(_holdout_head(graph, users, keep, hold) + (
+        int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1), _p(offsets.data_ptr()), _p(link_u.data_ptr()),
+        _p(link_v.data_ptr()), _p(rating.data_ptr()), link_u.numel(), _p(err.data_ptr()), _p(st))))
+
+
 def pair_negatives(graph, pos_u, pos_v, n, mask, seed, epoch, link_u, link_v, link_y, err, stream=None):
     """One negative per positive ``(pos_u[k], pos_v[k])``, ``k < n``, drawn under ``(seed, epoch, k)`` into the ``2 n`` slots of
     ``link_u`` / ``link_v`` / ``link_y`` (``igmc_pair_negatives``; no reference counterpart).  Every argument but the scalars

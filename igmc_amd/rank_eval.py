@@ -47,12 +47,27 @@ carries the rank ``MISS_RANK``, beyond every K.  A link that is no candidate kee
 by ``igmc_shortlist_places`` in the same pass (the link's place in the full vote order: ``place >= M`` is a cut), not by a second
 enumeration.  M >= every user's candidate count reproduces the exhaustive result bit for bit.  :func:`shortlist_recall` judges the
 shortlist by itself, without the model: the share of relevant held-out candidate links with ``place < M``.
+
+COLD START (:func:`hold_out`, :func:`cold_start_eval`): how good is the list of a user with 1, 2, 5 or 10 ratings -- the Given-N
+protocol of the collaborative-filtering literature: per user a uniform k-subset of the row is kept and everything else the user
+rated is the test set.  The split runs on the device (``igmc_holdout_count`` / ``_fill``, ``igmc_amd/csrc/holdout.hip``; keyed by
+(the source's seed, ``draw``, the user id), so a user's split does not depend on the users evaluated with it, and the kept
+sets of the levels are NESTED: the five ratings of level 5 contain the two of level 2), the reduced graph is built on the
+device (``engine.Graph.updated``) and ranked over through a ``recommend.GraphView``.  ``keep=1, hold=1`` is the NCF-style
+leave-one-out split.  TWO CAVEATS about what the numbers mean:
+
+(a) The removed links were regression targets when the model was trained.  IGMC has no per-user parameters, so what can leak
+    passes through the shared weights only -- but it can.  The ``extra`` block (links of a test set the model never saw, ranked
+    in the same lists) is the leak-free figure; the ``heldout`` block is not.
+(b) Every evaluated user goes cold TOGETHER, and they are each other's two-hop neighbours: the reduced graph lacks the removed
+    ratings of all of them.  A small ``users`` subset measures "a cold user in a warm system"; all users measures "a cold
+    system".  The two differ, and neither is wrong.
 """
 import numpy as np
 import torch
 
 from . import engine
-from .recommend import _check_shortlist, _dev_int32, _item_mask, candidate_passes
+from .recommend import GraphView, _check_shortlist, _dev_int32, _item_mask, candidate_passes
 
 MISS_RANK = 2 ** 31 - 1      # the rank of a held-out candidate link that a shortlist cut: at or beyond every K (a K is below 2^31),
                              # above every real rank (a list holds fewer than 2^31 - 1 entries)
@@ -62,20 +77,23 @@ class HeldOut(object):
     """Held-out links grouped by user, on the device: ``users`` (int32 ``[nu]``, distinct, ascending), ``offsets`` (int64
     ``[nu + 1]``: user ``users[i]`` owns the links ``offsets[i]:offsets[i + 1]``), ``items`` (int32 ``[n]``, ascending
     within a user), ``relevant`` (uint8 ``[n]``, or None = every link is relevant) and ``order`` (int64 ``[n]``: the
-    index in the input of the link at each place)."""
+    index in the input of the link at each place); ``source`` (uint8 ``[n]``, in the held-out order; None unless given):
+    which of several link sets a link came from (``Split.heldout``: 0 = removed from the graph, 1 = of the extra set)."""
 
-    def __init__(self, users, offsets, items, relevant, order):
+    def __init__(self, users, offsets, items, relevant, order, source=None):
         self.users, self.offsets, self.items, self.relevant, self.order = users, offsets, items, relevant, order
+        self.source = source
 
     def __len__(self):
         return self.items.numel()
 
     @classmethod
-    def from_links(cls, dataset_or_graph, u=None, v=None, ratings=None, min_rating=None):
+    def from_links(cls, dataset_or_graph, u=None, v=None, ratings=None, min_rating=None, source=None):
         """Links ``(u[i], v[i])`` (ids, host or device) sorted by (user, item) on the device.  ``relevant = ratings >=
         min_rating``; with ``min_rating=None`` every link is relevant.  The first argument names the rating graph the ids
         belong to (a dataset or its ``engine.Graph``); a dataset given WITHOUT ``u`` / ``v`` is the held-out set itself:
-        its ``link_u``, ``link_v`` and -- as ratings -- ``link_y``."""
+        its ``link_u``, ``link_v`` and -- as ratings -- ``link_y``.  ``source``: one uint8 per link, carried along by
+        ``order``."""
         src = dataset_or_graph
         graph = getattr(src, 'graph', src)
         if u is None and v is None:
@@ -107,8 +125,13 @@ class HeldOut(object):
         users, counts = torch.unique_consecutive(u, return_counts=True)
         offsets = torch.zeros(users.numel() + 1, dtype=torch.int64, device=dev)
         torch.cumsum(counts, 0, out=offsets[1:])
+        if source is not None:
+            source = torch.as_tensor(source).to(device=dev, dtype=torch.uint8)
+            if source.dim() != 1 or source.numel() != u.numel():
+                raise ValueError('one source per link')
+            source = source[order].contiguous()
         return cls(users.to(torch.int32), offsets, v.to(torch.int32).contiguous(),
-                   None if relevant is None else relevant[order].to(torch.uint8).contiguous(), order)
+                   None if relevant is None else relevant[order].to(torch.uint8).contiguous(), order, source)
 
 
 def _select(heldout, users):
@@ -287,3 +310,149 @@ def shortlist_recall(dataset, heldout, ms=(50, 100, 200, 500), users=None, exclu
         stats.update(users=sel_users.numel(), queries=items.numel(), links=int(host[-4]), users_counted=int(host[-3]),
                      not_candidates=int(host[-2]), passes=passes)
     return {m: dict(micro=host[2 * i], macro=host[2 * i + 1]) for i, m in enumerate(ms)}
+
+
+# ------------------------------------------------------------------ cold start: the Given-k split and the evaluation over it
+def _class_values(source):
+    while not hasattr(source, 'class_values') and hasattr(source, 'source'):
+        source = source.source
+    return getattr(source, 'class_values', None)
+
+
+class Split(object):
+    """A Given-k split (:func:`hold_out`), everything on the device: ``users`` (int32 ``[nq]``, as requested) and ``offsets``
+    (int64 ``[nq + 1]``: user ``users[q]`` lost the links ``offsets[q]:offsets[q + 1]``); the removed links ``u`` / ``v``
+    (int32), ``rel`` (uint8: the relation) and ``ratings`` (float32: ``class_values[rel]``, what ``link_y`` holds) in the
+    order of the users' rows; ``graph``, the rating graph without them, and ``view``, the source's settings over it."""
+
+    def __init__(self, dataset, users, offsets, u, v, rel, ratings, graph):
+        self.users, self.offsets, self.u, self.v, self.rel, self.ratings, self.graph = users, offsets, u, v, rel, ratings, graph
+        self.view = GraphView(dataset, graph)
+
+    def __len__(self):
+        return self.u.numel()
+
+    def heldout(self, extra=None, min_rating=None):
+        """The :class:`HeldOut` of the split: the removed links (``source`` 0) and -- ``extra``: a dataset, normally the test
+        set -- the links of ``extra`` that belong to the split's users (``source`` 1).  ``relevant = rating >= min_rating``."""
+        u, v, r = self.u, self.v, self.ratings
+        source = torch.zeros(u.numel(), dtype=torch.uint8, device=u.device)
+        if extra is not None:
+            n = len(extra)
+            eu = _dev_int32(extra.link_u[:n], u.device, 'u')
+            mine = torch.isin(eu, self.users)
+            u = torch.cat([u, eu[mine]])
+            v = torch.cat([v, _dev_int32(extra.link_v[:n], v.device, 'v')[mine]])
+            r = torch.cat([r, extra.link_y[:n].to(device=r.device, dtype=torch.float32)[mine]])
+            source = torch.cat([source, torch.ones(u.numel() - source.numel(), dtype=torch.uint8, device=u.device)])
+        return HeldOut.from_links(self.view, u, v, ratings=r, min_rating=min_rating, source=source)
+
+
+def hold_out(dataset, users=None, keep=0, hold=None, draw=0):
+    """The Given-k split of ``users`` (ids, host or device, no duplicates: ``ValueError``; default every user) over the rating
+    graph of ``dataset`` (a dataset or a ``recommend.GraphView``): per user the ``keep`` entries of the row with the smallest
+    hash key under (the source's ``seed``, ``draw``, the user id) stay -- the whole row where it has no more --, at most
+    ``hold`` of the others (None: all of them) are removed (``include/igmc_hip.h``: ``igmc_holdout_fill`` states the
+    definition).  Returns a :class:`Split`.  Two launches and ``engine.Graph.updated``; ONE host read besides that call's own:
+    the total, with the duplicate flag and the count's error word beside it (the fill's word can report only what that read
+    has excluded: it is sized by the total, at the prefix sums of the same counts).  No host loop over users or ratings."""
+    g = dataset.graph
+    dev = dataset.link_y.device
+    if users is None:
+        users = torch.arange(g.n_users, dtype=torch.int32, device=dev)
+    else:
+        users = _dev_int32(users, dev, 'users')
+    nq = users.numel()
+    if nq < 1:
+        raise ValueError('no users')
+    counts, err = engine.holdout_count(g, users, keep, hold)
+    offsets = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=offsets[1:])
+    ordered = torch.sort(users.long()).values
+    dup = (ordered[1:] == ordered[:-1]).sum()
+    total, dup, e = torch.stack([offsets[-1], dup, err[0].to(torch.int64)]).tolist()
+    if e:
+        raise ValueError('hold_out: a user id outside the rating graph (%d users)' % g.n_users)
+    if dup:
+        raise ValueError('hold_out: a user is named more than once')
+    if total > 2 ** 31 - 1:
+        raise ValueError('hold_out: %d held-out links do not fit int32 positions' % total)
+    u = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)
+    v = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)
+    rating = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)
+    engine.holdout_fill(g, users, keep, hold, offsets, u, v, rating, err, dataset.seed, draw)
+    u, v, rel = u[:total], v[:total], rating[:total] - 1
+    cv = _class_values(dataset)
+    if cv is None:
+        ratings = rel.to(torch.float32)
+    else:
+        ratings = torch.as_tensor(np.asarray(cv, np.float32), device=dev)[rel.long()]
+    return Split(dataset, users, offsets, u, v, rel, ratings, g.updated(u, v, torch.zeros_like(rating[:total])))
+
+
+def _source_block(res, heldout, which, ks, lib):
+    """The metrics of ``res`` (a :func:`rank_eval` result over ``heldout``) with only the links of source ``which`` counted as
+    relevant: the same ranks, one more ``engine.rank_metrics`` + :func:`reduce_metrics`."""
+    per = res['per_user']
+    source = heldout.source if per['index'] is None else heldout.source[per['index']]
+    rel = source == which
+    if per['relevant'] is not None:
+        rel &= per['relevant'] != 0
+    cnt, dcg = engine.rank_metrics(per['rank'], per['offsets'], ks, rel.to(torch.uint8).contiguous(), lib=lib)
+    host = reduce_metrics(cnt, dcg, ks).tolist()
+    out = dict(zip(metric_names(ks), host[:-1]))
+    out['users_evaluated'] = int(host[-1])
+    out['per_user'] = dict(users=per['users'], offsets=per['offsets'], relevant=rel, cnt=cnt, dcg=dcg)
+    return out
+
+
+def cold_start_eval(model, dataset, given=(1, 2, 5, 10), users=None, extra=None, ks=(5, 10, 20), draw=0, min_rating=None,
+                    stats=None, **kw):
+    """Ranking metrics of users cut down to ``k`` ratings, for every level ``k`` of ``given`` (module docstring: COLD START and
+    its two caveats).  EVALUATED are the requested users (default: every user; no duplicates) whose row in ``dataset.graph``
+    has more than ``max(given)`` entries, so that every level holds out at least one link of the same set of users; the others
+    are counted in ``stats['users_skipped']`` (``stats`` also receives ``users`` and, per level, ``removed``).
+
+    Per level: ``hold_out(dataset, evaluated, keep=k, draw=draw)``, then :func:`rank_eval` of the split's held-out set over the
+    split's view -- ``result[k]['heldout']``, a :func:`rank_eval` result.  ``extra`` (a dataset, normally the test set): its
+    links of the evaluated users are ranked in the same lists (and count in the ``heldout`` block), and ``result[k]['extra']``
+    holds the metrics of the SAME ranks with the extra links alone counted as relevant -- no second scoring pass;
+    ``result['full']['extra']`` is plain :func:`rank_eval` of those links over the unreduced graph, the warm baseline the
+    ``extra`` blocks compare with.  ``kw`` goes to :func:`rank_eval`: ``negatives``, ``shortlist``, ``seed_min_rel``,
+    ``vote_min_rel``, ``batch_size``, ``users_per_pass``, ``item_mask``; the sampled negatives are drawn under ``negatives_draw``
+    (default: ``draw``).  Works for ``DGCNN_RS`` and with side features as far as :func:`rank_eval` over a ``GraphView`` does."""
+    bad = set(kw) - {'negatives', 'negatives_draw', 'shortlist', 'seed_min_rel', 'vote_min_rel', 'batch_size', 'users_per_pass',
+                     'item_mask'}
+    if bad:
+        raise TypeError('cold_start_eval: unexpected arguments %s' % sorted(bad))
+    kw = dict(kw)
+    neg_draw = kw.pop('negatives_draw', None)
+    given = [int(k) for k in given]
+    if not 1 <= len(given) <= 8 or min(given) < 0 or len(set(given)) != len(given):
+        raise ValueError('given: 1 to 8 distinct levels >= 0')
+    g, dev = dataset.graph, dataset.link_y.device
+    users = torch.arange(g.n_users, dtype=torch.int32, device=dev) if users is None else _dev_int32(users, dev, 'users')
+    if users.numel() < 1:
+        raise ValueError('no users')
+    length, err = engine.holdout_count(g, users, 0)          # (keep 0, no limit: the rows' lengths)
+    evaluated = users[length > max(given)].contiguous()
+    if int(err.item()):
+        raise ValueError('cold_start_eval: a user id outside the rating graph (%d users)' % g.n_users)
+    if evaluated.numel() < 1:
+        raise ValueError('cold_start_eval: no user has more than %d ratings' % max(given))
+    if stats is not None:
+        stats.update(users=evaluated.numel(), users_skipped=users.numel() - evaluated.numel(), removed={})
+    kw['draw'] = int(draw if neg_draw is None else neg_draw)
+    result = {}
+    for k in given:
+        split = hold_out(dataset, evaluated, keep=k, draw=draw)
+        heldout = split.heldout(extra, min_rating)
+        result[k] = dict(heldout=rank_eval(model, split.view, heldout, ks, **kw))
+        if extra is not None:
+            result[k]['extra'] = _source_block(result[k]['heldout'], heldout, 1, ks, g.lib)
+        if stats is not None:
+            stats['removed'][k] = len(split)
+    if extra is not None:
+        result['full'] = dict(extra=rank_eval(model, dataset, HeldOut.from_links(extra, min_rating=min_rating), ks,
+                                              users=evaluated, **kw))
+    return result

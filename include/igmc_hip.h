@@ -452,6 +452,32 @@ int igmc_candidates_sample_fill(const igmc_graph* g, const int32_t* d_users, int
                                 int64_t n_must, int64_t k, uint64_t seed, uint64_t draw, const int64_t* d_offsets,
                                 int32_t* d_link_u, int32_t* d_link_v, uint8_t* d_forced /* may be NULL */, int64_t capacity,
                                 int32_t* d_err, void* stream);
+/* ---- The Given-k split: hold ratings out on the device (no reference counterpart: the reference evaluates one fixed split by
+ * RMSE; the Given-N protocol of the collaborative-filtering literature is, by hand, a host loop over every user's row, a host
+ * RNG and a rebuilt matrix per level).
+ *
+ * For request q of user u = d_users[q] (IN THE ORDER GIVEN), whose row has d entries:
+ *   held = min(hold, max(0, d - keep)),  kept = d - held            keep >= 0, hold >= 0; hold = INT64_MAX: no limit
+ *   the kept entries are the `kept` entries of the row with the smallest sampling key of igmc_rng.h under that header's holdout
+ *   salt of (seed, draw, u) -- a uniform subset keyed by the user ID (the key is a bijection of the item id: no ties), so it
+ *   does not depend on the users asked for with it, on their order or on the launch;
+ *   the segment of q is the OTHER entries in the row's own order -- relation ascending, then item ascending, as the CSR stores
+ *   them --: d_link_u[p] = u, d_link_v[p] = item (int32), d_rating[p] = relation + 1 (uint8, the convention of
+ *   igmc_graph_create and igmc_graph_apply: the list with its ratings zeroed is the removal list of igmc_graph_apply).
+ * Consequences: at hold = INT64_MAX the kept sets are NESTED in keep, kept(k) c kept(k + 1) for the same (seed, draw, u); a user
+ * with d <= keep loses nothing; keep = 1, hold = 1 is leave-one-out and never strips a user bare.
+ * _count writes the segments' lengths to d_counts (int64[nq]; it reads the row pointers only and needs no seed); the caller
+ * forms d_offsets (int64[nq + 1], offsets[0] = 0, their inclusive prefix sums behind it) and _fill writes the segments.
+ * capacity = entries of d_link_u / d_link_v / d_rating (>= 0): nothing is written at or past it.  d_err[0] (int32, zeroed by
+ * the caller, read after the launches): bit 0 = a segment reaches past capacity (its links there are missing), bit 1 = a user id
+ * outside [0, n_users) (no row is read; its segment is empty), bit 2 = the offsets are not the prefix sums of the counts.
+ * Refused (non-zero, nothing launched): a null argument, nq < 0, keep < 0, hold < 0, capacity < 0; nq = 0 launches nothing.
+ * One launch each, asynchronous on `stream`, capturable; the output does not depend on the launch geometry. */
+int igmc_holdout_count(const igmc_graph* g, const int32_t* d_users, int nq, int64_t keep, int64_t hold, int64_t* d_counts,
+                       int32_t* d_err, void* stream);
+int igmc_holdout_fill(const igmc_graph* g, const int32_t* d_users, int nq, int64_t keep, int64_t hold, uint64_t seed,
+                      uint64_t draw, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v, uint8_t* d_rating,
+                      int64_t capacity, int32_t* d_err, void* stream);
 /* igmc_select_segments: the `num` first of every segment [d_seg_off[s], d_seg_off[s + 1]) of d_keys, s < ns (no reference
  * counterpart; by hand `np.lexsort` per user on the host), 1 <= num <= 64, d_seg_off[ns] < 2^31.
  * THE ORDER: key DESCENDING, then index ascending; every NaN behind every number (NaNs among themselves by index);

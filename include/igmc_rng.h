@@ -55,6 +55,17 @@ IGMC_HD uint64_t igmc_negative_salt(uint64_t seed, uint64_t draw, uint64_t user)
   return s;
 }
 
+/* salt for the Given-k split of one (dataset seed, draw, user ID) (igmc_holdout_fill): the kept entries of the user's row are
+ * those with the smallest igmc_sample_key(salt, item).  Keyed by the id, not by the user's place in a request, so a user's split
+ * does not depend on the users asked for with it, on their order or on the grid.  The key order of a row does not depend on how
+ * many entries are kept: with no limit on the held entries the kept sets are NESTED, kept(k) is a subset of kept(k + 1). */
+IGMC_HD uint64_t igmc_holdout_salt(uint64_t seed, uint64_t draw, uint64_t user) {
+  uint64_t s = igmc_splitmix64(seed ^ 0x484F4C44ull); /* "HOLD" */
+  s = igmc_splitmix64(s ^ draw);
+  s = igmc_splitmix64(s ^ user);
+  return s;
+}
+
 /* salt for the negative of one (dataset seed, epoch, positive link) of pair training: `pos` is the positive's position in the
  * pair list, not its place in a batch, so a link's negative does not depend on the shuffle or on the batch size */
 IGMC_HD uint64_t igmc_pair_salt(uint64_t seed, uint64_t epoch, uint64_t pos) {
