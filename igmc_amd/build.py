@@ -15,8 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (debug hooks of the same-box A/B tooling: an experimental copy of the sources built into libraries of its own --
 #  IGMC_CSRC_DIR / IGMC_HIP_LIB_OUT / IGMC_EMU_LIB_OUT; the product never sets them)
 CSRC = os.environ.get('IGMC_CSRC_DIR') or os.path.join(ROOT, 'igmc_amd', 'csrc')
-SOURCES = ['extract.hip', 'model.hip', 'graphstep2.hip', 'sortpool.hip', 'scores.hip', 'candidates.hip', 'shortlist.hip', 'ranking.hip', 'graph_update.hip', 'explain.hip',
-           'pairs.hip', 'holdout.hip', 'capi.hip']
+SOURCES = sorted(s for s in os.listdir(CSRC) if s.endswith('.hip'))
 HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith('.h')) + ['../../include/igmc_hip.h', '../../include/igmc_rng.h']
 HIP_LIB = os.environ.get('IGMC_HIP_LIB_OUT') or os.path.join(ROOT, 'igmc_amd', 'lib', 'libigmc_hip.so')
 EMU_LIB = os.environ.get('IGMC_EMU_LIB_OUT') or os.path.join(ROOT, 'tests', 'emu', 'libigmc_emu.so')

@@ -5,9 +5,32 @@
 #pragma once
 #include "launch.h"
 
+#define IGMC_CAND_TILE_ITEMS 16384      // items of one LDS bitmap tile of the enumeration (wider graphs: tile after tile)
 #define CAND_TILE_WORDS IGMC_BLOCK                 // 64-item words of a bitmap tile: one per thread of the scan
 #define CAND_TILE (CAND_TILE_WORDS * 64)
-static_assert(CAND_TILE == IGMC_CAND_TILE_ITEMS, "launch.h names the tile");
+static_assert(CAND_TILE == IGMC_CAND_TILE_ITEMS, "the tile is named in items");
+
+// the argument block of k_candidates (candidates.hip); the tile build reads its graph, item_ok, must list and error word, which
+// is all that shortlist.hip fills in
+struct CandArgs {
+  GraphDev g;
+  const int32_t* users;
+  int nq;
+  const uint8_t* item_ok;
+  int exclude_seen;
+  const int64_t* must_off;      // sampled; null: no request has must items
+  const int32_t* must_item;
+  int64_t n_must;
+  int k;
+  uint64_t seed, draw;          // sampled fill
+  int64_t* counts;              // count
+  const int64_t* off;           // fill
+  int32_t* link_u;
+  int32_t* link_v;
+  uint8_t* forced;              // sampled fill; may be null
+  int64_t capacity;
+  int32_t* err;
+};
 
 // LDS of one workgroup: the must bitmap, the forced ballots, the histogram and the parked keys exist in the SAMPLED
 // instantiations alone (members in this order: the sampled fill's register count depends on it)

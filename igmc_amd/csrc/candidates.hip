@@ -41,7 +41,7 @@
 // np.inf, -k))) is that order only for segments without a -inf key.  A key and its GLOBAL position travel as one 64-bit
 // word (select.h: sel_word_desc), the order is "word ascending", words are distinct: the lists do not depend on k.
 // Plain vector stores only (error words: a vector atomic OR, reached on errors only).
-#include "launch.h"
+#include "capi.h"
 #include "select.h"
 #include "cand_tile.h"      // CAND_TILE, CandLds, cand_build_tile: the one definition of C; CandTiles, cand_place_tile
 #include "kth_key.h"        // the k-th smallest key of the pool
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_segsel_merge(const float* __rest
 // ------------------------------------------------------------------ host
 static int cand_grid(int64_t jobs) { return (int)(jobs < 1 ? 1 : jobs > 65536 ? 65536 : jobs); }
 
-void igmc_launch_candidates(const CandArgs& a, int fill, int sampled, void* stream) {
+static void igmc_launch_candidates(const CandArgs& a, int fill, int sampled, void* stream) {
   static const char* const names[2][2] = {{"k_candidates_count", "k_candidates_fill"},
                                           {"k_sampled_candidates_count", "k_sampled_candidates_fill"}};
   igmc_dispatch(
@@ -294,7 +294,7 @@ int igmc_segsel_default_split(int ns) {
   return k < 1 ? 1 : k > IGMC_SEGSEL_MAX_SPLIT ? IGMC_SEGSEL_MAX_SPLIT : k;
 }
 
-void igmc_launch_select_segments(const float* keys, const int64_t* seg_off, int ns, int num, int k, void* scratch,
+static void igmc_launch_select_segments(const float* keys, const int64_t* seg_off, int ns, int num, int k, void* scratch,
                                  int32_t* idx_out, float* key_out, int32_t* count, void* stream) {
   unsigned long long* part = (unsigned long long*)scratch;
   IGMC_PLAUNCH("k_segsel_part", k_segsel_part, cand_grid((int64_t)ns * k), IGMC_BLOCK, 0, stream, keys, seg_off, ns, num, k,
@@ -302,4 +302,109 @@ void igmc_launch_select_segments(const float* keys, const int64_t* seg_off, int 
   if (k > 1)
     IGMC_PLAUNCH("k_segsel_merge", k_segsel_merge, cand_grid(ns), IGMC_BLOCK, 0, stream, keys, seg_off, ns, num, k,
                  (const unsigned long long*)part, idx_out, key_out, count);
+}
+
+// ------------------------------------------------------------------ C ABI
+// The four entry points -- every candidate, or (sample) cut down to k sampled negatives + the must items of every request --
+// fill ONE argument block: cand_args checks and files what all four take (the exhaustive pair: no must list, k = 0),
+// cand_fill_args what the two fills add.  Either returns the refusal, or null.
+static const char* cand_args(CandArgs* a, const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
+                             int exclude_seen, const int64_t* d_must_off, const int32_t* d_must_item, int64_t n_must, int64_t k,
+                             int32_t* d_err) {
+  if (!g || !d_users || !d_err) return "null argument";
+  if (nq < 1) return "nq must be at least 1";
+  if (k < 0 || k > (int64_t)INT32_MAX) return "k must be in [0, 2^31)";
+  if (n_must < 0 || n_must > (int64_t)INT32_MAX) return "n_must must be in [0, 2^31)";
+  if (d_must_off && n_must > 0 && !d_must_item) return "null argument";
+  *a = CandArgs{g->d, d_users, nq, d_item_ok, exclude_seen != 0, d_must_off, d_must_item, n_must, (int)k};
+  a->err = d_err;
+  return nullptr;
+}
+static const char* cand_fill_args(CandArgs* a, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v,
+                                  int64_t capacity) {
+  if (!d_offsets || !d_link_u || !d_link_v) return "null argument";
+  if (capacity < 1 || capacity > (int64_t)INT32_MAX) return "capacity must be in [1, 2^31)";
+  a->off = d_offsets;
+  a->link_u = d_link_u;
+  a->link_v = d_link_v;
+  a->capacity = capacity;
+  return nullptr;
+}
+extern "C" int igmc_candidates_count(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
+                                     int exclude_seen, int64_t* d_counts, int32_t* d_err, void* stream) {
+  CandArgs a;
+  const char* bad = cand_args(&a, g, d_users, nq, d_item_ok, exclude_seen, nullptr, nullptr, 0, 0, d_err);
+  if (bad) IGMC_FAIL(bad);
+  if (!d_counts) IGMC_FAIL("null argument");
+  a.counts = d_counts;
+  igmc_launch_candidates(a, 0, 0, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int igmc_candidates_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
+                                    int exclude_seen, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v,
+                                    int64_t capacity, int32_t* d_err, void* stream) {
+  CandArgs a;
+  const char* bad = cand_args(&a, g, d_users, nq, d_item_ok, exclude_seen, nullptr, nullptr, 0, 0, d_err);
+  if (!bad) bad = cand_fill_args(&a, d_offsets, d_link_u, d_link_v, capacity);
+  if (bad) IGMC_FAIL(bad);
+  igmc_launch_candidates(a, 1, 0, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int igmc_candidates_sample_count(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
+                                            int exclude_seen, const int64_t* d_must_off, const int32_t* d_must_item,
+                                            int64_t n_must, int64_t k, int64_t* d_counts, int32_t* d_err, void* stream) {
+  CandArgs a;
+  const char* bad = cand_args(&a, g, d_users, nq, d_item_ok, exclude_seen, d_must_off, d_must_item, n_must, k, d_err);
+  if (bad) IGMC_FAIL(bad);
+  if (!d_counts) IGMC_FAIL("null argument");
+  a.counts = d_counts;
+  igmc_launch_candidates(a, 0, 1, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int igmc_candidates_sample_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
+                                           int exclude_seen, const int64_t* d_must_off, const int32_t* d_must_item,
+                                           int64_t n_must, int64_t k, uint64_t seed, uint64_t draw, const int64_t* d_offsets,
+                                           int32_t* d_link_u, int32_t* d_link_v, uint8_t* d_forced, int64_t capacity,
+                                           int32_t* d_err, void* stream) {
+  CandArgs a;
+  const char* bad = cand_args(&a, g, d_users, nq, d_item_ok, exclude_seen, d_must_off, d_must_item, n_must, k, d_err);
+  if (!bad) bad = cand_fill_args(&a, d_offsets, d_link_u, d_link_v, capacity);
+  if (bad) IGMC_FAIL(bad);
+  a.seed = seed;
+  a.draw = draw;
+  a.forced = d_forced;
+  igmc_launch_candidates(a, 1, 1, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+static int segsel_split(int ns, int num, int geometry) {
+  if (ns < 1 || num < 1 || num > IGMC_SELECT_MAX_NUM || geometry < 0 || geometry > IGMC_SEGSEL_MAX_SPLIT) return -1;
+  return geometry > 0 ? geometry : igmc_segsel_default_split(ns);
+}
+static int64_t segsel_bytes(int ns, int num, int k) {      // (one workgroup per segment writes the result itself: a token word)
+  return k > 1 ? (int64_t)ns * k * num * (int64_t)sizeof(uint64_t) : (int64_t)sizeof(uint64_t);
+}
+extern "C" int64_t igmc_select_segments_scratch_bytes(int ns, int num, int geometry) {
+  const int k = segsel_split(ns, num, geometry);
+  if (k < 0) {
+    igmc_err() = std::string(__func__) + ": ns must be at least 1, num in [1, 64], geometry in [0, 64]";
+    return -1;
+  }
+  return segsel_bytes(ns, num, k);
+}
+extern "C" int igmc_select_segments(const float* d_keys, const int64_t* d_seg_off, int ns, int num, int32_t* d_idx_out,
+                                    float* d_key_out, int32_t* d_count, void* d_scratch, int64_t scratch_bytes, int geometry,
+                                    void* stream) {
+  if (!d_keys || !d_seg_off || !d_idx_out || !d_count || !d_scratch) IGMC_FAIL("null argument");
+  const int k = segsel_split(ns, num, geometry);
+  if (k < 0) IGMC_FAIL("ns must be at least 1, num in [1, 64], geometry in [0, 64]");
+  if (scratch_bytes < segsel_bytes(ns, num, k)) IGMC_FAIL("scratch too small (igmc_select_segments_scratch_bytes)");
+  if (((uintptr_t)d_scratch & 7) != 0) IGMC_FAIL("scratch must be 8-byte aligned");
+  igmc_launch_select_segments(d_keys, d_seg_off, ns, num, k, d_scratch, d_idx_out, d_key_out, d_count, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
 }

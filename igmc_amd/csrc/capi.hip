@@ -1,124 +1,19 @@
-// capi.hip -- C-ABI host layer of libigmc_hip.so (see include/igmc_hip.h for the contract).
-#include "launch.h"
+// capi.hip -- C-ABI host layer of libigmc_hip.so (see include/igmc_hip.h for the contract): the handle objects and the calls
+// that run the model.  A serving family's entry points stand in the family's own file, the gradient exchange in comm.hip.
+#include "capi.h"
 #include "sortpool.h"
 #include "g2_image.h"
 
-#include <algorithm>
-#include <climits>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <map>
-#include <mutex>
-#include <string>
-#include <vector>
 
-static thread_local std::string g_err;
+std::string& igmc_err() {
+  static thread_local std::string err;
+  return err;
+}
 int g_igmc_prof_on = 0;
-
-#define IGMC_FAIL(msg)                                                      \
-  do {                                                                      \
-    g_err = std::string(__func__) + ": " + (msg);                           \
-    return 1;                                                               \
-  } while (0)
-#define HIPCHECK(expr)                                                      \
-  do {                                                                      \
-    hipError_t e_ = (expr);                                                 \
-    if (e_ != hipSuccess) {                                                 \
-      g_err = std::string(__func__) + ": " #expr " -> " + hipGetErrorString(e_); \
-      return 1;                                                             \
-    }                                                                       \
-  } while (0)
-
-// Buffers of one handle are carved out of a few large slabs (256-byte aligned) instead of one hipMalloc each: the
-// ~40 arrays a kernel chain touches then share a handful of large pages (fewer address-translation misses on the
-// first touch of every hop) and creation does 1-2 driver calls instead of 40.
-struct Allocs {
-  std::vector<void*> ptrs;
-  size_t bytes = 0;
-  char* slab = nullptr;
-  size_t slab_left = 0;
-  static constexpr size_t SLAB = (size_t)32 << 20;
-  template <typename T> int get(T** out, size_t n) {
-    const size_t b = (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255;
-    bytes += b;
-    if (b > SLAB / 2 && !(packed && b <= slab_left)) {                 // large arrays get their own allocation
-      void* p = nullptr;
-      if (hipMalloc(&p, b) != hipSuccess) return 1;
-      ptrs.push_back(p);
-      *out = (T*)p;
-      return 0;
-    }
-    if (b > slab_left) {
-      void* p = nullptr;
-      if (hipMalloc(&p, SLAB) != hipSuccess) return 1;
-      ptrs.push_back(p);
-      slab = (char*)p;
-      slab_left = SLAB;
-    }
-    *out = (T*)slab;
-    slab += b;
-    slab_left -= b;
-    return 0;
-  }
-  // the arrays that follow were counted into `b` bytes (256-byte steps): one allocation of exactly that size takes them all
-  bool packed = false;
-  int reserve(size_t b) {
-    void* p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(b, 256)) != hipSuccess) return 1;
-    ptrs.push_back(p);
-    slab = (char*)p;
-    slab_left = std::max<size_t>(b, 256);
-    packed = true;
-    return 0;
-  }
-  void release() {
-    for (void* p : ptrs) hipFree(p);
-    ptrs.clear();
-    slab = nullptr;
-    slab_left = 0;
-  }
-};
-
-struct igmc_graph {
-  int device;
-  GraphDev d;
-  int64_t nnz;
-  int max_rel;
-  int max_deg_u, max_deg_v;     // longest user row / item column (bounds the hop-1 subgraph sides)
-  Allocs mem;
-};
-
-struct igmc_batch {
-  const igmc_graph* g;
-  BatchDev d;
-  int last_B;
-  const float* side;
-  int n_side;
-  const float* side_src;    // dataset-wide [n_links, n_side] matrix (igmc_batch_bind_side_source); rows gathered per batch
-  const float *side_u, *side_v;      // per-node tables [side_nu, side_fu] / [side_nv, side_fv] (igmc_batch_bind_side_tables);
-  int side_nu, side_fu, side_nv, side_fv;      // rows of the batch's target nodes gathered per batch; both NULL: none bound
-  float* side_buf;          // [graph_cap, n_side] owned by the arena
-  int side_buf_cols;
-  int lean;                 // igmc_batch_set_lean: extraction stops after the dense blocks (capped arenas)
-  const int64_t* ctrl;
-  Allocs mem;
-};
-
-struct igmc_model {
-  int device;
-  ModelDev d;
-  ModelAux ax;
-  int* done_ctr;
-  int last_B, last_training, last_flags;
-  // weight images (g2_w) of the subgraph / dense-layer kernels: whose parameters they hold, and the caller's one-shot
-  // assertion that those parameters have not changed since the previous call (igmc_model_weights_unchanged)
-  int img_valid, img_hint;
-  const float* img_params;
-  Allocs mem;
-};
-
 extern int g_igmc_compose_count;      // graphstep2.hip: launches of k_g2_compose so far
 
 // One call's view of the images: the compose launch is skipped when the caller asserted unchanged parameters AND the
@@ -151,7 +46,7 @@ extern "C" int igmc_model_weights_unchanged(igmc_model* m, int on) {
   return 0;
 }
 
-extern "C" const char* igmc_last_error(void) { return g_err.c_str(); }
+extern "C" const char* igmc_last_error(void) { return igmc_err().c_str(); }
 extern "C" int igmc_version(void) { return 100; }
 
 // ------------------------------------------------------------------ profiling
@@ -310,126 +205,6 @@ extern "C" void igmc_graph_destroy(igmc_graph* g) {
   delete g;
 }
 extern "C" int64_t igmc_graph_hbm_bytes(const igmc_graph* g) { return g ? (int64_t)g->mem.bytes : 0; }
-
-// ------------------------------------------------------------------ rating changes on the device (graph_update.hip)
-// Scratch of an update (sorted change lists, flags, the new pointer arrays, the block of sizes): one allocation per device,
-// kept between calls and grown on demand -- an update of a few ratings would otherwise spend most of its time in hipMalloc /
-// hipFree.  A call is synchronous and holds the lock from its first launch to its last read, so the next call finds the
-// scratch idle.  Lists whose scratch exceeds GU_SCRATCH_KEEP get an allocation of their own that the call releases.
-#define GU_SCRATCH_KEEP ((size_t)64 << 20)
-static std::mutex g_gu_lock;
-static std::map<int, std::pair<void*, size_t>> g_gu_scratch;      // device -> (allocation, bytes)
-
-static int gu_scratch_get(int device, size_t bytes, void** out, bool* owned) {
-  *owned = bytes > GU_SCRATCH_KEEP;
-  if (*owned) return hipMalloc(out, bytes) != hipSuccess;
-  std::pair<void*, size_t>& c = g_gu_scratch[device];
-  if (c.second < bytes) {
-    if (c.first) hipFree(c.first);
-    c = std::make_pair((void*)nullptr, (size_t)0);
-    const size_t want = std::max(bytes, (size_t)1 << 20);
-    if (hipMalloc(&c.first, want) != hipSuccess) {
-      c.first = nullptr;
-      return 1;
-    }
-    c.second = want;
-  }
-  *out = c.first;
-  return 0;
-}
-
-#define GU_TRY(expr, what)                                     \
-  do {                                                         \
-    if ((expr) != 0) {                                         \
-      if (owned) hipFree(scratch);                             \
-      ng->mem.release();                                       \
-      delete ng;                                               \
-      IGMC_FAIL(what);                                         \
-    }                                                          \
-  } while (0)
-extern "C" int igmc_graph_apply(const igmc_graph* g, int n_users_new, int n_items_new, const int32_t* d_user,
-                                const int32_t* d_item, const uint8_t* d_rating, int64_t n, void* stream, igmc_graph** out) {
-  if (!g || !out) IGMC_FAIL("null argument");
-  if (n < 0 || n > ((int64_t)1 << 30)) IGMC_FAIL("n must be in [0, 2^30]");
-  if (n > 0 && (!d_user || !d_item || !d_rating)) IGMC_FAIL("null argument");
-  if (n_users_new < g->d.n_users || n_items_new < g->d.n_items) IGMC_FAIL("a graph grows or keeps its size, it does not shrink");
-  if (n_users_new == INT_MAX || n_items_new == INT_MAX) IGMC_FAIL("sizes must be below 2^31 - 1");
-  HIPCHECK(hipSetDevice(g->device));
-  std::lock_guard<std::mutex> lock(g_gu_lock);
-  hipStream_t st = (hipStream_t)stream;
-  GuSide sd[2];
-  memset(sd, 0, sizeof(sd));
-  sd[0].optr = g->d.u_ptr; sd[0].oidx = g->d.u_idx; sd[0].orel = g->d.u_rel;
-  sd[0].rows_old = g->d.n_users; sd[0].rows_new = n_users_new;
-  sd[1].optr = g->d.v_ptr; sd[1].oidx = g->d.v_idx; sd[1].orel = g->d.v_rel;
-  sd[1].rows_old = g->d.n_items; sd[1].rows_new = n_items_new;
-  // the scratch, carved at 256-byte steps
-  const int64_t P = igmc_graph_update_padded(n);
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  size_t need = al(sizeof(GuStats));
-  for (int s = 0; s < 2; ++s)
-    need += al(((size_t)sd[s].rows_new + 1) * 4) + al((size_t)sd[s].rows_new) + al((size_t)P * 8) + al((size_t)P * 4) + 2 * al((size_t)n * 2);
-  igmc_graph* ng = new igmc_graph();
-  void* scratch = nullptr;
-  bool owned = false;
-  if (gu_scratch_get(g->device, need, &scratch, &owned)) {
-    delete ng;
-    IGMC_FAIL("hipMalloc failed");
-  }
-  char* at = (char*)scratch;
-  auto carve = [&](size_t b) { char* p = at; at += al(b); return (void*)p; };
-  GuStats* d_st = (GuStats*)carve(sizeof(GuStats));
-  for (int s = 0; s < 2; ++s) {
-    sd[s].nptr = (int32_t*)carve(((size_t)sd[s].rows_new + 1) * 4);
-    sd[s].touched = (uint8_t*)carve((size_t)sd[s].rows_new);
-    sd[s].keys = (unsigned long long*)carve((size_t)P * 8);
-    sd[s].idx = (uint32_t*)carve((size_t)P * 4);
-    sd[s].s_new = (int16_t*)carve((size_t)n * 2);
-    sd[s].s_old = (int16_t*)carve((size_t)n * 2);
-  }
-  GuStats h;
-  GU_TRY(hipMemsetAsync(d_st, 0, sizeof(GuStats), st), "hipMemsetAsync failed");
-  for (int s = 0; s < 2; ++s)
-    igmc_launch_graph_update_plan(sd[s], s, d_user, d_item, d_rating, n, n_users_new, n_items_new, d_st, stream);
-  GU_TRY(hipGetLastError(), "a launch failed");
-  GU_TRY(hipMemcpyAsync(&h, d_st, sizeof(GuStats), hipMemcpyDeviceToHost, st), "hipMemcpyAsync failed");
-  GU_TRY(hipStreamSynchronize(st), "hipStreamSynchronize failed");
-  if (h.err & 1) GU_TRY(1, "a user id outside [0, n_users_new)");
-  if (h.err & 2) GU_TRY(1, "an item id outside [0, n_items_new)");
-  if (h.err & 4) GU_TRY(1, "the resulting nnz must fit int32");
-  if (h.nnz[0] != h.nnz[1]) GU_TRY(1, "internal: the two orientations disagree about nnz");
-  // the new graph: ONE allocation of exactly its six arrays
-  const int64_t nz = h.nnz[0];
-  int32_t* fptr[2];
-  GU_TRY(ng->mem.reserve(al(((size_t)n_users_new + 1) * 4) + al(((size_t)n_items_new + 1) * 4) +
-                         2 * (al((size_t)std::max<int64_t>(nz, 1) * 4) + al((size_t)std::max<int64_t>(nz, 1)))),
-         "hipMalloc failed");
-  for (int s = 0; s < 2; ++s)
-    GU_TRY(ng->mem.get(&fptr[s], (size_t)sd[s].rows_new + 1) || ng->mem.get(&sd[s].nidx, (size_t)nz) ||
-               ng->mem.get(&sd[s].nrel, (size_t)nz),
-           "hipMalloc failed");
-  for (int s = 0; s < 2; ++s) {
-    igmc_launch_graph_update_write(sd[s], s, n, g->nnz, d_st, stream);
-    GU_TRY(hipMemcpyAsync(fptr[s], sd[s].nptr, ((size_t)sd[s].rows_new + 1) * 4, hipMemcpyDeviceToDevice, st),
-           "hipMemcpyAsync failed");
-  }
-  GU_TRY(hipGetLastError(), "a launch failed");
-  GU_TRY(hipMemcpyAsync(&h, d_st, sizeof(GuStats), hipMemcpyDeviceToHost, st), "hipMemcpyAsync failed");
-  GU_TRY(hipStreamSynchronize(st), "hipStreamSynchronize failed");
-  if (owned) hipFree(scratch);
-  ng->device = g->device;
-  ng->nnz = nz;
-  ng->max_rel = h.max_rel;
-  ng->max_deg_u = h.max_deg[0];
-  ng->max_deg_v = h.max_deg[1];
-  ng->d.n_users = n_users_new;
-  ng->d.n_items = n_items_new;
-  ng->d.u_ptr = fptr[0]; ng->d.u_idx = sd[0].nidx; ng->d.u_rel = sd[0].nrel;
-  ng->d.v_ptr = fptr[1]; ng->d.v_idx = sd[1].nidx; ng->d.v_rel = sd[1].nrel;
-  *out = ng;
-  return 0;
-}
-#undef GU_TRY
 
 extern "C" int igmc_graph_info(const igmc_graph* g, int64_t out6[6]) {
   if (!g || !out6) IGMC_FAIL("null argument");
@@ -1308,216 +1083,7 @@ extern "C" int igmc_sse_accumulate_tick(const float* d_out, const igmc_batch* b,
   return 0;
 }
 
-// ------------------------------------------------------------------ scores kept on the device + their extremes (scores.hip)
-extern "C" int igmc_scores_store(const float* d_out, const igmc_batch* b, double* d_acc, float* d_scores, float* d_labels,
-                                 int64_t n, int64_t first_or_minus1, int64_t* d_ctrl, int32_t* d_err, void* stream) {
-  if (!d_out || !b || !d_acc || !d_scores || !d_labels || !d_err) IGMC_FAIL("null argument");
-  if (n < 1 || n > (int64_t)INT32_MAX) IGMC_FAIL("n must be in [1, 2^31)");
-  if (first_or_minus1 < -1 || first_or_minus1 >= n) IGMC_FAIL("first must be -1 (the arena's stamp) or a position below n");
-  igmc_launch_scores_store(b->d, d_out, d_acc, d_ctrl, d_scores, d_labels, n, first_or_minus1, d_err, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-static int select_grid(int64_t n, int num, int grid) {
-  if (n < 1 || n > (int64_t)INT32_MAX || num < 1 || num > IGMC_SELECT_MAX_NUM || grid < 0 || grid > IGMC_SELECT_MAX_GRID) return -1;
-  return grid > 0 ? grid : igmc_select_default_grid(n);
-}
-extern "C" int64_t igmc_select_scratch_bytes(int64_t n, int num, int grid) {
-  const int g = select_grid(n, num, grid);
-  if (g < 0) {
-    g_err = std::string(__func__) + ": n must be in [1, 2^31), num in [1, 64], grid in [0, 1024]";
-    return -1;
-  }
-  return (int64_t)2 * g * num * (int64_t)sizeof(uint64_t);
-}
-extern "C" int igmc_select_extremes(const float* d_keys, int64_t n, int num, int32_t* d_idx_low, int32_t* d_idx_high,
-                                    float* d_key_low, float* d_key_high, int32_t* d_count, void* d_scratch,
-                                    int64_t scratch_bytes, int grid, void* stream) {
-  if (!d_keys || !d_idx_low || !d_idx_high || !d_scratch) IGMC_FAIL("null argument");
-  const int g = select_grid(n, num, grid);
-  if (g < 0) IGMC_FAIL("n must be in [1, 2^31), num in [1, 64], grid in [0, 1024]");
-  if (scratch_bytes < (int64_t)2 * g * num * (int64_t)sizeof(uint64_t)) IGMC_FAIL("scratch too small (igmc_select_scratch_bytes)");
-  if (((uintptr_t)d_scratch & 7) != 0) IGMC_FAIL("scratch must be 8-byte aligned");
-  igmc_launch_select(d_keys, n, num, g, d_scratch, d_idx_low, d_idx_high, d_key_low, d_key_high, d_count, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// ------------------------------------------------------------------ candidate links + the best of every segment (candidates.hip)
-// The four entry points -- every candidate, or (sample) cut down to k sampled negatives + the must items of every request --
-// fill ONE argument block: cand_args checks and files what all four take (the exhaustive pair: no must list, k = 0),
-// cand_fill_args what the two fills add.  Either returns the refusal, or null.
-static const char* cand_args(CandArgs* a, const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
-                             int exclude_seen, const int64_t* d_must_off, const int32_t* d_must_item, int64_t n_must, int64_t k,
-                             int32_t* d_err) {
-  if (!g || !d_users || !d_err) return "null argument";
-  if (nq < 1) return "nq must be at least 1";
-  if (k < 0 || k > (int64_t)INT32_MAX) return "k must be in [0, 2^31)";
-  if (n_must < 0 || n_must > (int64_t)INT32_MAX) return "n_must must be in [0, 2^31)";
-  if (d_must_off && n_must > 0 && !d_must_item) return "null argument";
-  *a = CandArgs{g->d, d_users, nq, d_item_ok, exclude_seen != 0, d_must_off, d_must_item, n_must, (int)k};
-  a->err = d_err;
-  return nullptr;
-}
-static const char* cand_fill_args(CandArgs* a, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v,
-                                  int64_t capacity) {
-  if (!d_offsets || !d_link_u || !d_link_v) return "null argument";
-  if (capacity < 1 || capacity > (int64_t)INT32_MAX) return "capacity must be in [1, 2^31)";
-  a->off = d_offsets;
-  a->link_u = d_link_u;
-  a->link_v = d_link_v;
-  a->capacity = capacity;
-  return nullptr;
-}
-extern "C" int igmc_candidates_count(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
-                                     int exclude_seen, int64_t* d_counts, int32_t* d_err, void* stream) {
-  CandArgs a;
-  const char* bad = cand_args(&a, g, d_users, nq, d_item_ok, exclude_seen, nullptr, nullptr, 0, 0, d_err);
-  if (bad) IGMC_FAIL(bad);
-  if (!d_counts) IGMC_FAIL("null argument");
-  a.counts = d_counts;
-  igmc_launch_candidates(a, 0, 0, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-extern "C" int igmc_candidates_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
-                                    int exclude_seen, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v,
-                                    int64_t capacity, int32_t* d_err, void* stream) {
-  CandArgs a;
-  const char* bad = cand_args(&a, g, d_users, nq, d_item_ok, exclude_seen, nullptr, nullptr, 0, 0, d_err);
-  if (!bad) bad = cand_fill_args(&a, d_offsets, d_link_u, d_link_v, capacity);
-  if (bad) IGMC_FAIL(bad);
-  igmc_launch_candidates(a, 1, 0, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-extern "C" int igmc_candidates_sample_count(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
-                                            int exclude_seen, const int64_t* d_must_off, const int32_t* d_must_item,
-                                            int64_t n_must, int64_t k, int64_t* d_counts, int32_t* d_err, void* stream) {
-  CandArgs a;
-  const char* bad = cand_args(&a, g, d_users, nq, d_item_ok, exclude_seen, d_must_off, d_must_item, n_must, k, d_err);
-  if (bad) IGMC_FAIL(bad);
-  if (!d_counts) IGMC_FAIL("null argument");
-  a.counts = d_counts;
-  igmc_launch_candidates(a, 0, 1, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-extern "C" int igmc_candidates_sample_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
-                                           int exclude_seen, const int64_t* d_must_off, const int32_t* d_must_item,
-                                           int64_t n_must, int64_t k, uint64_t seed, uint64_t draw, const int64_t* d_offsets,
-                                           int32_t* d_link_u, int32_t* d_link_v, uint8_t* d_forced, int64_t capacity,
-                                           int32_t* d_err, void* stream) {
-  CandArgs a;
-  const char* bad = cand_args(&a, g, d_users, nq, d_item_ok, exclude_seen, d_must_off, d_must_item, n_must, k, d_err);
-  if (!bad) bad = cand_fill_args(&a, d_offsets, d_link_u, d_link_v, capacity);
-  if (bad) IGMC_FAIL(bad);
-  a.seed = seed;
-  a.draw = draw;
-  a.forced = d_forced;
-  igmc_launch_candidates(a, 1, 1, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// ------------------------------------------------------------------ the Given-k split (holdout.hip)
-// what both entry points take; returns the refusal, or null
-static const char* hold_args(HoldArgs* a, const igmc_graph* g, const int32_t* d_users, int nq, int64_t keep, int64_t hold,
-                             int32_t* d_err) {
-  if (!g || !d_users || !d_err) return "null argument";
-  if (nq < 0) return "nq must be at least 0";
-  if (keep < 0) return "keep must be at least 0";
-  if (hold < 0) return "hold must be at least 0";
-  *a = HoldArgs{g->d, d_users, nq, keep, hold};
-  a->err = d_err;
-  return nullptr;
-}
-extern "C" int igmc_holdout_count(const igmc_graph* g, const int32_t* d_users, int nq, int64_t keep, int64_t hold,
-                                  int64_t* d_counts, int32_t* d_err, void* stream) {
-  HoldArgs a;
-  const char* bad = hold_args(&a, g, d_users, nq, keep, hold, d_err);
-  if (bad) IGMC_FAIL(bad);
-  if (!d_counts) IGMC_FAIL("null argument");
-  a.counts = d_counts;
-  igmc_launch_holdout(a, 0, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-extern "C" int igmc_holdout_fill(const igmc_graph* g, const int32_t* d_users, int nq, int64_t keep, int64_t hold, uint64_t seed,
-                                 uint64_t draw, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v,
-                                 uint8_t* d_rating, int64_t capacity, int32_t* d_err, void* stream) {
-  HoldArgs a;
-  const char* bad = hold_args(&a, g, d_users, nq, keep, hold, d_err);
-  if (bad) IGMC_FAIL(bad);
-  if (!d_offsets || !d_link_u || !d_link_v || !d_rating) IGMC_FAIL("null argument");
-  if (capacity < 0) IGMC_FAIL("capacity must be at least 0");
-  a.seed = seed;
-  a.draw = draw;
-  a.off = d_offsets;
-  a.link_u = d_link_u;
-  a.link_v = d_link_v;
-  a.rating = d_rating;
-  a.capacity = capacity;
-  igmc_launch_holdout(a, 1, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
 // ------------------------------------------------------------------ pair training (pairs.hip)
-static int pair_tries() {
-  int tries = IGMC_PAIR_TRIES;
-  if (const char* e = getenv("IGMC_PAIR_TRIES")) tries = atoi(e);      // (test hook: the cyclic scan after few tries, or none)
-  return tries < 0 ? 0 : tries > (1 << 20) ? (1 << 20) : tries;
-}
-
-extern "C" int igmc_pair_negatives(const igmc_graph* g, const int32_t* d_pos_u, const int32_t* d_pos_v, int64_t n,
-                                   const uint8_t* d_item_ok, uint64_t seed, uint64_t epoch, int32_t* d_link_u,
-                                   int32_t* d_link_v, float* d_link_y, int32_t* d_err, void* stream) {
-  if (!g || !d_pos_u || !d_pos_v || !d_link_u || !d_link_v || !d_link_y || !d_err) IGMC_FAIL("null argument");
-  if (n < 1 || n >= ((int64_t)1 << 30)) IGMC_FAIL("n must be in [1, 2^30): the 2 n link positions are int32");
-  const PairArgs a = {g->d, d_pos_u, d_pos_v, n, d_item_ok, seed, epoch, pair_tries(), d_link_u, d_link_v, d_link_y, d_err};
-  igmc_launch_pair_negatives(a, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-extern "C" int igmc_pair_negatives_shortlist(const igmc_graph* g, const int32_t* d_pos_u, const int32_t* d_pos_v, int64_t n,
-                                             const uint8_t* d_item_ok, uint64_t seed, uint64_t epoch, const int64_t* d_sl_off,
-                                             const int32_t* d_sl_item, int64_t sl_total, double hard_share, int32_t* d_link_u,
-                                             int32_t* d_link_v, float* d_link_y, int32_t* d_err, void* stream) {
-  if (!g || !d_pos_u || !d_pos_v || !d_link_u || !d_link_v || !d_link_y || !d_err) IGMC_FAIL("null argument");
-  if (n < 1 || n >= ((int64_t)1 << 30)) IGMC_FAIL("n must be in [1, 2^30): the 2 n link positions are int32");
-  if (!(hard_share >= 0.0 && hard_share <= 1.0)) IGMC_FAIL("hard_share must be in [0, 1]");
-  if (hard_share > 0.0 && (!d_sl_off || !d_sl_item)) IGMC_FAIL("a share above 0 needs the table: d_sl_off and d_sl_item");
-  if (sl_total < 0 || sl_total >= ((int64_t)1 << 31)) IGMC_FAIL("sl_total must be in [0, 2^31)");
-  PairArgs a = {g->d, d_pos_u, d_pos_v, n, d_item_ok, seed, epoch, pair_tries(), d_link_u, d_link_v, d_link_y, d_err};
-  a.sl_off = d_sl_off;
-  a.sl_item = d_sl_item;
-  a.sl_total = sl_total;
-  a.hard_thr = igmc_pair_hard_threshold(hard_share);
-  if (a.hard_thr == 0) igmc_launch_pair_negatives(a, stream);      // (no pair can decide hard: the table is not looked at)
-  else igmc_launch_pair_negatives_shortlist(a, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-extern "C" int igmc_pair_kind_stats(const float* d_out, const float* d_y, int B, double* d_stats6, void* stream) {
-  if (!d_out || !d_y || !d_stats6) IGMC_FAIL("null argument");
-  if (B < 2 || (B & 1)) IGMC_FAIL("a pair batch holds an even number of links, at least two");
-  igmc_launch_pair_kind_stats(d_out, d_y, B, d_stats6, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-extern "C" int igmc_pair_loss(const float* d_out, const float* d_y, int B, float mse_weight, float* d_gout, double* d_stats,
-                              void* stream) {
-  if (!d_out || !d_y || !d_gout || !d_stats) IGMC_FAIL("null argument");
-  if (B < 2 || (B & 1)) IGMC_FAIL("a pair batch holds an even number of links, at least two");
-  igmc_launch_pair_loss(d_out, d_y, B, mse_weight, d_gout, d_stats, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
 extern "C" int igmc_pair_loss_grad(igmc_model* m, const float* d_params, const igmc_batch* b, int use_edge_flags,
                                    const uint8_t* d_lin_mask, uint64_t seed, uint64_t step, float multiply_by, float ARR,
                                    float mse_weight, float* d_out, float* d_gout, float* d_grad, double* d_stats,
@@ -1538,197 +1104,6 @@ extern "C" int igmc_pair_loss_grad(igmc_model* m, const float* d_params, const i
   end_call(m, b, 1, use_edge_flags);
   return 0;
 }
-static int segsel_split(int ns, int num, int geometry) {
-  if (ns < 1 || num < 1 || num > IGMC_SELECT_MAX_NUM || geometry < 0 || geometry > IGMC_SEGSEL_MAX_SPLIT) return -1;
-  return geometry > 0 ? geometry : igmc_segsel_default_split(ns);
-}
-static int64_t segsel_bytes(int ns, int num, int k) {      // (one workgroup per segment writes the result itself: a token word)
-  return k > 1 ? (int64_t)ns * k * num * (int64_t)sizeof(uint64_t) : (int64_t)sizeof(uint64_t);
-}
-extern "C" int64_t igmc_select_segments_scratch_bytes(int ns, int num, int geometry) {
-  const int k = segsel_split(ns, num, geometry);
-  if (k < 0) {
-    g_err = std::string(__func__) + ": ns must be at least 1, num in [1, 64], geometry in [0, 64]";
-    return -1;
-  }
-  return segsel_bytes(ns, num, k);
-}
-extern "C" int igmc_select_segments(const float* d_keys, const int64_t* d_seg_off, int ns, int num, int32_t* d_idx_out,
-                                    float* d_key_out, int32_t* d_count, void* d_scratch, int64_t scratch_bytes, int geometry,
-                                    void* stream) {
-  if (!d_keys || !d_seg_off || !d_idx_out || !d_count || !d_scratch) IGMC_FAIL("null argument");
-  const int k = segsel_split(ns, num, geometry);
-  if (k < 0) IGMC_FAIL("ns must be at least 1, num in [1, 64], geometry in [0, 64]");
-  if (scratch_bytes < segsel_bytes(ns, num, k)) IGMC_FAIL("scratch too small (igmc_select_segments_scratch_bytes)");
-  if (((uintptr_t)d_scratch & 7) != 0) IGMC_FAIL("scratch must be 8-byte aligned");
-  igmc_launch_select_segments(d_keys, d_seg_off, ns, num, k, d_scratch, d_idx_out, d_key_out, d_count, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// ------------------------------------------------------------------ co-rating shortlists (shortlist.hip)
-// short_args checks and files what both entry points take, and plans the launch.  Returns the refusal, or null.
-static const char* short_args(ShortArgs* a, ShortPlan* p, const igmc_graph* g, const int32_t* d_users, int nq,
-                              const uint8_t* d_item_ok, int exclude_seen, int seed_min_rel, int vote_min_rel, int32_t* d_err,
-                              void* d_scratch, int64_t scratch_bytes, int grid) {
-  if (!g || !d_users || !d_err) return "null argument";
-  if (nq < 1) return "nq must be at least 1";
-  if (seed_min_rel < 0 || vote_min_rel < 0) return "seed_min_rel and vote_min_rel must be at least 0";
-  if (grid < 0 || grid > 65536) return "grid must be in [0, 65536]";
-  if ((int64_t)g->max_deg_u * (int64_t)g->max_deg_v > (int64_t)INT32_MAX)
-    return "max_deg_u * max_deg_v reaches 2^31: the vote counts may not fit";
-  igmc_shortlist_plan(g->d.n_users, g->d.n_items, nq, grid, p);
-  if (p->scratch_bytes > 0) {
-    if (!d_scratch) return "null argument";
-    if (scratch_bytes < p->scratch_bytes) return "scratch too small (igmc_shortlist_scratch_bytes)";
-    if (((uintptr_t)d_scratch & 3) != 0) return "scratch must be 4-byte aligned";
-  }
-  *a = ShortArgs{};
-  a->g = g->d;
-  a->users = d_users;
-  a->nq = nq;
-  a->item_ok = d_item_ok;
-  a->exclude_seen = exclude_seen != 0;
-  a->seed_min_rel = seed_min_rel;
-  a->vote_min_rel = vote_min_rel;
-  a->err = d_err;
-  a->scratch = (uint32_t*)d_scratch;
-  a->row_words = p->row_words;
-  if (igmc_shortlist_prepare()) return "the kernels' LDS size could not be set";
-  return nullptr;
-}
-extern "C" int64_t igmc_shortlist_scratch_bytes(const igmc_graph* g, int nq, int grid) {
-  if (!g || nq < 1 || grid < 0 || grid > 65536) {
-    g_err = std::string(__func__) + ": a graph, nq of at least 1, grid in [0, 65536]";
-    return -1;
-  }
-  ShortPlan p;
-  igmc_shortlist_plan(g->d.n_users, g->d.n_items, nq, grid, &p);
-  return p.scratch_bytes;
-}
-extern "C" int igmc_shortlist_plan_info(const igmc_graph* g, int nq, int grid, int64_t out6[6]) {
-  if (!g || !out6) IGMC_FAIL("null argument");
-  if (nq < 1 || grid < 0 || grid > 65536) IGMC_FAIL("nq must be at least 1, grid in [0, 65536]");
-  ShortPlan p;
-  igmc_shortlist_plan(g->d.n_users, g->d.n_items, nq, grid, &p);
-  out6[0] = p.grid;
-  out6[1] = p.lds_bytes;
-  out6[2] = p.w_lds;
-  out6[3] = p.v_lds;
-  out6[4] = p.scratch_bytes;
-  out6[5] = p.w_lds_max_users;
-  return 0;
-}
-extern "C" int igmc_shortlist_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
-                                   int exclude_seen, int seed_min_rel, int vote_min_rel, int64_t m, const int64_t* d_offsets,
-                                   int32_t* d_link_u, int32_t* d_link_v, uint32_t* d_votes, int64_t capacity, int32_t* d_err,
-                                   void* d_scratch, int64_t scratch_bytes, int grid, void* stream) {
-  ShortArgs a;
-  ShortPlan p;
-  if (!d_offsets || !d_link_u || !d_link_v) IGMC_FAIL("null argument");
-  if (m < 1 || m > (int64_t)INT32_MAX) IGMC_FAIL("m must be in [1, 2^31)");
-  if (capacity < 1 || capacity > (int64_t)INT32_MAX) IGMC_FAIL("capacity must be in [1, 2^31)");
-  const char* bad = short_args(&a, &p, g, d_users, nq, d_item_ok, exclude_seen, seed_min_rel, vote_min_rel, d_err, d_scratch,
-                               scratch_bytes, grid);
-  if (bad) IGMC_FAIL(bad);
-  a.m = m;
-  a.off = d_offsets;
-  a.link_u = d_link_u;
-  a.link_v = d_link_v;
-  a.votes_out = d_votes;
-  a.capacity = capacity;
-  igmc_launch_shortlist(a, p, 0, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-extern "C" int igmc_shortlist_places(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
-                                     int exclude_seen, int seed_min_rel, int vote_min_rel, const int64_t* d_q_off,
-                                     const int32_t* d_q_id, int64_t n_query, int32_t* d_q_place, uint32_t* d_q_votes,
-                                     int32_t* d_err, void* d_scratch, int64_t scratch_bytes, int grid, void* stream) {
-  ShortArgs a;
-  ShortPlan p;
-  if (!d_q_off) IGMC_FAIL("null argument");
-  if (n_query < 0 || n_query > (int64_t)INT32_MAX) IGMC_FAIL("n_query must be in [0, 2^31)");
-  if (n_query > 0 && (!d_q_id || !d_q_place)) IGMC_FAIL("null argument");
-  const char* bad = short_args(&a, &p, g, d_users, nq, d_item_ok, exclude_seen, seed_min_rel, vote_min_rel, d_err, d_scratch,
-                               scratch_bytes, grid);
-  if (bad) IGMC_FAIL(bad);
-  a.q_off = d_q_off;
-  a.q_id = d_q_id;
-  a.n_query = n_query;
-  a.q_place = d_q_place;
-  a.q_votes = d_q_votes;
-  igmc_launch_shortlist(a, p, 1, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// ------------------------------------------------------------------ places of given ids in their segments + metric sums (ranking.hip)
-extern "C" int igmc_rank_segments(const float* d_keys, const int32_t* d_ids, int64_t n, const int64_t* d_seg_off, int ns,
-                                  const int64_t* d_q_off, const int32_t* d_q_id, int64_t nq, int32_t* d_q_pos,
-                                  int32_t* d_q_rank, int32_t* d_err, int geometry, void* stream) {
-  if (!d_keys || !d_ids || !d_seg_off || !d_q_off || !d_err) IGMC_FAIL("null argument");
-  if (nq > 0 && (!d_q_id || !d_q_pos || !d_q_rank)) IGMC_FAIL("null argument");
-  if (n < 1 || n > (int64_t)INT32_MAX) IGMC_FAIL("n must be in [1, 2^31)");
-  if (nq < 0 || nq > (int64_t)INT32_MAX) IGMC_FAIL("nq must be in [0, 2^31)");
-  if (ns < 1 || geometry < 0 || geometry > IGMC_SEGSEL_MAX_SPLIT) IGMC_FAIL("ns must be at least 1, geometry in [0, 64]");
-  igmc_launch_rank_segments(d_keys, d_ids, n, d_seg_off, ns, d_q_off, d_q_id, nq,
-                            geometry > 0 ? geometry : igmc_segsel_default_split(ns), d_q_pos, d_q_rank, d_err, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-extern "C" int igmc_rank_metrics(const int32_t* d_q_rank, const int64_t* d_q_off, const uint8_t* d_q_rel, int64_t nq, int ns,
-                                 const int32_t* d_ks, int nk, int32_t* d_cnt, double* d_dcg, int32_t* d_err, int grid,
-                                 void* stream) {
-  if (!d_q_off || !d_ks || !d_cnt || !d_dcg || !d_err) IGMC_FAIL("null argument");
-  if (nq > 0 && !d_q_rank) IGMC_FAIL("null argument");
-  if (nq < 0 || nq > (int64_t)INT32_MAX) IGMC_FAIL("nq must be in [0, 2^31)");
-  if (ns < 1 || nk < 1 || nk > IGMC_RANK_MAX_KS || grid < 0 || grid > 65536)
-    IGMC_FAIL("ns must be at least 1, nk in [1, 8], grid in [0, 65536]");
-  igmc_launch_rank_metrics(d_q_rank, d_q_off, d_q_rel, d_ks, nk, ns, nq, grid, d_cnt, d_dcg, d_err, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// ------------------------------------------------------------------ leave-one-out variants + attributions (explain.hip)
-extern "C" int igmc_loo_count(const igmc_batch* base, int B, int64_t* d_nvar, int64_t* d_nu_ids, int64_t* d_nv_ids,
-                              void* stream) {
-  if (!base || !d_nvar || !d_nu_ids || !d_nv_ids) IGMC_FAIL("null argument");
-  if (B < 1 || B > base->last_B) IGMC_FAIL("B must be in [1, the number of links extracted into the arena]");
-  igmc_launch_loo_count(base->d, B, d_nvar, d_nu_ids, d_nv_ids, stream);      // (sizes only: a lean arena is not made to emit)
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-extern "C" int igmc_loo_fill(const igmc_graph* g, const igmc_batch* base, int B, int64_t link0, const int64_t* d_var_off,
-                             const int64_t* d_uent_off, const int64_t* d_vent_off, int64_t cap_var, int64_t cap_uent,
-                             int64_t cap_vent, int64_t* d_uoff, int32_t* d_unodes, uint8_t* d_udist, int64_t* d_voff,
-                             int32_t* d_vnodes, uint8_t* d_vdist, int32_t* d_var_link, uint8_t* d_var_side,
-                             int32_t* d_var_node, uint8_t* d_var_rating, int32_t* d_err, void* stream) {
-  if (!g || !base || base->g != g) IGMC_FAIL("the arena does not belong to this graph");
-  if (B < 1 || B > base->last_B) IGMC_FAIL("B must be in [1, the number of links extracted into the arena]");
-  if (!d_var_off || !d_uent_off || !d_vent_off || !d_uoff || !d_unodes || !d_udist || !d_voff || !d_vnodes || !d_vdist ||
-      !d_var_link || !d_var_side || !d_var_node || !d_var_rating || !d_err)
-    IGMC_FAIL("null argument");
-  if (cap_var < 1 || cap_uent < 1 || cap_vent < 1) IGMC_FAIL("capacities must be at least 1");
-  if (link0 < 0 || link0 + B > (int64_t)INT32_MAX) IGMC_FAIL("link indices must stay below 2^31");
-  LooCache c;
-  c.var_off = d_var_off; c.uent_off = d_uent_off; c.vent_off = d_vent_off;
-  c.cap_var = cap_var; c.cap_uent = cap_uent; c.cap_vent = cap_vent;
-  c.uoff = d_uoff; c.unodes = d_unodes; c.udist = d_udist; c.voff = d_voff; c.vnodes = d_vnodes; c.vdist = d_vdist;
-  c.var_link = d_var_link; c.var_side = d_var_side; c.var_node = d_var_node; c.var_rating = d_var_rating;
-  igmc_launch_loo_fill(g->d, base->d, B, link0, c, igmc_loo_default_chunks(), d_err, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-extern "C" int igmc_loo_deltas(const float* d_scores, const int64_t* d_var_off, int64_t n_links, float* d_base, float* d_delta,
-                               float* d_key, const int64_t* d_seg_off, void* stream) {
-  if (!d_scores || !d_var_off || !d_base || !d_delta || !d_key || !d_seg_off) IGMC_FAIL("null argument");
-  if (n_links < 1 || n_links > (int64_t)INT32_MAX) IGMC_FAIL("n_links must be in [1, 2^31)");
-  igmc_launch_loo_deltas(d_scores, d_var_off, n_links, d_base, d_delta, d_key, d_seg_off, stream);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
 // ------------------------------------------------------------------ device-side step control
 extern "C" int igmc_ctrl_tick(int64_t* d_ctrl, void* stream) {
   if (!d_ctrl) IGMC_FAIL("null ctrl");
@@ -1843,429 +1218,6 @@ extern "C" int igmc_train_step(igmc_model* m, float* d_params, const igmc_batch*
   return 0;
 }
 
-// ------------------------------------------------------------------ gradient exchange (RCCL behind the C ABI)
-#define IGMC_MAX_PEERS 16
-struct igmc_comm {
-  void* nccl;        // ncclComm_t (NULL: host-callback / peer communicator, or the emulation build's single rank)
-  int rank, world, device;
-  igmc_allreduce_fn host_fn;      // igmc_comm_create_host: the caller's own sum over the ranks
-  void* host_user;
-  // peer communicator (igmc_comm_peer_alloc / _connect): every rank publishes into its OWN buffer, mapped by the others
-  unsigned long long* pub[IGMC_MAX_PEERS];      // [2 slots][cap] {f32, tag} words of rank r (pub[rank] = the local buffer)
-  int64_t cap;                                  // floats a slot holds
-  int* d_state;                                 // device: [0] launch sequence number, [1] workgroups done, [2] poll timed out
-  int peer;                                     // 1 = peer communicator
-  int connected;
-  int fine;                                     // the local buffer is fine-grained device memory
-};
-#ifndef IGMC_HIPEMU
-#include <dlfcn.h>
-// RCCL's entry points, resolved at the first use.  The few types needed are restated here (rccl.h: ncclUniqueId = 128
-// opaque bytes; ncclFloat = 7, ncclSum = 0; results: 0 = success) so that the build needs no RCCL headers.
-struct NcclId { char internal[128]; };
-struct RcclApi {
-  int (*GetUniqueId)(NcclId*);
-  int (*CommInitRank)(void**, int, NcclId, int);
-  int (*CommDestroy)(void*);
-  int (*CommCount)(const void*, int*);
-  int (*CommUserRank)(const void*, int*);
-  int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t);
-  int (*GroupStart)();
-  int (*GroupEnd)();
-  const char* (*GetErrorString)(int);
-  bool ok = false;
-};
-static RcclApi g_rccl;
-static int rccl_load(std::string* why) {
-  if (g_rccl.ok) return 0;
-  void* h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);      // the copy the process already holds, if any (same soname)
-  if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-  if (!h) { *why = std::string("cannot load librccl.so.1: ") + dlerror(); return 1; }
-  struct { const char* name; void** slot; } syms[] = {
-      {"ncclGetUniqueId", (void**)&g_rccl.GetUniqueId}, {"ncclCommInitRank", (void**)&g_rccl.CommInitRank},
-      {"ncclCommDestroy", (void**)&g_rccl.CommDestroy}, {"ncclCommCount", (void**)&g_rccl.CommCount},
-      {"ncclCommUserRank", (void**)&g_rccl.CommUserRank}, {"ncclAllReduce", (void**)&g_rccl.AllReduce},
-      {"ncclGroupStart", (void**)&g_rccl.GroupStart}, {"ncclGroupEnd", (void**)&g_rccl.GroupEnd},
-      {"ncclGetErrorString", (void**)&g_rccl.GetErrorString}};
-  for (auto& sy : syms) {
-    *sy.slot = dlsym(h, sy.name);
-    if (!*sy.slot) { *why = std::string("librccl.so.1 lacks ") + sy.name; return 1; }
-  }
-  g_rccl.ok = true;
-  return 0;
-}
-#define RCCLCHECK(expr)                                                                              \
-  do {                                                                                               \
-    int r_ = (expr);                                                                                 \
-    if (r_ != 0) {                                                                                   \
-      g_err = std::string(__func__) + ": " #expr " -> " + g_rccl.GetErrorString(r_);                 \
-      return 1;                                                                                      \
-    }                                                                                                \
-  } while (0)
-#endif
-
-__global__ __launch_bounds__(IGMC_BLOCK) void k_scale_flat(float* p, int64_t n, float s) {
-  for (int64_t i = (int64_t)blockIdx.x * IGMC_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * IGMC_BLOCK) p[i] *= s;
-}
-
-extern "C" int igmc_comm_unique_id(uint8_t* h_id128) {
-  if (!h_id128) IGMC_FAIL("null id buffer");
-#ifndef IGMC_HIPEMU
-  std::string why;
-  if (rccl_load(&why)) IGMC_FAIL(why);
-  NcclId id;
-  RCCLCHECK(g_rccl.GetUniqueId(&id));
-  memcpy(h_id128, id.internal, 128);
-#else
-  memset(h_id128, 0, 128);
-#endif
-  return 0;
-}
-
-extern "C" int igmc_comm_create(const uint8_t* h_id128, int rank, int world, int device, igmc_comm** out) {
-  if (!h_id128 || !out || world < 1 || rank < 0 || rank >= world) IGMC_FAIL("bad arguments");
-  igmc_comm* c = new igmc_comm();
-  c->nccl = nullptr;
-  c->rank = rank;
-  c->world = world;
-  c->device = device;
-  c->host_fn = nullptr;
-  c->host_user = nullptr;
-  c->peer = 0;
-  c->d_state = nullptr;
-#ifndef IGMC_HIPEMU
-  std::string why;
-  if (rccl_load(&why)) { delete c; IGMC_FAIL(why); }
-  HIPCHECK(hipSetDevice(device));
-  NcclId id;
-  memcpy(id.internal, h_id128, 128);
-  const int r = g_rccl.CommInitRank(&c->nccl, world, id, rank);
-  if (r != 0) {
-    delete c;
-    IGMC_FAIL(std::string("ncclCommInitRank -> ") + g_rccl.GetErrorString(r));
-  }
-#else
-  if (world != 1) { delete c; IGMC_FAIL("the emulation build has no RCCL: one rank only"); }
-#endif
-  *out = c;
-  return 0;
-}
-
-extern "C" int igmc_comm_create_host(igmc_allreduce_fn fn, void* user, int rank, int world, igmc_comm** out) {
-  if (!fn || !out || world < 1 || rank < 0 || rank >= world) IGMC_FAIL("bad arguments");
-  igmc_comm* c = new igmc_comm();
-  c->nccl = nullptr;
-  c->rank = rank;
-  c->world = world;
-  c->device = -1;
-  c->host_fn = fn;
-  c->host_user = user;
-  c->peer = 0;
-  c->d_state = nullptr;
-  *out = c;
-  return 0;
-}
-
-// ---- peer communicator: a one-shot all-reduce over peer-mapped buffers ------------------------------------------------
-// The exchange of a step is ~60 k floats between a handful of GPUs of ONE node: a ring collective pays 2 (G - 1) hops of
-// launch + link latency for it, while every rank can simply READ the other ranks' values -- xGMI is point to point.  Every
-// rank owns a publish buffer (hipMalloc + hipIpcGetMemHandle, mapped by the others with hipIpcOpenMemHandle); a launch
-// of k_peer_allreduce writes the rank's span into its own buffer as 8-byte {value, tag} words (flag in data: single-copy
-// atomic, system scope), then reads the same words of EVERY rank in rank order -- polling a word until its tag is this
-// launch's -- and leaves the sum in place.  Same order on every rank: bit-identical replicas.  No barrier, no second
-// launch: about one xGMI round trip.  Two slots alternate: a rank can only be ONE launch ahead of the slowest one (it
-// cannot finish launch s + 1 before every rank published s + 1, i.e. finished reading s), so slot s & 1 is never
-// overwritten while someone still reads it.  The launch sequence number lives in device memory and is advanced by the
-// launch's last workgroup -- a hipGraph replay carries no host-side counter.  Bounded polls raise d_state[2].
-struct PeerArgs {
-  unsigned long long* pub[IGMC_MAX_PEERS];
-  int world, rank;
-  int64_t cap;
-  unsigned long long timeout_ticks;      // bound of a poll on the device's constant-rate clock (100 MHz)
-  int* state;
-  float* a;
-  int64_t na;
-  float* b;
-  int64_t nb;
-};
-__global__ __launch_bounds__(IGMC_BLOCK) void k_peer_allreduce(PeerArgs p) {
-#ifndef IGMC_HIPEMU
-  const uint32_t seq = (uint32_t)__hip_atomic_load(p.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  const uint32_t seq = (uint32_t)p.state[0];
-#endif
-  const unsigned long long tag = (unsigned long long)seq << 32;
-  const int64_t n = p.na + p.nb, base = (int64_t)(seq & 1u) * p.cap;
-  const int64_t T = (int64_t)gridDim.x * IGMC_BLOCK, t0 = (int64_t)blockIdx.x * IGMC_BLOCK + threadIdx.x;
-  unsigned long long* mine = p.pub[p.rank] + base;
-  for (int64_t i = t0; i < n; i += T) {
-    const float v = (i < p.na) ? p.a[i] : p.b[i - p.na];
-    const unsigned long long w = tag | (unsigned long long)__float_as_uint(v);
-#ifndef IGMC_HIPEMU
-    __hip_atomic_store(mine + i, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#else
-    mine[i] = w;
-#endif
-  }
-  // A rank may be late by far more than a kernel's length -- first-step capture, a checkpoint write on rank 0, a
-  // time-sliced device: the polls are bounded by WALL-CLOCK time (p.timeout_ticks, a minute by default), not by an
-  // iteration count.  A word that never arrives raises the sticky p.state[2]: the element is left as it was, every thread
-  // that sees the flag stops summing, but elements summed BEFORE a thread gave up stay summed -- after a time-out the spans
-  // are a mixture of sums and local values and MUST NOT be used (no foreign or torn value is ever written: a word counts
-  // only with this launch's tag in it).  The gradient / Adam kernel of igmc_train_step_dp behind this launch reads the
-  // flag and leaves parameters, moments and counters alone (AdamTail::skip); the host raises at its next check
-  // (igmc_comm_check).  Callers of the bare igmc_allreduce_grads must call igmc_comm_check before they use the spans.
-  //
-  // CROSS-DEVICE visibility (the words of rank r live in r's HBM, fine-grained, mapped over xGMI): value and flag are ONE
-  // 8-byte word written by ONE system-scope atomic store (global_store_dwordx2 sc0 sc1: written through, never parked in the
-  // writer's L2) and read by ONE system-scope atomic load (sc0 sc1: never served from the reader's L2) -- single-copy
-  // atomic, so a reader sees either the old word (old tag: polls again) or the whole new one.  Nothing else is published
-  // through these buffers, so no release / acquire ordering BETWEEN words is needed: every word validates itself.
-#ifndef IGMC_HIPEMU
-  const unsigned long long t_start = wall_clock64();
-#endif
-  for (int64_t i = t0; i < n; i += T) {
-    float s = 0.f;
-    bool ok = true;
-    for (int r = 0; r < p.world && ok; ++r) {
-      const unsigned long long* src = p.pub[r] + base + i;
-      unsigned long long w = 0;
-      for (long it = 0;; ++it) {
-#ifndef IGMC_HIPEMU
-        w = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#else
-        w = *src;
-#endif
-        if ((w >> 32) == (unsigned long long)seq) break;
-#ifndef IGMC_HIPEMU
-        if ((it & 63) == 63 && wall_clock64() - t_start > p.timeout_ticks) ok = false;
-        if (__hip_atomic_load(p.state + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) ok = false;      // (another thread gave up)
-#else
-        if (it > (1L << 22)) ok = false;
-#endif
-        if (!ok) {
-          p.state[2] = 1;
-          break;
-        }
-#ifndef IGMC_HIPEMU
-        __builtin_amdgcn_s_sleep(4);
-#endif
-      }
-      s += __uint_as_float((uint32_t)w);
-    }
-    if (ok) {
-      if (i < p.na) p.a[i] = s;
-      else p.b[i - p.na] = s;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#ifndef IGMC_HIPEMU
-    if (__hip_atomic_fetch_add(p.state + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) {
-      __hip_atomic_store(p.state + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(p.state, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-#else
-    if (p.state[1]++ == (int)gridDim.x - 1) {
-      p.state[1] = 0;
-      p.state[0] += 1;
-    }
-#endif
-  }
-}
-
-extern "C" int igmc_comm_peer_alloc(int rank, int world, int device, int64_t max_floats, igmc_comm** out, uint8_t* h_handle64) {
-  if (!out || !h_handle64 || world < 1 || world > IGMC_MAX_PEERS || rank < 0 || rank >= world || max_floats < 1) IGMC_FAIL("bad arguments");
-  igmc_comm* c = new igmc_comm();
-  c->nccl = nullptr;
-  c->rank = rank;
-  c->world = world;
-  c->device = device;
-  c->host_fn = nullptr;
-  c->host_user = nullptr;
-  c->peer = 1;
-  c->connected = 0;
-  c->cap = (max_floats + 63) & ~(int64_t)63;
-  for (int r = 0; r < IGMC_MAX_PEERS; ++r) c->pub[r] = nullptr;
-  memset(h_handle64, 0, 64);
-#ifndef IGMC_HIPEMU
-  HIPCHECK(hipSetDevice(device));
-  // FINE-GRAINED device memory where the runtime can share it (coherent between devices while kernels run: what RCCL's
-  // own buffers are); else ordinary device memory -- the words are written and read with system-scope accesses either way
-  const size_t bytes = (size_t)2 * c->cap * sizeof(unsigned long long);
-  hipIpcMemHandle_t h;
-  static_assert(sizeof(hipIpcMemHandle_t) <= 64, "IPC handle larger than the 64 bytes of the C ABI");
-  bool fine = hipExtMallocWithFlags((void**)&c->pub[rank], bytes, hipDeviceMallocFinegrained) == hipSuccess;
-  if (fine && hipIpcGetMemHandle(&h, c->pub[rank]) != hipSuccess) {
-    (void)hipGetLastError();
-    (void)hipFree(c->pub[rank]);
-    c->pub[rank] = nullptr;
-    fine = false;
-  }
-  if (!fine) {
-    (void)hipGetLastError();
-    HIPCHECK(hipMalloc((void**)&c->pub[rank], bytes));
-    HIPCHECK(hipIpcGetMemHandle(&h, c->pub[rank]));
-  }
-  c->fine = fine ? 1 : 0;
-  HIPCHECK(hipMemset(c->pub[rank], 0, bytes));      // tag 0 is never a launch's
-  HIPCHECK(hipMalloc((void**)&c->d_state, 4 * sizeof(int)));
-  const int init[4] = {1, 0, 0, 0};
-  HIPCHECK(hipMemcpy(c->d_state, init, sizeof(init), hipMemcpyHostToDevice));
-  memcpy(h_handle64, &h, sizeof(h));
-  HIPCHECK(hipDeviceSynchronize());
-#else
-  if (world != 1) { delete c; IGMC_FAIL("the emulation build has one rank only"); }
-  c->pub[rank] = (unsigned long long*)calloc((size_t)2 * c->cap, sizeof(unsigned long long));
-  c->d_state = (int*)calloc(4, sizeof(int));
-  c->d_state[0] = 1;
-#endif
-  *out = c;
-  return 0;
-}
-
-extern "C" int igmc_comm_peer_connect(igmc_comm* c, const uint8_t* h_handles) {
-  if (!c || !c->peer || !h_handles) IGMC_FAIL("not a peer communicator");
-#ifndef IGMC_HIPEMU
-  HIPCHECK(hipSetDevice(c->device));
-  for (int r = 0; r < c->world; ++r) {
-    if (r == c->rank) continue;
-    hipIpcMemHandle_t h;
-    memcpy(&h, h_handles + (size_t)r * 64, sizeof(h));
-    void* ptr = nullptr;
-    HIPCHECK(hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess));
-    c->pub[r] = (unsigned long long*)ptr;
-  }
-#endif
-  c->connected = 1;
-  return 0;
-}
-
-// 0 = the communicator's device-side state is sane; synchronises `stream`.  A peer communicator whose bounded poll ran out
-// (a rank that never published: not co-resident, crashed, or peer memory that is not visible) reports it here.
-extern "C" int igmc_comm_check(igmc_comm* c, void* stream) {
-  if (!c) IGMC_FAIL("null communicator");
-#ifndef IGMC_HIPEMU
-  HIPCHECK(hipStreamSynchronize((hipStream_t)stream));
-  if (c->peer && c->d_state) {
-    int st[4];
-    HIPCHECK(hipMemcpy(st, c->d_state, sizeof(st), hipMemcpyDeviceToHost));
-    if (st[2]) {
-      // reported once: the flag is cleared so that a caller that recovers (or tears the job down in order) is not told again
-      const int zero = 0;
-      (void)hipMemcpy(c->d_state + 2, &zero, sizeof(int), hipMemcpyHostToDevice);
-      IGMC_FAIL("peer all-reduce: another rank's words did not arrive within the time limit (IGMC_PEER_TIMEOUT_S); the spans of that "
-                "launch were left unsummed and the optimiser step behind it was skipped");
-    }
-  }
-#endif
-  return 0;
-}
-
-// 0 none (one rank), 1 RCCL, 2 host callback, 3 peer-mapped buffers (4: in fine-grained device memory)
-extern "C" int igmc_comm_kind(const igmc_comm* c) {
-  if (!c) return 0;
-  if (c->peer) return c->fine ? 4 : 3;
-  if (c->host_fn) return 2;
-  return c->nccl ? 1 : 0;
-}
-
-static int peer_sum2(igmc_comm* c, float* a, int64_t na, float* b, int64_t nb, void* stream) {
-  if (!c->connected) { g_err = "peer communicator is not connected (igmc_comm_peer_connect)"; return 1; }
-  if (c->world == 1 && !getenv("IGMC_PEER_ALWAYS")) return 0;      // one rank: the spans ARE the sums (IGMC_PEER_ALWAYS: test hook)
-  if (!a) na = 0;
-  if (!b) nb = 0;
-  double tmo = 60.0;
-  if (const char* e = getenv("IGMC_PEER_TIMEOUT_S")) tmo = atof(e) > 0 ? atof(e) : tmo;
-  // spans beyond a slot go in pieces (each piece is a launch of its own: the sequence number advances per launch)
-  while (na + nb > 0) {
-    PeerArgs p;
-    memset(&p, 0, sizeof(p));
-    for (int r = 0; r < c->world; ++r) p.pub[r] = c->pub[r];
-    p.world = c->world; p.rank = c->rank; p.cap = c->cap; p.state = c->d_state;
-    p.timeout_ticks = (unsigned long long)(tmo * 1e8);
-    const int64_t ta = na < c->cap ? na : c->cap;
-    const int64_t tb = (nb < c->cap - ta) ? nb : c->cap - ta;
-    p.a = a; p.na = ta; p.b = b; p.nb = tb;
-    int grid = (int)((ta + tb + 4 * IGMC_BLOCK - 1) / (4 * IGMC_BLOCK));      // four words a thread; few workgroups: every
-    if (grid > 64) grid = 64;                                                  // rank's launch must be on its chip at once
-    if (grid < 1) grid = 1;
-    IGMC_PLAUNCH("k_peer_allreduce", k_peer_allreduce, grid, IGMC_BLOCK, 0, stream, p);
-    a += ta; na -= ta;
-    b += tb; nb -= tb;
-  }
-#ifndef IGMC_HIPEMU
-  if (hipGetLastError() != hipSuccess) { g_err = "k_peer_allreduce launch failed"; return 1; }
-#endif
-  return 0;
-}
-
-extern "C" void igmc_comm_destroy(igmc_comm* c) {
-  if (!c) return;
-#ifndef IGMC_HIPEMU
-  if (c->nccl && g_rccl.ok) g_rccl.CommDestroy(c->nccl);
-  if (c->peer) {
-    for (int r = 0; r < c->world; ++r)
-      if (c->pub[r]) {
-        if (r == c->rank) hipFree(c->pub[r]);
-        else hipIpcCloseMemHandle(c->pub[r]);
-      }
-    if (c->d_state) hipFree(c->d_state);
-  }
-#else
-  if (c->peer) {
-    free(c->pub[c->rank]);
-    free(c->d_state);
-  }
-#endif
-  delete c;
-}
-
-extern "C" int igmc_comm_info(const igmc_comm* c, int* rank, int* world) {
-  if (!c) IGMC_FAIL("null communicator");
-  int r = c->rank, w = c->world;
-#ifndef IGMC_HIPEMU
-  if (c->nccl) {
-    RCCLCHECK(g_rccl.CommUserRank(c->nccl, &r));
-    RCCLCHECK(g_rccl.CommCount(c->nccl, &w));
-  }
-#endif
-  if (rank) *rank = r;
-  if (world) *world = w;
-  return 0;
-}
-
-// sum of up to two spans over the ranks, in place: ONE grouped collective (RCCL), or the host callback once per span
-static int comm_sum2(void* user, float* a, int64_t na, float* b, int64_t nb, void* stream) {
-  igmc_comm* c = (igmc_comm*)user;
-  if (c->peer) return peer_sum2(c, a, na, b, nb, stream);
-  if (c->host_fn) {
-    if (a && na > 0 && c->host_fn(c->host_user, a, na, stream)) { g_err = "comm_sum2: the host all-reduce callback failed"; return 1; }
-    if (b && nb > 0 && c->host_fn(c->host_user, b, nb, stream)) { g_err = "comm_sum2: the host all-reduce callback failed"; return 1; }
-    return 0;
-  }
-#ifndef IGMC_HIPEMU
-  if (!c->nccl) return 0;
-  const bool two = a && na > 0 && b && nb > 0;
-  if (two) RCCLCHECK(g_rccl.GroupStart());
-  if (a && na > 0) RCCLCHECK(g_rccl.AllReduce(a, a, (size_t)na, /*ncclFloat*/ 7, /*ncclSum*/ 0, c->nccl, (hipStream_t)stream));
-  if (b && nb > 0) RCCLCHECK(g_rccl.AllReduce(b, b, (size_t)nb, 7, 0, c->nccl, (hipStream_t)stream));
-  if (two) RCCLCHECK(g_rccl.GroupEnd());
-#endif
-  return 0;
-}
-
-extern "C" int igmc_allreduce_grads(igmc_comm* c, float* d_flat_grad, int64_t n, float scale, void* stream) {
-  if (!c || !d_flat_grad || n <= 0) IGMC_FAIL("bad arguments");
-  if (comm_sum2(c, d_flat_grad, n, nullptr, 0, stream)) return 1;
-  if (scale != 1.0f) {
-    int grid = (int)((n + IGMC_BLOCK - 1) / IGMC_BLOCK);
-    IGMC_PLAUNCH("k_scale_flat", k_scale_flat, grid > 1024 ? 1024 : grid, IGMC_BLOCK, 0, stream, d_flat_grad, n, scale);
-    HIPCHECK(hipGetLastError());
-  }
-  return 0;
-}
-
 // One optimisation step of a data-parallel job (reference train_eval.py:157-177 per rank, gradients averaged over the
 // ranks): igmc_train_step with the exchange INSIDE the step.  Where the step keeps its gradient sources in reduced form
 // (StepPlan::exchange_inside: the subgraph kernel's tables, the per-layer path's basis-space sums) those are summed over
@@ -2280,7 +1232,7 @@ extern "C" int igmc_train_step_dp(igmc_model* m, igmc_comm* comm, float* d_param
   if (check_call(m, b, d_params && d_out && d_grad && d_exp_avg && d_exp_avg_sq && d_loss, &why)) IGMC_FAIL(why);
   if (!d_ctrl && adam_t < 1) IGMC_FAIL("adam_t must be >= 1");
   const AdamHyper ah = adam_scalars(d_ctrl, adam_t, lr, beta1, beta2, eps, weight_decay);
-  const int world = comm ? comm->world : 1;
+  const int world = igmc_comm_world(comm);
   const int B = b->last_B;
   const float gscale = 1.0f / ((float)B * (float)world);
   const StepPlan sp = begin_call(m, b, IGMC_CALL_STEP, stream);
@@ -2288,7 +1240,7 @@ extern "C" int igmc_train_step_dp(igmc_model* m, igmc_comm* comm, float* d_param
   int emitted = 0;
   const StepHead hd = {d_params, d_lin_mask, seed, step, multiply_by, gscale, d_out};
   if (sp.exchange_inside) {
-    StepExchange x = {comm_sum2, comm, (comm && comm->peer) ? comm->d_state + 2 : nullptr};
+    StepExchange x = igmc_comm_exchange(comm);
     // (the ARR term depends on the weights only: every rank adds it in full AFTER the exchange)
     const AdamTail at = adam_tail(m, d_params, d_exp_avg, d_exp_avg_sq, ah, d_ctrl, d_loss, d_total);
     const int rc = igmc_launch_loss_grad(m->d, b->d, sp, B, use_edge_flags, hd, ARR, 1.0f, d_grad, nullptr, &at, stream,
@@ -2297,7 +1249,7 @@ extern "C" int igmc_train_step_dp(igmc_model* m, igmc_comm* comm, float* d_param
     if (rc) return 1;
   } else {
     igmc_launch_loss_grad(m->d, b->d, sp, B, use_edge_flags, hd, ARR, 1.0f / (float)world, d_grad, nullptr, nullptr, stream);
-    if (comm && comm_sum2(comm, d_grad, m->d.n_params, nullptr, 0, stream)) return 1;
+    if (comm && igmc_comm_sum_flat(comm, d_grad, m->d.n_params, stream)) return 1;
     igmc_launch_finish(m->d, b->d, d_params, d_grad, d_exp_avg, d_exp_avg_sq, ah, d_ctrl, ARR, d_loss, d_total, use_edge_flags, stream);
     img.done_updated(0);
   }

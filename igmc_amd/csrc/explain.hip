@@ -31,7 +31,7 @@
 //               straight into igmc_select_segments.  A NaN score gives a NaN key, which that selection ranks last.
 //
 // Plain vector stores only, no float atomics (error word: a vector atomic OR, reached on errors only).
-#include "launch.h"
+#include "capi.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -199,19 +199,35 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_loo_deltas(const float* __restri
 }
 
 // ------------------------------------------------------------------ host
-void igmc_launch_loo_count(const BatchDev& b, int B, int64_t* nvar, int64_t* nu_ids, int64_t* nv_ids, void* stream) {
+struct LooCache {
+  const int64_t* var_off;   // [B + 1] each: the batch's slice of the prefix sums of the three counts
+  const int64_t* uent_off;
+  const int64_t* vent_off;
+  int64_t cap_var, cap_uent, cap_vent;
+  int64_t* uoff;            // [cap_var + 1]  the cache arrays igmc_launch_load_nodes reads
+  int32_t* unodes;          // [cap_uent]
+  uint8_t* udist;
+  int64_t* voff;
+  int32_t* vnodes;          // [cap_vent]
+  uint8_t* vdist;
+  int32_t* var_link;        // [cap_var] each
+  uint8_t* var_side;
+  int32_t* var_node;
+  uint8_t* var_rating;
+};
+static void igmc_launch_loo_count(const BatchDev& b, int B, int64_t* nvar, int64_t* nu_ids, int64_t* nv_ids, void* stream) {
   IGMC_PLAUNCH("k_loo_count", k_loo_count, (B + IGMC_BLOCK - 1) / IGMC_BLOCK, IGMC_BLOCK, 0, stream, (const int32_t*)b.n_users,
                (const int32_t*)b.n_items, B, nvar, nu_ids, nv_ids);
 }
 
 // workgroups per link of the fill where the caller names none: 16 x 4 waves take a 128 + 128 link's 255 variants in four rounds
-int igmc_loo_default_chunks() {
+static int igmc_loo_default_chunks() {
   const char* e = getenv("IGMC_LOO_CHUNKS");      // (test hook: the output does not depend on it)
   const int c = e ? atoi(e) : 16;
   return c < 1 ? 1 : c > 1024 ? 1024 : c;
 }
 
-void igmc_launch_loo_fill(const GraphDev& g, const BatchDev& b, int B, int64_t link0, const LooCache& c, int chunks, int32_t* err,
+static void igmc_launch_loo_fill(const GraphDev& g, const BatchDev& b, int B, int64_t link0, const LooCache& c, int chunks, int32_t* err,
                           void* stream) {
   LooFill a;
   a.g = g;
@@ -226,8 +242,47 @@ void igmc_launch_loo_fill(const GraphDev& g, const BatchDev& b, int B, int64_t l
   IGMC_PLAUNCH("k_loo_fill", k_loo_fill, dim3(B, chunks), IGMC_BLOCK, 0, stream, a);
 }
 
-void igmc_launch_loo_deltas(const float* scores, const int64_t* var_off, int64_t n_links, float* base, float* delta, float* key,
+static void igmc_launch_loo_deltas(const float* scores, const int64_t* var_off, int64_t n_links, float* base, float* delta, float* key,
                             const int64_t* seg_off, void* stream) {
   const int grid = (int)(n_links < 1 ? 1 : n_links > 65536 ? 65536 : n_links);
   IGMC_PLAUNCH("k_loo_deltas", k_loo_deltas, grid, IGMC_BLOCK, 0, stream, scores, var_off, n_links, base, delta, key, seg_off);
+}
+
+// ------------------------------------------------------------------ C ABI
+extern "C" int igmc_loo_count(const igmc_batch* base, int B, int64_t* d_nvar, int64_t* d_nu_ids, int64_t* d_nv_ids,
+                              void* stream) {
+  if (!base || !d_nvar || !d_nu_ids || !d_nv_ids) IGMC_FAIL("null argument");
+  if (B < 1 || B > base->last_B) IGMC_FAIL("B must be in [1, the number of links extracted into the arena]");
+  igmc_launch_loo_count(base->d, B, d_nvar, d_nu_ids, d_nv_ids, stream);      // (sizes only: a lean arena is not made to emit)
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int igmc_loo_fill(const igmc_graph* g, const igmc_batch* base, int B, int64_t link0, const int64_t* d_var_off,
+                             const int64_t* d_uent_off, const int64_t* d_vent_off, int64_t cap_var, int64_t cap_uent,
+                             int64_t cap_vent, int64_t* d_uoff, int32_t* d_unodes, uint8_t* d_udist, int64_t* d_voff,
+                             int32_t* d_vnodes, uint8_t* d_vdist, int32_t* d_var_link, uint8_t* d_var_side,
+                             int32_t* d_var_node, uint8_t* d_var_rating, int32_t* d_err, void* stream) {
+  if (!g || !base || base->g != g) IGMC_FAIL("the arena does not belong to this graph");
+  if (B < 1 || B > base->last_B) IGMC_FAIL("B must be in [1, the number of links extracted into the arena]");
+  if (!d_var_off || !d_uent_off || !d_vent_off || !d_uoff || !d_unodes || !d_udist || !d_voff || !d_vnodes || !d_vdist ||
+      !d_var_link || !d_var_side || !d_var_node || !d_var_rating || !d_err)
+    IGMC_FAIL("null argument");
+  if (cap_var < 1 || cap_uent < 1 || cap_vent < 1) IGMC_FAIL("capacities must be at least 1");
+  if (link0 < 0 || link0 + B > (int64_t)INT32_MAX) IGMC_FAIL("link indices must stay below 2^31");
+  LooCache c;
+  c.var_off = d_var_off; c.uent_off = d_uent_off; c.vent_off = d_vent_off;
+  c.cap_var = cap_var; c.cap_uent = cap_uent; c.cap_vent = cap_vent;
+  c.uoff = d_uoff; c.unodes = d_unodes; c.udist = d_udist; c.voff = d_voff; c.vnodes = d_vnodes; c.vdist = d_vdist;
+  c.var_link = d_var_link; c.var_side = d_var_side; c.var_node = d_var_node; c.var_rating = d_var_rating;
+  igmc_launch_loo_fill(g->d, base->d, B, link0, c, igmc_loo_default_chunks(), d_err, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int igmc_loo_deltas(const float* d_scores, const int64_t* d_var_off, int64_t n_links, float* d_base, float* d_delta,
+                               float* d_key, const int64_t* d_seg_off, void* stream) {
+  if (!d_scores || !d_var_off || !d_base || !d_delta || !d_key || !d_seg_off) IGMC_FAIL("null argument");
+  if (n_links < 1 || n_links > (int64_t)INT32_MAX) IGMC_FAIL("n_links must be in [1, 2^31)");
+  igmc_launch_loo_deltas(d_scores, d_var_off, n_links, d_base, d_delta, d_key, d_seg_off, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
 }

@@ -28,8 +28,34 @@
 //                  with more changes counts by a pass over its segment in memory, (old length + changes) x changes: slow
 //                  (quadratic in the changes of that one row), never refused.
 // Plain vector stores only (error word: a vector atomic OR, reached on errors only).
-#include "launch.h"
+#include "capi.h"
 #include <stdlib.h>
+#include <map>
+#include <mutex>
+
+// One orientation at a time (side 0: rows are users, side 1: rows are items).  plan: the sorted change list, the new row
+// lengths, their prefix sums, nnz and the longest row; write: the rows of the new graph, once the host has read nnz and
+// allocated them.
+struct GuStats {
+  int32_t err;              // bit 0: a user id out of range, bit 1: an item id out of range, bit 2: nnz does not fit int32
+  int32_t max_deg[2];
+  int32_t max_rel;
+  long long nnz[2];
+};
+struct GuSide {
+  const int32_t* optr;      // the old graph's arrays of this orientation
+  const int32_t* oidx;
+  const uint8_t* orel;
+  int rows_old, rows_new;
+  unsigned long long* keys; // [padded n] sorted (row << 32 | col) words
+  uint32_t* idx;            // [padded n] their list positions
+  int16_t* s_new;           // [n] -1: overridden, 0: the winner removes, else the winner's rating
+  int16_t* s_old;           // [n] a winner's relation in the old row, or -1
+  uint8_t* touched;         // [rows_new] the row has changes in the list
+  int32_t* nptr;            // the new graph's arrays
+  int32_t* nidx;
+  uint8_t* nrel;
+};
 
 #define GU_TILE 2048          // pairs of one LDS tile of the sort (24 KB)
 #define GU_SCAN_ITEMS 16      // rows per thread and round of the scan
@@ -402,14 +428,14 @@ static int gu_grid(int64_t jobs) {
   return (int)(jobs < 1 ? 1 : jobs > 65536 ? 65536 : jobs);
 }
 
-int64_t igmc_graph_update_padded(int64_t n) {
+static int64_t igmc_graph_update_padded(int64_t n) {
   if (n < 1) return 0;
   int64_t P = 2;
   while (P < n) P <<= 1;
   return P;
 }
 
-void igmc_launch_graph_update_plan(const GuSide& s, int side, const int32_t* user, const int32_t* item, const uint8_t* rating,
+static void igmc_launch_graph_update_plan(const GuSide& s, int side, const int32_t* user, const int32_t* item, const uint8_t* rating,
                                    int64_t n, int n_users, int n_items, GuStats* st, void* stream) {
   const int64_t P = igmc_graph_update_padded(n);
   if (n > 0) {
@@ -431,7 +457,7 @@ void igmc_launch_graph_update_plan(const GuSide& s, int side, const int32_t* use
   IGMC_PLAUNCH("k_gu_scan", k_gu_scan, 1, IGMC_BLOCK, 0, stream, s.nptr, (int64_t)s.rows_new, side, st);
 }
 
-void igmc_launch_graph_update_write(const GuSide& s, int side, int64_t n, int64_t nnz_old, GuStats* st, void* stream) {
+static void igmc_launch_graph_update_write(const GuSide& s, int side, int64_t n, int64_t nnz_old, GuStats* st, void* stream) {
   const int wpb = IGMC_BLOCK >> 6;
   if (nnz_old > 0) {
     const int64_t blocks = (nnz_old + IGMC_BLOCK - 1) / IGMC_BLOCK;
@@ -441,3 +467,123 @@ void igmc_launch_graph_update_write(const GuSide& s, int side, int64_t n, int64_
   IGMC_PLAUNCH("k_gu_write", k_gu_write, gu_grid(((int64_t)s.rows_new + wpb - 1) / wpb), IGMC_BLOCK, 0, stream, s,
                side == 0 ? 1 : 0, n, st);
 }
+
+// ------------------------------------------------------------------ C ABI
+// Scratch of an update (sorted change lists, flags, the new pointer arrays, the block of sizes): one allocation per device,
+// kept between calls and grown on demand -- an update of a few ratings would otherwise spend most of its time in hipMalloc /
+// hipFree.  A call is synchronous and holds the lock from its first launch to its last read, so the next call finds the
+// scratch idle.  Lists whose scratch exceeds GU_SCRATCH_KEEP get an allocation of their own that the call releases.
+#define GU_SCRATCH_KEEP ((size_t)64 << 20)
+static std::mutex g_gu_lock;
+static std::map<int, std::pair<void*, size_t>> g_gu_scratch;      // device -> (allocation, bytes)
+
+static int gu_scratch_get(int device, size_t bytes, void** out, bool* owned) {
+  *owned = bytes > GU_SCRATCH_KEEP;
+  if (*owned) return hipMalloc(out, bytes) != hipSuccess;
+  std::pair<void*, size_t>& c = g_gu_scratch[device];
+  if (c.second < bytes) {
+    if (c.first) hipFree(c.first);
+    c = std::make_pair((void*)nullptr, (size_t)0);
+    const size_t want = std::max(bytes, (size_t)1 << 20);
+    if (hipMalloc(&c.first, want) != hipSuccess) {
+      c.first = nullptr;
+      return 1;
+    }
+    c.second = want;
+  }
+  *out = c.first;
+  return 0;
+}
+
+#define GU_TRY(expr, what)                                     \
+  do {                                                         \
+    if ((expr) != 0) {                                         \
+      if (owned) hipFree(scratch);                             \
+      ng->mem.release();                                       \
+      delete ng;                                               \
+      IGMC_FAIL(what);                                         \
+    }                                                          \
+  } while (0)
+extern "C" int igmc_graph_apply(const igmc_graph* g, int n_users_new, int n_items_new, const int32_t* d_user,
+                                const int32_t* d_item, const uint8_t* d_rating, int64_t n, void* stream, igmc_graph** out) {
+  if (!g || !out) IGMC_FAIL("null argument");
+  if (n < 0 || n > ((int64_t)1 << 30)) IGMC_FAIL("n must be in [0, 2^30]");
+  if (n > 0 && (!d_user || !d_item || !d_rating)) IGMC_FAIL("null argument");
+  if (n_users_new < g->d.n_users || n_items_new < g->d.n_items) IGMC_FAIL("a graph grows or keeps its size, it does not shrink");
+  if (n_users_new == INT_MAX || n_items_new == INT_MAX) IGMC_FAIL("sizes must be below 2^31 - 1");
+  HIPCHECK(hipSetDevice(g->device));
+  std::lock_guard<std::mutex> lock(g_gu_lock);
+  hipStream_t st = (hipStream_t)stream;
+  GuSide sd[2];
+  memset(sd, 0, sizeof(sd));
+  sd[0].optr = g->d.u_ptr; sd[0].oidx = g->d.u_idx; sd[0].orel = g->d.u_rel;
+  sd[0].rows_old = g->d.n_users; sd[0].rows_new = n_users_new;
+  sd[1].optr = g->d.v_ptr; sd[1].oidx = g->d.v_idx; sd[1].orel = g->d.v_rel;
+  sd[1].rows_old = g->d.n_items; sd[1].rows_new = n_items_new;
+  // the scratch, carved at 256-byte steps
+  const int64_t P = igmc_graph_update_padded(n);
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  size_t need = al(sizeof(GuStats));
+  for (int s = 0; s < 2; ++s)
+    need += al(((size_t)sd[s].rows_new + 1) * 4) + al((size_t)sd[s].rows_new) + al((size_t)P * 8) + al((size_t)P * 4) + 2 * al((size_t)n * 2);
+  igmc_graph* ng = new igmc_graph();
+  void* scratch = nullptr;
+  bool owned = false;
+  if (gu_scratch_get(g->device, need, &scratch, &owned)) {
+    delete ng;
+    IGMC_FAIL("hipMalloc failed");
+  }
+  char* at = (char*)scratch;
+  auto carve = [&](size_t b) { char* p = at; at += al(b); return (void*)p; };
+  GuStats* d_st = (GuStats*)carve(sizeof(GuStats));
+  for (int s = 0; s < 2; ++s) {
+    sd[s].nptr = (int32_t*)carve(((size_t)sd[s].rows_new + 1) * 4);
+    sd[s].touched = (uint8_t*)carve((size_t)sd[s].rows_new);
+    sd[s].keys = (unsigned long long*)carve((size_t)P * 8);
+    sd[s].idx = (uint32_t*)carve((size_t)P * 4);
+    sd[s].s_new = (int16_t*)carve((size_t)n * 2);
+    sd[s].s_old = (int16_t*)carve((size_t)n * 2);
+  }
+  GuStats h;
+  GU_TRY(hipMemsetAsync(d_st, 0, sizeof(GuStats), st), "hipMemsetAsync failed");
+  for (int s = 0; s < 2; ++s)
+    igmc_launch_graph_update_plan(sd[s], s, d_user, d_item, d_rating, n, n_users_new, n_items_new, d_st, stream);
+  GU_TRY(hipGetLastError(), "a launch failed");
+  GU_TRY(hipMemcpyAsync(&h, d_st, sizeof(GuStats), hipMemcpyDeviceToHost, st), "hipMemcpyAsync failed");
+  GU_TRY(hipStreamSynchronize(st), "hipStreamSynchronize failed");
+  if (h.err & 1) GU_TRY(1, "a user id outside [0, n_users_new)");
+  if (h.err & 2) GU_TRY(1, "an item id outside [0, n_items_new)");
+  if (h.err & 4) GU_TRY(1, "the resulting nnz must fit int32");
+  if (h.nnz[0] != h.nnz[1]) GU_TRY(1, "internal: the two orientations disagree about nnz");
+  // the new graph: ONE allocation of exactly its six arrays
+  const int64_t nz = h.nnz[0];
+  int32_t* fptr[2];
+  GU_TRY(ng->mem.reserve(al(((size_t)n_users_new + 1) * 4) + al(((size_t)n_items_new + 1) * 4) +
+                         2 * (al((size_t)std::max<int64_t>(nz, 1) * 4) + al((size_t)std::max<int64_t>(nz, 1)))),
+         "hipMalloc failed");
+  for (int s = 0; s < 2; ++s)
+    GU_TRY(ng->mem.get(&fptr[s], (size_t)sd[s].rows_new + 1) || ng->mem.get(&sd[s].nidx, (size_t)nz) ||
+               ng->mem.get(&sd[s].nrel, (size_t)nz),
+           "hipMalloc failed");
+  for (int s = 0; s < 2; ++s) {
+    igmc_launch_graph_update_write(sd[s], s, n, g->nnz, d_st, stream);
+    GU_TRY(hipMemcpyAsync(fptr[s], sd[s].nptr, ((size_t)sd[s].rows_new + 1) * 4, hipMemcpyDeviceToDevice, st),
+           "hipMemcpyAsync failed");
+  }
+  GU_TRY(hipGetLastError(), "a launch failed");
+  GU_TRY(hipMemcpyAsync(&h, d_st, sizeof(GuStats), hipMemcpyDeviceToHost, st), "hipMemcpyAsync failed");
+  GU_TRY(hipStreamSynchronize(st), "hipStreamSynchronize failed");
+  if (owned) hipFree(scratch);
+  ng->device = g->device;
+  ng->nnz = nz;
+  ng->max_rel = h.max_rel;
+  ng->max_deg_u = h.max_deg[0];
+  ng->max_deg_v = h.max_deg[1];
+  ng->d.n_users = n_users_new;
+  ng->d.n_items = n_items_new;
+  ng->d.u_ptr = fptr[0]; ng->d.u_idx = sd[0].nidx; ng->d.u_rel = sd[0].nrel;
+  ng->d.v_ptr = fptr[1]; ng->d.v_idx = sd[1].nidx; ng->d.v_rel = sd[1].nrel;
+  *out = ng;
+  return 0;
+}
+#undef GU_TRY

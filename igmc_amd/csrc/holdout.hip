@@ -21,8 +21,23 @@
 //                  chunks before it.  The output is a function of the inputs alone: the only atomics are the LDS histogram /
 //                  list-cursor adds, which commute, and the error word's OR, reached on errors only.  Plain vector stores.
 //                  Rows of any length: LDS holds the histogram, the parked list and the scan words, never the row.
-#include "launch.h"
+#include "capi.h"
 #include "kth_key.h"        // the k-th smallest key of the row
+
+struct HoldArgs {
+  GraphDev g;
+  const int32_t* users;
+  int nq;
+  int64_t keep, hold;
+  uint64_t seed, draw;          // fill
+  int64_t* counts;              // count
+  const int64_t* off;           // fill
+  int32_t* link_u;
+  int32_t* link_v;
+  uint8_t* rating;
+  int64_t capacity;
+  int32_t* err;
+};
 
 struct HoldLds {
   int hist[IGMC_BLOCK];
@@ -116,7 +131,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_holdout(HoldArgs a) {
 }
 
 // ------------------------------------------------------------------ host
-void igmc_launch_holdout(const HoldArgs& a, int fill, void* stream) {
+static void igmc_launch_holdout(const HoldArgs& a, int fill, void* stream) {
   if (a.nq < 1) return;
   const int64_t jobs = fill ? (int64_t)a.nq : ((int64_t)a.nq + IGMC_BLOCK - 1) / IGMC_BLOCK;
   const int grid = (int)(jobs > 65536 ? 65536 : jobs);        // as k_candidates caps it: a workgroup takes a second request
@@ -124,4 +139,47 @@ void igmc_launch_holdout(const HoldArgs& a, int fill, void* stream) {
     IGMC_PLAUNCH("k_holdout_fill", k_holdout<true>, grid, IGMC_BLOCK, 0, stream, a);
   else
     IGMC_PLAUNCH("k_holdout_count", k_holdout<false>, grid, IGMC_BLOCK, 0, stream, a);
+}
+
+// ------------------------------------------------------------------ C ABI
+// what both entry points take; returns the refusal, or null
+static const char* hold_args(HoldArgs* a, const igmc_graph* g, const int32_t* d_users, int nq, int64_t keep, int64_t hold,
+                             int32_t* d_err) {
+  if (!g || !d_users || !d_err) return "null argument";
+  if (nq < 0) return "nq must be at least 0";
+  if (keep < 0) return "keep must be at least 0";
+  if (hold < 0) return "hold must be at least 0";
+  *a = HoldArgs{g->d, d_users, nq, keep, hold};
+  a->err = d_err;
+  return nullptr;
+}
+extern "C" int igmc_holdout_count(const igmc_graph* g, const int32_t* d_users, int nq, int64_t keep, int64_t hold,
+                                  int64_t* d_counts, int32_t* d_err, void* stream) {
+  HoldArgs a;
+  const char* bad = hold_args(&a, g, d_users, nq, keep, hold, d_err);
+  if (bad) IGMC_FAIL(bad);
+  if (!d_counts) IGMC_FAIL("null argument");
+  a.counts = d_counts;
+  igmc_launch_holdout(a, 0, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int igmc_holdout_fill(const igmc_graph* g, const int32_t* d_users, int nq, int64_t keep, int64_t hold, uint64_t seed,
+                                 uint64_t draw, const int64_t* d_offsets, int32_t* d_link_u, int32_t* d_link_v,
+                                 uint8_t* d_rating, int64_t capacity, int32_t* d_err, void* stream) {
+  HoldArgs a;
+  const char* bad = hold_args(&a, g, d_users, nq, keep, hold, d_err);
+  if (bad) IGMC_FAIL(bad);
+  if (!d_offsets || !d_link_u || !d_link_v || !d_rating) IGMC_FAIL("null argument");
+  if (capacity < 0) IGMC_FAIL("capacity must be at least 0");
+  a.seed = seed;
+  a.draw = draw;
+  a.off = d_offsets;
+  a.link_u = d_link_u;
+  a.link_v = d_link_v;
+  a.rating = d_rating;
+  a.capacity = capacity;
+  igmc_launch_holdout(a, 1, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
 }

@@ -1,4 +1,4 @@
-// launch.h -- host-side launcher declarations + optional per-kernel HIP-event timing (internal).
+// launch.h -- host-side launcher declarations that cross translation units + optional per-kernel HIP-event timing (internal).
 #pragma once
 #include "model.h"
 #include <string.h>
@@ -39,6 +39,7 @@ static inline int igmc_sample_park() { const char* e = getenv("IGMC_SAMPLE_PARK"
 #else
 #define IGMC_SAMPLE_PARK IGMC_BLOCK
 #endif
+// (IGMC_CAND_TILE_ITEMS, the enumeration's tile that tests/selection_checks.py restates, stands with CandArgs in cand_tile.h)
 
 // model.hip
 // auxiliary streams / events of a model (created with it; no launch sequence uses them at present: see the note at k_wgrad)
@@ -111,182 +112,10 @@ int igmc_launch_loss_grad(const ModelDev& m, const BatchDev& b, const StepPlan& 
 //  *img_emitted = 1 when the step's last kernel also left the weight images of the updated parameters in m.g2_w)
 void igmc_launch_loss(const ModelDev& m, const BatchDev& b, float ARR, float* loss, void* stream);
 void igmc_launch_sse(const BatchDev& b, const float* out, double* acc, int64_t* ctrl, void* stream);
-// scores.hip: the scoring step's tail (k_sse_acc + the outputs / labels filed at their positions) and the extremes of a key array
-#define IGMC_SELECT_MAX_GRID 1024
-#define IGMC_SELECT_MAX_NUM 64
-void igmc_launch_scores_store(const BatchDev& b, const float* out, double* acc, int64_t* ctrl, float* scores, float* labels,
-                              int64_t n, int64_t first, int32_t* err, void* stream);
-int igmc_select_default_grid(int64_t n);
-void igmc_launch_select(const float* keys, int64_t n, int num, int grid, void* scratch, int32_t* idx_low, int32_t* idx_high,
-                        float* key_low, float* key_high, int32_t* count, void* stream);
-// candidates.hip: the candidate links of a set of users (count, then fill at the offsets of the counts) -- every candidate, or
-// (sampled) cut down to k sampled negatives + the must items of every request: ONE kernel template, k_candidates<fill, sampled>
-// -- and the `num` first of every segment of a key array in the order (key descending, index ascending)
-#define IGMC_CAND_TILE_ITEMS 16384      // items of one LDS bitmap tile of the enumeration (wider graphs: tile after tile)
-#define IGMC_SEGSEL_MAX_SPLIT 64        // workgroups per segment at most (64 lists of 64 words are what the merge stages)
-struct CandArgs {
-  GraphDev g;
-  const int32_t* users;
-  int nq;
-  const uint8_t* item_ok;
-  int exclude_seen;
-  const int64_t* must_off;      // sampled; null: no request has must items
-  const int32_t* must_item;
-  int64_t n_must;
-  int k;
-  uint64_t seed, draw;          // sampled fill
-  int64_t* counts;              // count
-  const int64_t* off;           // fill
-  int32_t* link_u;
-  int32_t* link_v;
-  uint8_t* forced;              // sampled fill; may be null
-  int64_t capacity;
-  int32_t* err;
-};
-void igmc_launch_candidates(const CandArgs& a, int fill, int sampled, void* stream);
-int igmc_segsel_default_split(int ns);
-void igmc_launch_select_segments(const float* keys, const int64_t* seg_off, int ns, int num, int k, void* scratch,
-                                 int32_t* idx_out, float* key_out, int32_t* count, void* stream);
-// holdout.hip: the Given-k split of a set of users -- per user a uniform `kept`-subset of the row stays, the rest is written as
-// held-out links in the row's own order (count, then fill at the offsets of the counts): k_holdout<fill>
-struct HoldArgs {
-  GraphDev g;
-  const int32_t* users;
-  int nq;
-  int64_t keep, hold;
-  uint64_t seed, draw;          // fill
-  int64_t* counts;              // count
-  const int64_t* off;           // fill
-  int32_t* link_u;
-  int32_t* link_v;
-  uint8_t* rating;
-  int64_t capacity;
-  int32_t* err;
-};
-void igmc_launch_holdout(const HoldArgs& a, int fill, void* stream);
-// pairs.hip: pair training -- one negative per positive link and epoch drawn into a link list of (positive, negative) slots, and
-// the pair loss of a batch of such slots with its gradient w.r.t. the outputs
-#define IGMC_PAIR_TRIES 256             // hashed candidates tried before the cyclic scan decides (IGMC_PAIR_TRIES: test hook)
-struct PairArgs {
-  GraphDev g;
-  const int32_t* pos_u;
-  const int32_t* pos_v;
-  int64_t n;
-  const uint8_t* item_ok;       // may be null
-  uint64_t seed, epoch;
-  int tries;
-  int32_t* link_u;              // [2n] each
-  int32_t* link_v;
-  float* link_y;
-  int32_t* err;
-  const int64_t* sl_off;        // igmc_pair_negatives_shortlist alone: the per-user table, its entries, floor(share * 2^32)
-  const int32_t* sl_item;
-  int64_t sl_total;
-  uint64_t hard_thr;
-};
-void igmc_launch_pair_negatives(const PairArgs& a, void* stream);
-void igmc_launch_pair_negatives_shortlist(const PairArgs& a, void* stream);
-void igmc_launch_pair_kind_stats(const float* out, const float* y, int B, double* stats6, void* stream);
+// pairs.hip: the pair loss of a batch of (positive, negative) slots with its gradient w.r.t. the outputs, and the ARR term
+// filed into its stats -- igmc_pair_loss_grad (capi.hip) runs them between the model's forward and backward
 void igmc_launch_pair_loss(const float* out, const float* y, int B, float mse_weight, float* gout, double* stats, void* stream);
 void igmc_launch_pair_arr(const float* arr_part, float ARR, double* stats, void* stream);
-// shortlist.hip: the co-rating shortlist of a set of users (igmc_hip.h states the definition) -- the segments themselves, or
-// the places of given items in the full vote order
-#define IGMC_SHORT_TILE_ITEMS IGMC_CAND_TILE_ITEMS      // items of the LDS vote table (uint32 each, 64 KB): every bundled dataset
-                                                        // and ml_10m (10 677 items) in one tile; wider graphs keep their votes in
-                                                        // the workgroup's scratch row
-#define IGMC_SHORT_LDS_BYTES (160 * 1024)               // LDS of one workgroup at most (gfx950: 160 KB a CU): w sits in LDS
-                                                        // where it fits beside the fixed part and the vote table, else in scratch
-#define IGMC_SHORT_MAX_GRID 512                         // workgroups (and scratch rows) where the caller names no grid: 2 a CU
-struct ShortArgs {
-  GraphDev g;
-  const int32_t* users;
-  int nq;
-  const uint8_t* item_ok;
-  int exclude_seen;
-  int seed_min_rel, vote_min_rel;
-  int64_t m;                    // fill
-  const int64_t* off;
-  int32_t* link_u;
-  int32_t* link_v;
-  uint32_t* votes_out;          // may be null
-  int64_t capacity;
-  const int64_t* q_off;         // places
-  const int32_t* q_id;
-  int64_t n_query;
-  int32_t* q_place;
-  uint32_t* q_votes;            // may be null
-  int32_t* err;
-  uint32_t* scratch;            // [grid] rows of row_words: w (n_users words, where not in LDS), then the votes (n_items words,
-  int64_t row_words;            // where the graph is wider than the LDS vote table)
-};
-struct ShortPlan {
-  int grid, w_lds, v_lds;       // workgroups; w / the vote table in LDS
-  int lds_bytes;                // dynamic LDS of the launch
-  int64_t row_words, scratch_bytes;
-  int w_lds_max_users;          // the most users whose w fits LDS for this graph's item count
-};
-void igmc_shortlist_plan(int n_users, int n_items, int nq, int grid, ShortPlan* p);
-int igmc_shortlist_prepare();
-void igmc_launch_shortlist(const ShortArgs& a, const ShortPlan& p, int places, void* stream);
-// ranking.hip: the position and the 0-based place (the order of igmc_launch_select_segments) of given ids in their segments,
-// and the per-segment sums of the ranking metrics over those places
-#define IGMC_RANK_MAX_KS 8              // cut-offs K of one metrics launch at most
-void igmc_launch_rank_segments(const float* keys, const int32_t* ids, int64_t n, const int64_t* seg_off, int ns,
-                               const int64_t* q_off, const int32_t* q_id, int64_t nq, int k, int32_t* q_pos, int32_t* q_rank,
-                               int32_t* err, void* stream);
-void igmc_launch_rank_metrics(const int32_t* q_rank, const int64_t* q_off, const uint8_t* q_rel, const int32_t* ks, int nk,
-                              int ns, int64_t nq, int grid, int32_t* cnt, double* dcg, int32_t* err, void* stream);
-// graph_update.hip: rating changes applied to a resident graph -- one orientation at a time (side 0: rows are users, side 1:
-// rows are items).  plan: the sorted change list, the new row lengths, their prefix sums, nnz and the longest row; write: the
-// rows of the new graph, once the caller has read nnz and allocated them.
-struct GuStats {
-  int32_t err;              // bit 0: a user id out of range, bit 1: an item id out of range, bit 2: nnz does not fit int32
-  int32_t max_deg[2];
-  int32_t max_rel;
-  long long nnz[2];
-};
-struct GuSide {
-  const int32_t* optr;      // the old graph's arrays of this orientation
-  const int32_t* oidx;
-  const uint8_t* orel;
-  int rows_old, rows_new;
-  unsigned long long* keys; // [padded n] sorted (row << 32 | col) words
-  uint32_t* idx;            // [padded n] their list positions
-  int16_t* s_new;           // [n] -1: overridden, 0: the winner removes, else the winner's rating
-  int16_t* s_old;           // [n] a winner's relation in the old row, or -1
-  uint8_t* touched;         // [rows_new] the row has changes in the list
-  int32_t* nptr;            // the new graph's arrays
-  int32_t* nidx;
-  uint8_t* nrel;
-};
-int64_t igmc_graph_update_padded(int64_t n);
-void igmc_launch_graph_update_plan(const GuSide& s, int side, const int32_t* user, const int32_t* item, const uint8_t* rating,
-                                   int64_t n, int n_users, int n_items, GuStats* st, void* stream);
-void igmc_launch_graph_update_write(const GuSide& s, int side, int64_t n, int64_t nnz_old, GuStats* st, void* stream);
-// explain.hip: leave-one-out variants of the links of an extracted arena written into a node-set cache (count, then fill at
-// the offsets of the counts), and the variant scores turned into per-link attribution segments
-struct LooCache {
-  const int64_t* var_off;   // [B + 1] each: the batch's slice of the prefix sums of the three counts
-  const int64_t* uent_off;
-  const int64_t* vent_off;
-  int64_t cap_var, cap_uent, cap_vent;
-  int64_t* uoff;            // [cap_var + 1]  the cache arrays igmc_launch_load_nodes reads
-  int32_t* unodes;          // [cap_uent]
-  uint8_t* udist;
-  int64_t* voff;
-  int32_t* vnodes;          // [cap_vent]
-  uint8_t* vdist;
-  int32_t* var_link;        // [cap_var] each
-  uint8_t* var_side;
-  int32_t* var_node;
-  uint8_t* var_rating;
-};
-void igmc_launch_loo_count(const BatchDev& b, int B, int64_t* nvar, int64_t* nu_ids, int64_t* nv_ids, void* stream);
-int igmc_loo_default_chunks();
-void igmc_launch_loo_fill(const GraphDev& g, const BatchDev& b, int B, int64_t link0, const LooCache& c, int chunks, int32_t* err,
-                          void* stream);
-void igmc_launch_loo_deltas(const float* scores, const int64_t* var_off, int64_t n_links, float* base, float* delta, float* key,
-                            const int64_t* seg_off, void* stream);
 int igmc_model_prepare(const ModelDev& m);
 void igmc_launch_adam(float* p, const float* g, float* m1, float* m2, int64_t n, const AdamHyper& h, int64_t* ctrl, int tick,
                       void* stream);

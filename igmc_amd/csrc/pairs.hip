@@ -20,9 +20,28 @@
 // k_pair_kind_stats one workgroup over the same batch: count, ordered pairs and pair term per kind of negative (label 1 / 2), the
 //                   sums as k_pair_loss forms them.
 // Plain vector stores only (error word: a vector atomic OR, reached on errors only).
-#include "launch.h"
+#include "capi.h"
+#include <stdlib.h>
 
 #define PAIR_GRID_MAX 2048      // workgroups of the sampler at most: four positives each, the rest by the grid stride
+#define IGMC_PAIR_TRIES 256             // hashed candidates tried before the cyclic scan decides (IGMC_PAIR_TRIES: test hook)
+struct PairArgs {
+  GraphDev g;
+  const int32_t* pos_u;
+  const int32_t* pos_v;
+  int64_t n;
+  const uint8_t* item_ok;       // may be null
+  uint64_t seed, epoch;
+  int tries;
+  int32_t* link_u;              // [2n] each
+  int32_t* link_v;
+  float* link_y;
+  int32_t* err;
+  const int64_t* sl_off;        // igmc_pair_negatives_shortlist alone: the per-user table, its entries, floor(share * 2^32)
+  const int32_t* sl_item;
+  int64_t sl_total;
+  uint64_t hard_thr;
+};
 
 template <bool HARD>
 __global__ __launch_bounds__(IGMC_BLOCK) void k_pair_negatives(PairArgs a) {
@@ -184,15 +203,15 @@ static int pair_grid(int64_t n) {
   return (int)(blocks < 1 ? 1 : blocks > PAIR_GRID_MAX ? PAIR_GRID_MAX : blocks);
 }
 
-void igmc_launch_pair_negatives(const PairArgs& a, void* stream) {
+static void igmc_launch_pair_negatives(const PairArgs& a, void* stream) {
   IGMC_PLAUNCH("k_pair_negatives", k_pair_negatives<false>, pair_grid(a.n), IGMC_BLOCK, 0, stream, a);
 }
 
-void igmc_launch_pair_negatives_shortlist(const PairArgs& a, void* stream) {
+static void igmc_launch_pair_negatives_shortlist(const PairArgs& a, void* stream) {
   IGMC_PLAUNCH("k_pair_negatives_shortlist", k_pair_negatives<true>, pair_grid(a.n), IGMC_BLOCK, 0, stream, a);
 }
 
-void igmc_launch_pair_kind_stats(const float* out, const float* y, int B, double* stats6, void* stream) {
+static void igmc_launch_pair_kind_stats(const float* out, const float* y, int B, double* stats6, void* stream) {
   IGMC_PLAUNCH("k_pair_kind_stats", k_pair_kind_stats, 1, IGMC_BLOCK, 0, stream, out, y, B / 2, stats6);
 }
 
@@ -202,4 +221,59 @@ void igmc_launch_pair_loss(const float* out, const float* y, int B, float mse_we
 
 void igmc_launch_pair_arr(const float* arr_part, float ARR, double* stats, void* stream) {
   IGMC_PLAUNCH("k_pair_arr", k_pair_arr, 1, 64, 0, stream, arr_part, ARR, stats);
+}
+
+// ------------------------------------------------------------------ C ABI (igmc_pair_loss_grad runs the model: capi.hip)
+static int pair_tries() {
+  int tries = IGMC_PAIR_TRIES;
+  if (const char* e = getenv("IGMC_PAIR_TRIES")) tries = atoi(e);      // (test hook: the cyclic scan after few tries, or none)
+  return tries < 0 ? 0 : tries > (1 << 20) ? (1 << 20) : tries;
+}
+
+extern "C" int igmc_pair_negatives(const igmc_graph* g, const int32_t* d_pos_u, const int32_t* d_pos_v, int64_t n,
+                                   const uint8_t* d_item_ok, uint64_t seed, uint64_t epoch, int32_t* d_link_u,
+                                   int32_t* d_link_v, float* d_link_y, int32_t* d_err, void* stream) {
+  if (!g || !d_pos_u || !d_pos_v || !d_link_u || !d_link_v || !d_link_y || !d_err) IGMC_FAIL("null argument");
+  if (n < 1 || n >= ((int64_t)1 << 30)) IGMC_FAIL("n must be in [1, 2^30): the 2 n link positions are int32");
+  const PairArgs a = {g->d, d_pos_u, d_pos_v, n, d_item_ok, seed, epoch, pair_tries(), d_link_u, d_link_v, d_link_y, d_err};
+  igmc_launch_pair_negatives(a, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int igmc_pair_negatives_shortlist(const igmc_graph* g, const int32_t* d_pos_u, const int32_t* d_pos_v, int64_t n,
+                                             const uint8_t* d_item_ok, uint64_t seed, uint64_t epoch, const int64_t* d_sl_off,
+                                             const int32_t* d_sl_item, int64_t sl_total, double hard_share, int32_t* d_link_u,
+                                             int32_t* d_link_v, float* d_link_y, int32_t* d_err, void* stream) {
+  if (!g || !d_pos_u || !d_pos_v || !d_link_u || !d_link_v || !d_link_y || !d_err) IGMC_FAIL("null argument");
+  if (n < 1 || n >= ((int64_t)1 << 30)) IGMC_FAIL("n must be in [1, 2^30): the 2 n link positions are int32");
+  if (!(hard_share >= 0.0 && hard_share <= 1.0)) IGMC_FAIL("hard_share must be in [0, 1]");
+  if (hard_share > 0.0 && (!d_sl_off || !d_sl_item)) IGMC_FAIL("a share above 0 needs the table: d_sl_off and d_sl_item");
+  if (sl_total < 0 || sl_total >= ((int64_t)1 << 31)) IGMC_FAIL("sl_total must be in [0, 2^31)");
+  PairArgs a = {g->d, d_pos_u, d_pos_v, n, d_item_ok, seed, epoch, pair_tries(), d_link_u, d_link_v, d_link_y, d_err};
+  a.sl_off = d_sl_off;
+  a.sl_item = d_sl_item;
+  a.sl_total = sl_total;
+  a.hard_thr = igmc_pair_hard_threshold(hard_share);
+  if (a.hard_thr == 0) igmc_launch_pair_negatives(a, stream);      // (no pair can decide hard: the table is not looked at)
+  else igmc_launch_pair_negatives_shortlist(a, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int igmc_pair_kind_stats(const float* d_out, const float* d_y, int B, double* d_stats6, void* stream) {
+  if (!d_out || !d_y || !d_stats6) IGMC_FAIL("null argument");
+  if (B < 2 || (B & 1)) IGMC_FAIL("a pair batch holds an even number of links, at least two");
+  igmc_launch_pair_kind_stats(d_out, d_y, B, d_stats6, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int igmc_pair_loss(const float* d_out, const float* d_y, int B, float mse_weight, float* d_gout, double* d_stats,
+                              void* stream) {
+  if (!d_out || !d_y || !d_gout || !d_stats) IGMC_FAIL("null argument");
+  if (B < 2 || (B & 1)) IGMC_FAIL("a pair batch holds an even number of links, at least two");
+  igmc_launch_pair_loss(d_out, d_y, B, mse_weight, d_gout, d_stats, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
 }

@@ -21,9 +21,10 @@
 //                 xor butterfly -- float64 sums in an order that depends on the user's queries alone, so the output is
 //                 bit-identical for every grid.
 // Plain vector loads and stores; atomics: the LDS and global integer adds of the counts, the OR of the error word.
-#include "launch.h"
+#include "capi.h"
 #include "select.h"
 
+#define IGMC_RANK_MAX_KS 8              // cut-offs K of one metrics launch at most
 #define RANK_TILE IGMC_BLOCK      // queries of one tile: at most one per thread
 #define RANK_CHUNK 2048           // selection words of a slice staged at a time (16 KB)
 
@@ -207,7 +208,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_rank_metrics(const int32_t* __re
 // ------------------------------------------------------------------ host
 static int rank_grid(int64_t jobs) { return (int)(jobs < 1 ? 1 : jobs > 65536 ? 65536 : jobs); }
 
-void igmc_launch_rank_segments(const float* keys, const int32_t* ids, int64_t n, const int64_t* seg_off, int ns,
+static void igmc_launch_rank_segments(const float* keys, const int32_t* ids, int64_t n, const int64_t* seg_off, int ns,
                                const int64_t* q_off, const int32_t* q_id, int64_t nq, int k, int32_t* q_pos, int32_t* q_rank,
                                int32_t* err, void* stream) {
   const int64_t most = nq > ns ? nq : (int64_t)ns;
@@ -220,9 +221,36 @@ void igmc_launch_rank_segments(const float* keys, const int32_t* ids, int64_t n,
                nq, (const int32_t*)q_pos, q_rank, (const int32_t*)err);
 }
 
-void igmc_launch_rank_metrics(const int32_t* q_rank, const int64_t* q_off, const uint8_t* q_rel, const int32_t* ks, int nk,
+static void igmc_launch_rank_metrics(const int32_t* q_rank, const int64_t* q_off, const uint8_t* q_rel, const int32_t* ks, int nk,
                               int ns, int64_t nq, int grid, int32_t* cnt, double* dcg, int32_t* err, void* stream) {
   const int waves = IGMC_BLOCK >> 6;
   IGMC_PLAUNCH("k_rank_metrics", k_rank_metrics, grid > 0 ? grid : rank_grid(((int64_t)ns + waves - 1) / waves), IGMC_BLOCK, 0,
                stream, q_rank, q_off, q_rel, ks, nk, ns, nq, cnt, dcg, err);
+}
+
+// ------------------------------------------------------------------ C ABI
+extern "C" int igmc_rank_segments(const float* d_keys, const int32_t* d_ids, int64_t n, const int64_t* d_seg_off, int ns,
+                                  const int64_t* d_q_off, const int32_t* d_q_id, int64_t nq, int32_t* d_q_pos,
+                                  int32_t* d_q_rank, int32_t* d_err, int geometry, void* stream) {
+  if (!d_keys || !d_ids || !d_seg_off || !d_q_off || !d_err) IGMC_FAIL("null argument");
+  if (nq > 0 && (!d_q_id || !d_q_pos || !d_q_rank)) IGMC_FAIL("null argument");
+  if (n < 1 || n > (int64_t)INT32_MAX) IGMC_FAIL("n must be in [1, 2^31)");
+  if (nq < 0 || nq > (int64_t)INT32_MAX) IGMC_FAIL("nq must be in [0, 2^31)");
+  if (ns < 1 || geometry < 0 || geometry > IGMC_SEGSEL_MAX_SPLIT) IGMC_FAIL("ns must be at least 1, geometry in [0, 64]");
+  igmc_launch_rank_segments(d_keys, d_ids, n, d_seg_off, ns, d_q_off, d_q_id, nq,
+                            geometry > 0 ? geometry : igmc_segsel_default_split(ns), d_q_pos, d_q_rank, d_err, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int igmc_rank_metrics(const int32_t* d_q_rank, const int64_t* d_q_off, const uint8_t* d_q_rel, int64_t nq, int ns,
+                                 const int32_t* d_ks, int nk, int32_t* d_cnt, double* d_dcg, int32_t* d_err, int grid,
+                                 void* stream) {
+  if (!d_q_off || !d_ks || !d_cnt || !d_dcg || !d_err) IGMC_FAIL("null argument");
+  if (nq > 0 && !d_q_rank) IGMC_FAIL("null argument");
+  if (nq < 0 || nq > (int64_t)INT32_MAX) IGMC_FAIL("nq must be in [0, 2^31)");
+  if (ns < 1 || nk < 1 || nk > IGMC_RANK_MAX_KS || grid < 0 || grid > 65536)
+    IGMC_FAIL("ns must be at least 1, nk in [1, 8], grid in [0, 65536]");
+  igmc_launch_rank_metrics(d_q_rank, d_q_off, d_q_rel, d_ks, nk, ns, nq, grid, d_cnt, d_dcg, d_err, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
 }

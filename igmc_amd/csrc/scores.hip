@@ -14,8 +14,10 @@
 // depend on how the keys are divided among threads, waves or workgroups (any grid gives the same lists).
 // Selection is `num` rounds of "smallest word above the last one taken" (and its mirror): no sorting network, no atomics,
 // plain vector stores only; num <= 64 rounds over data that sits in L2 (1 M keys = 4 MB).
-#include "launch.h"
-#include "select.h"      // sel_image / sel_word, SEL_LOW_NONE / SEL_HIGH_NONE
+#include "capi.h"
+#include "select.h"      // sel_image / sel_word, SEL_LOW_NONE / SEL_HIGH_NONE, IGMC_SELECT_MAX_NUM
+
+#define IGMC_SELECT_MAX_GRID 1024
 
 // (min, max) over the workgroup, result in every thread.  sm: 2 * 4 words of LDS.
 __device__ __forceinline__ void sel_block_minmax(unsigned long long& lo, unsigned long long& hi, unsigned long long* sm) {
@@ -130,19 +132,19 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_scores_store(BatchDev b, const f
 }
 
 // ------------------------------------------------------------------ host
-void igmc_launch_scores_store(const BatchDev& b, const float* out, double* acc, int64_t* ctrl, float* scores, float* labels,
+static void igmc_launch_scores_store(const BatchDev& b, const float* out, double* acc, int64_t* ctrl, float* scores, float* labels,
                               int64_t n, int64_t first, int32_t* err, void* stream) {
   IGMC_PLAUNCH("k_scores_store", k_scores_store, 1, IGMC_BLOCK, 0, stream, b, out, acc, ctrl, scores, labels, n, first, err);
 }
 
 // workgroups of the partial pass where the caller names none: 16 keys per thread and round, at most SEL_MAX_GRID lists to merge
-int igmc_select_default_grid(int64_t n) {
+static int igmc_select_default_grid(int64_t n) {
   const int64_t per = (int64_t)IGMC_BLOCK * 16;
   const int64_t g = (n + per - 1) / per;
   return (int)(g < 1 ? 1 : g > IGMC_SELECT_MAX_GRID ? IGMC_SELECT_MAX_GRID : g);
 }
 
-void igmc_launch_select(const float* keys, int64_t n, int num, int grid, void* scratch, int32_t* idx_low, int32_t* idx_high,
+static void igmc_launch_select(const float* keys, int64_t n, int num, int grid, void* scratch, int32_t* idx_low, int32_t* idx_high,
                         float* key_low, float* key_high, int32_t* count, void* stream) {
   unsigned long long* part_low = (unsigned long long*)scratch;
   unsigned long long* part_high = part_low + (size_t)grid * num;
@@ -150,4 +152,39 @@ void igmc_launch_select(const float* keys, int64_t n, int num, int grid, void* s
   IGMC_PLAUNCH("k_select_merge", k_select_merge, 1, IGMC_BLOCK, 0, stream, keys, n, num,
                (const unsigned long long*)part_low, (const unsigned long long*)part_high, grid * num, idx_low, idx_high,
                key_low, key_high, count);
+}
+
+// ------------------------------------------------------------------ C ABI
+extern "C" int igmc_scores_store(const float* d_out, const igmc_batch* b, double* d_acc, float* d_scores, float* d_labels,
+                                 int64_t n, int64_t first_or_minus1, int64_t* d_ctrl, int32_t* d_err, void* stream) {
+  if (!d_out || !b || !d_acc || !d_scores || !d_labels || !d_err) IGMC_FAIL("null argument");
+  if (n < 1 || n > (int64_t)INT32_MAX) IGMC_FAIL("n must be in [1, 2^31)");
+  if (first_or_minus1 < -1 || first_or_minus1 >= n) IGMC_FAIL("first must be -1 (the arena's stamp) or a position below n");
+  igmc_launch_scores_store(b->d, d_out, d_acc, d_ctrl, d_scores, d_labels, n, first_or_minus1, d_err, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+static int select_grid(int64_t n, int num, int grid) {
+  if (n < 1 || n > (int64_t)INT32_MAX || num < 1 || num > IGMC_SELECT_MAX_NUM || grid < 0 || grid > IGMC_SELECT_MAX_GRID) return -1;
+  return grid > 0 ? grid : igmc_select_default_grid(n);
+}
+extern "C" int64_t igmc_select_scratch_bytes(int64_t n, int num, int grid) {
+  const int g = select_grid(n, num, grid);
+  if (g < 0) {
+    igmc_err() = std::string(__func__) + ": n must be in [1, 2^31), num in [1, 64], grid in [0, 1024]";
+    return -1;
+  }
+  return (int64_t)2 * g * num * (int64_t)sizeof(uint64_t);
+}
+extern "C" int igmc_select_extremes(const float* d_keys, int64_t n, int num, int32_t* d_idx_low, int32_t* d_idx_high,
+                                    float* d_key_low, float* d_key_high, int32_t* d_count, void* d_scratch,
+                                    int64_t scratch_bytes, int grid, void* stream) {
+  if (!d_keys || !d_idx_low || !d_idx_high || !d_scratch) IGMC_FAIL("null argument");
+  const int g = select_grid(n, num, grid);
+  if (g < 0) IGMC_FAIL("n must be in [1, 2^31), num in [1, 64], grid in [0, 1024]");
+  if (scratch_bytes < (int64_t)2 * g * num * (int64_t)sizeof(uint64_t)) IGMC_FAIL("scratch too small (igmc_select_scratch_bytes)");
+  if (((uintptr_t)d_scratch & 7) != 0) IGMC_FAIL("scratch must be 8-byte aligned");
+  igmc_launch_select(d_keys, n, num, g, d_scratch, d_idx_low, d_idx_high, d_key_low, d_key_high, d_count, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
 }

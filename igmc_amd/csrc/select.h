@@ -1,8 +1,13 @@
-// select.h -- the 64-bit selection word shared by scores.hip (extremes of one key vector) and candidates.hip (the first `num` of
-// every segment): order-preserving image of the float key in the high half, index in the low half.  Words are distinct, so
+// select.h -- the 64-bit selection word shared by scores.hip (extremes of one key vector), candidates.hip (the first `num` of
+// every segment) and ranking.hip (places in that order): order-preserving image of the float key in the high half, index in the low half.  Words are distinct, so
 // "the i-th of the order" is "the i-th smallest word" and minima / maxima of words are associative and commutative.
 #pragma once
 #include "common.h"
+
+// what the selections of scores.hip, candidates.hip and ranking.hip agree on
+#define IGMC_SELECT_MAX_NUM 64
+#define IGMC_SEGSEL_MAX_SPLIT 64        // workgroups per segment at most (64 lists of 64 words are what the merge stages)
+int igmc_segsel_default_split(int ns);      // candidates.hip; igmc_rank_segments (ranking.hip) splits its segments the same way
 
 #define SEL_LOW_NONE 0xFFFFFFFFFFFFFFFFull      // no word: above every word (a NaN's image is 0xFFFFFFFF, an index < 2^31)
 #define SEL_HIGH_NONE 0ull                       // no word: below every word (the image of -inf is 0x007FFFFF)

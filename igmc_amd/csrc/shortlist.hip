@@ -40,9 +40,44 @@
 //                  k_rank_check does.
 // All adds are integer atomics (LDS, or vector atomics on the scratch row), which commute: the output is a function of the
 // inputs alone, whatever the grid.  No float anywhere.  Plain vector loads and stores; the error word: a vector atomic OR.
-#include "launch.h"
+#include "capi.h"
 #include "cand_tile.h"
 #include "kth_key.h"
+
+#define IGMC_SHORT_TILE_ITEMS IGMC_CAND_TILE_ITEMS      // items of the LDS vote table (uint32 each, 64 KB): every bundled dataset
+                                                        // and ml_10m (10 677 items) in one tile; wider graphs keep their votes in
+                                                        // the workgroup's scratch row
+#define IGMC_SHORT_LDS_BYTES (160 * 1024)               // LDS of one workgroup at most (gfx950: 160 KB a CU): w sits in LDS
+                                                        // where it fits beside the fixed part and the vote table, else in scratch
+#define IGMC_SHORT_MAX_GRID 512                         // workgroups (and scratch rows) where the caller names no grid: 2 a CU
+struct ShortArgs {
+  GraphDev g;
+  const int32_t* users;
+  int nq;
+  const uint8_t* item_ok;
+  int exclude_seen;
+  int seed_min_rel, vote_min_rel;
+  int64_t m;                    // fill
+  const int64_t* off;
+  int32_t* link_u;
+  int32_t* link_v;
+  uint32_t* votes_out;          // may be null
+  int64_t capacity;
+  const int64_t* q_off;         // places
+  const int32_t* q_id;
+  int64_t n_query;
+  int32_t* q_place;
+  uint32_t* q_votes;            // may be null
+  int32_t* err;
+  uint32_t* scratch;            // [grid] rows of row_words: w (n_users words, where not in LDS), then the votes (n_items words,
+  int64_t row_words;            // where the graph is wider than the LDS vote table)
+};
+struct ShortPlan {
+  int grid, w_lds, v_lds;       // workgroups; w / the vote table in LDS
+  int lds_bytes;                // dynamic LDS of the launch
+  int64_t row_words, scratch_bytes;
+  int w_lds_max_users;          // the most users whose w fits LDS for this graph's item count
+};
 
 static_assert(IGMC_SHORT_TILE_ITEMS == CAND_TILE, "the vote table and the candidate ballots cover the same tile");
 
@@ -258,7 +293,7 @@ __global__ __launch_bounds__(IGMC_BLOCK) void k_short_check(const int64_t* __res
 }
 
 // ------------------------------------------------------------------ host
-void igmc_shortlist_plan(int n_users, int n_items, int nq, int grid, ShortPlan* p) {
+static void igmc_shortlist_plan(int n_users, int n_items, int nq, int grid, ShortPlan* p) {
   const int64_t fixed = (int64_t)sizeof(ShortLds);
   p->v_lds = n_items <= IGMC_SHORT_TILE_ITEMS;
   const int64_t vbytes = p->v_lds ? (int64_t)short_pad64(n_items) * 4 : 0;
@@ -273,7 +308,7 @@ void igmc_shortlist_plan(int n_users, int n_items, int nq, int grid, ShortPlan* 
 }
 
 // dynamic LDS above 64 KB needs an explicit opt-in on HIP (per device, once)
-int igmc_shortlist_prepare() {
+static int igmc_shortlist_prepare() {
 #ifndef IGMC_HIPEMU
   static bool done[64] = {};
   int dev = 0;
@@ -290,7 +325,7 @@ int igmc_shortlist_prepare() {
   return 0;
 }
 
-void igmc_launch_shortlist(const ShortArgs& a, const ShortPlan& p, int places, void* stream) {
+static void igmc_launch_shortlist(const ShortArgs& a, const ShortPlan& p, int places, void* stream) {
   if (places) {
     const int64_t most = a.n_query > a.nq ? a.n_query : (int64_t)a.nq;
     const int64_t cg = (most + IGMC_BLOCK - 1) / IGMC_BLOCK;
@@ -304,4 +339,101 @@ void igmc_launch_shortlist(const ShortArgs& a, const ShortPlan& p, int places, v
                      p.lds_bytes, stream, a);
       },
       places != 0, p.w_lds != 0, p.v_lds != 0);
+}
+
+// ------------------------------------------------------------------ C ABI
+// short_args checks and files what both entry points take, and plans the launch.  Returns the refusal, or null.
+static const char* short_args(ShortArgs* a, ShortPlan* p, const igmc_graph* g, const int32_t* d_users, int nq,
+                              const uint8_t* d_item_ok, int exclude_seen, int seed_min_rel, int vote_min_rel, int32_t* d_err,
+                              void* d_scratch, int64_t scratch_bytes, int grid) {
+  if (!g || !d_users || !d_err) return "null argument";
+  if (nq < 1) return "nq must be at least 1";
+  if (seed_min_rel < 0 || vote_min_rel < 0) return "seed_min_rel and vote_min_rel must be at least 0";
+  if (grid < 0 || grid > 65536) return "grid must be in [0, 65536]";
+  if ((int64_t)g->max_deg_u * (int64_t)g->max_deg_v > (int64_t)INT32_MAX)
+    return "max_deg_u * max_deg_v reaches 2^31: the vote counts may not fit";
+  igmc_shortlist_plan(g->d.n_users, g->d.n_items, nq, grid, p);
+  if (p->scratch_bytes > 0) {
+    if (!d_scratch) return "null argument";
+    if (scratch_bytes < p->scratch_bytes) return "scratch too small (igmc_shortlist_scratch_bytes)";
+    if (((uintptr_t)d_scratch & 3) != 0) return "scratch must be 4-byte aligned";
+  }
+  *a = ShortArgs{};
+  a->g = g->d;
+  a->users = d_users;
+  a->nq = nq;
+  a->item_ok = d_item_ok;
+  a->exclude_seen = exclude_seen != 0;
+  a->seed_min_rel = seed_min_rel;
+  a->vote_min_rel = vote_min_rel;
+  a->err = d_err;
+  a->scratch = (uint32_t*)d_scratch;
+  a->row_words = p->row_words;
+  if (igmc_shortlist_prepare()) return "the kernels' LDS size could not be set";
+  return nullptr;
+}
+extern "C" int64_t igmc_shortlist_scratch_bytes(const igmc_graph* g, int nq, int grid) {
+  if (!g || nq < 1 || grid < 0 || grid > 65536) {
+    igmc_err() = std::string(__func__) + ": a graph, nq of at least 1, grid in [0, 65536]";
+    return -1;
+  }
+  ShortPlan p;
+  igmc_shortlist_plan(g->d.n_users, g->d.n_items, nq, grid, &p);
+  return p.scratch_bytes;
+}
+extern "C" int igmc_shortlist_plan_info(const igmc_graph* g, int nq, int grid, int64_t out6[6]) {
+  if (!g || !out6) IGMC_FAIL("null argument");
+  if (nq < 1 || grid < 0 || grid > 65536) IGMC_FAIL("nq must be at least 1, grid in [0, 65536]");
+  ShortPlan p;
+  igmc_shortlist_plan(g->d.n_users, g->d.n_items, nq, grid, &p);
+  out6[0] = p.grid;
+  out6[1] = p.lds_bytes;
+  out6[2] = p.w_lds;
+  out6[3] = p.v_lds;
+  out6[4] = p.scratch_bytes;
+  out6[5] = p.w_lds_max_users;
+  return 0;
+}
+extern "C" int igmc_shortlist_fill(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
+                                   int exclude_seen, int seed_min_rel, int vote_min_rel, int64_t m, const int64_t* d_offsets,
+                                   int32_t* d_link_u, int32_t* d_link_v, uint32_t* d_votes, int64_t capacity, int32_t* d_err,
+                                   void* d_scratch, int64_t scratch_bytes, int grid, void* stream) {
+  ShortArgs a;
+  ShortPlan p;
+  if (!d_offsets || !d_link_u || !d_link_v) IGMC_FAIL("null argument");
+  if (m < 1 || m > (int64_t)INT32_MAX) IGMC_FAIL("m must be in [1, 2^31)");
+  if (capacity < 1 || capacity > (int64_t)INT32_MAX) IGMC_FAIL("capacity must be in [1, 2^31)");
+  const char* bad = short_args(&a, &p, g, d_users, nq, d_item_ok, exclude_seen, seed_min_rel, vote_min_rel, d_err, d_scratch,
+                               scratch_bytes, grid);
+  if (bad) IGMC_FAIL(bad);
+  a.m = m;
+  a.off = d_offsets;
+  a.link_u = d_link_u;
+  a.link_v = d_link_v;
+  a.votes_out = d_votes;
+  a.capacity = capacity;
+  igmc_launch_shortlist(a, p, 0, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+extern "C" int igmc_shortlist_places(const igmc_graph* g, const int32_t* d_users, int nq, const uint8_t* d_item_ok,
+                                     int exclude_seen, int seed_min_rel, int vote_min_rel, const int64_t* d_q_off,
+                                     const int32_t* d_q_id, int64_t n_query, int32_t* d_q_place, uint32_t* d_q_votes,
+                                     int32_t* d_err, void* d_scratch, int64_t scratch_bytes, int grid, void* stream) {
+  ShortArgs a;
+  ShortPlan p;
+  if (!d_q_off) IGMC_FAIL("null argument");
+  if (n_query < 0 || n_query > (int64_t)INT32_MAX) IGMC_FAIL("n_query must be in [0, 2^31)");
+  if (n_query > 0 && (!d_q_id || !d_q_place)) IGMC_FAIL("null argument");
+  const char* bad = short_args(&a, &p, g, d_users, nq, d_item_ok, exclude_seen, seed_min_rel, vote_min_rel, d_err, d_scratch,
+                               scratch_bytes, grid);
+  if (bad) IGMC_FAIL(bad);
+  a.q_off = d_q_off;
+  a.q_id = d_q_id;
+  a.n_query = n_query;
+  a.q_place = d_q_place;
+  a.q_votes = d_q_votes;
+  igmc_launch_shortlist(a, p, 1, stream);
+  HIPCHECK(hipGetLastError());
+  return 0;
 }
