@@ -887,6 +887,21 @@ extern "C" int igmc_debug_weight_images(const igmc_model* m, float* h_out, int64
   return 0;
 }
 
+// debug aid (tests): every byte of what the model step writes for a later launch and never clears itself -- the partial
+// weight-gradient tables, layer 3's centre vectors and the h_l rows -- set to `byte` (0xFF: NaNs).  A step must leave results
+// that do not depend on it: it stores every element the tail reads.  Synchronises the device.
+extern "C" int igmc_debug_fill_tables(igmc_model* m, int byte) {
+  if (!m) IGMC_FAIL("null argument");
+  if (byte < 0 || byte > 255) IGMC_FAIL("not a byte");
+  const ModelDev& d = m->d;
+  HIPCHECK(hipDeviceSynchronize());
+  if (d.ts_part) HIPCHECK(hipMemset(d.ts_part, byte, (size_t)4 * IGMC_TS_BLOCKS * d.ts_stride * sizeof(float)));
+  if (d.l3_vec) HIPCHECK(hipMemset(d.l3_vec, byte, (size_t)d.graph_cap * 2 * (G2_NR + 2) * 32 * sizeof(float)));
+  for (int l = 0; l < 4; ++l) HIPCHECK(hipMemset(d.h[l], byte, (size_t)d.node_cap * 32 * sizeof(float)));
+  HIPCHECK(hipDeviceSynchronize());
+  return 0;
+}
+
 extern "C" void igmc_model_destroy(igmc_model* m) {
   if (!m) return;
   for (int i = 0; i < 8; ++i) hipEventDestroy((hipEvent_t)m->ax.ev[i]);

@@ -189,6 +189,35 @@ __device__ __forceinline__ void g2_planes_load(uint32_t* pl, const unsigned char
   for (int c = wave; c < pieces; c += nwaves) g2_glds16<16>((const float4*)px + c * 64, (float4*)pl + c * 64, lane);
 }
 
+// ---- stores nobody in the launch waits for (the partial weight-gradient tables: their first reader is the tail's launch) --
+//      written THROUGH to memory (sc1): left as dirty L2 lines they are written back at the kernel's end, in front of the tail.
+//      Vector stores the compiler counts.
+// A table slot is a buffer of its own (wave-uniform base, `bytes` long: a store past it is dropped), the lane's offset in bytes.
+struct G2Slot {
+#ifndef IGMC_HIPEMU
+  __amdgpu_buffer_rsrc_t rs;
+#else
+  float* base;
+#endif
+};
+__device__ __forceinline__ G2Slot g2_slot(float* base, int bytes) {
+  G2Slot s;
+#ifndef IGMC_HIPEMU
+  s.rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000);
+#else
+  s.base = base;
+  (void)bytes;
+#endif
+  return s;
+}
+__device__ __forceinline__ void g2_slot_store16(const G2Slot& s, int off, const f32x4& v) {
+#ifndef IGMC_HIPEMU
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), s.rs, off, 0, 16);      // (aux 16 = sc1)
+#else
+  *(f32x4*)((char*)s.base + off) = v;
+#endif
+}
+
 #ifdef IGMC_HIPEMU
 #define G2_SCHED_BARRIER() do { } while (0)
 #else

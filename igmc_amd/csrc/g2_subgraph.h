@@ -942,7 +942,9 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
           f32x4 w3[3];
 #pragma unroll
           for (int i3 = 0; i3 < 3; ++i3) w3[i3] = (f32x4){0.f, 0.f, 0.f, 0.f};
-          const int m2w = wave >> 2, wo = wave & 3;       // tiles 3 wo .. 3 wo + 2 of the row half
+          // tiles 2 wo, 2 wo + 1 and 8 + wo of the row half: the first two are both 16-column halves of 16 rows of one block --
+          // whole 128-byte lines from one wave's two consecutive stores (which wave owns a tile does not touch its bits)
+          const int m2w = wave >> 2, wo = wave & 3;
 #pragma unroll 1
           for (int wb = 0; wb < G2_NB; ++wb) {
             const float* Tb = TILES + wb * 16 * G2_TP;
@@ -956,7 +958,7 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
               const float* db = Db + (4 * s4 + kq) * G2_XP + li;
 #pragma unroll
               for (int i3 = 0; i3 < 3; ++i3) {
-                const int nt = 3 * wo + i3;              // (wave-uniform: column tiles 10, 11 come from the dPre tile)
+                const int nt = i3 < 2 ? 2 * wo + i3 : 8 + wo;      // (wave-uniform: column tiles 10, 11 come from the dPre tile)
                 bw3[s4][i3] = (nt < 2 * G2_NR) ? tb[nt * 16] : db[(nt - 2 * G2_NR) * 16];
               }
             }
@@ -965,26 +967,37 @@ __global__ __launch_bounds__(G2_THREADS) void k_graph_step2(G2Args a) {
             for (int s4 = 0; s4 < 4; ++s4)
 #pragma unroll
               for (int i3 = 0; i3 < 3; ++i3)
-                w3[i3] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[s4], bw3[s4][i3], w3[i3], 0, 0, 0);
+                w3[i3] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw3[s4][i3], av[s4], w3[i3], 0, 0, 0);
           }
+          // The instruction takes one value a lane for each operand and the two enter symmetrically: with T' / dPre as ITS A and
+          // h_{l-1} as ITS B the accumulator holds the tile transposed -- lane (li, kq) the four consecutive COLUMNS 4 kq .. + 3 of
+          // table row 16 m2 + li, one 16-byte store a tile (four 4-byte stores 32 floats apart the other way round) -- from the
+          // same products added in the same k order: the same bits (profiles/table_handover_identity.txt).
+          // Nobody in the launch reads a table, so the straight-line forms write them through (g2_prims.h); the looping grid,
+          // which adds its later subgraphs to the slot, keeps ordinary stores.
 #pragma unroll
           for (int i3 = 0; i3 < 3; ++i3) {
-            const int m2 = m2w, nt = 3 * wo + i3;
+            const int m2 = m2w, nt = i3 < 2 ? 2 * wo + i3 : 8 + wo;
             const int r = nt >> 1;                      // 32-column block: relation, or G2_NR = root
             if (r >= R && r < G2_NR) continue;
-            float* pp = wpart + (kq * 4) * 32 + li + (r < R ? r : R) * 1024 + m2 * 512 + (nt & 1) * 16;
-            if (first_graph) {
-#pragma unroll
-              for (int rr = 0; rr < 4; ++rr) pp[rr * 32] = w3[i3][rr];
+            const int e = (r < R ? r : R) * 1024 + (m2 * 16 + li) * 32 + (nt & 1) * 16 + 4 * kq;
+            if constexpr (ONCE) {
+              g2_slot_store16(g2_slot(wpart, ts * 4), e * 4, w3[i3]);
             } else {
-#pragma unroll
-              for (int rr = 0; rr < 4; ++rr) pp[rr * 32] += w3[i3][rr];
+              float4* pp = (float4*)(wpart + e);
+              if (first_graph) {
+                *pp = make_float4(w3[i3][0], w3[i3][1], w3[i3][2], w3[i3][3]);
+              } else {
+                const float4 c = *pp;
+                *pp = make_float4(c.x + w3[i3][0], c.y + w3[i3][1], c.z + w3[i3][2], c.w + w3[i3][3]);
+              }
             }
           }
         }
         G2_STAMP(22 + 5 * (3 - l));
         // the opposite side's dPre_{l-1}: its waves raised their flags before their own table products (the exchange ran
         // under this one); global -> LDS, landed by the barrier below
+        // (layer 2's fetch between the halves of its table product: measured, slower -- profiles/table_handover_ab_bench.txt)
         if (l > 1) fetch(6 - l);
         __syncthreads();
         G2_STAMP(23 + 5 * (3 - l));
