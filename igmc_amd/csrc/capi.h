@@ -115,6 +115,19 @@ struct igmc_model {
   Allocs mem;
 };
 
+// g2_probe.h (graphstep2.hip): debug aid of the tests -- one primitive of g2_prims.h / g2_image.h over n items of device memory
+#define IGMC_PRIM_SPLIT 0    // (x, y) -> the three packed words of g2_split2
+#define IGMC_PRIM_TANH 1     // x -> g2_tanh(x)
+#define IGMC_PRIM_EXP 2      // x -> the exponential g2_tanh uses
+#define IGMC_PRIM_RCP 3      // x -> the reciprocal g2_tanh uses
+#define IGMC_PRIM_MFMA 4     // per lane of a wave: A [4], B [4], C [4] -> D [4] of one g2_mfma_bf16
+#define IGMC_PRIM_MASK 5     // (word, r1, keep bit, FLAGS) -> g2_expand4, g2_bytemask, g2_mask_frag
+#define IGMC_PRIM_OPS 6
+extern "C" int igmc_debug_g2_prims(int op, const void* in, int64_t n, void* out, void* stream);
+
+// capi.hip: debug aid of the tests -- the stored rows h_0 .. h_2 of the last training launch (igmc_debug_l3_sums reads h_2 through it)
+extern "C" int igmc_debug_layer_rows(const igmc_model* m, const igmc_batch* b, int layer, int form, float* h_out, int64_t n);
+
 // comm.hip: what igmc_train_step_dp needs of a communicator, and no more (c == NULL: one rank)
 IGMC_INTERNAL int igmc_comm_world(const igmc_comm* c);
 IGMC_INTERNAL StepExchange igmc_comm_exchange(igmc_comm* c);      // the sum of two spans, its user pointer, the peer failure word

@@ -854,19 +854,38 @@ extern "C" int igmc_debug_head_array(const igmc_model* m, int which, float* h_ou
 extern "C" int igmc_debug_l3_sums(const igmc_model* m, const igmc_batch* b, int which, float* h_out, int64_t n) {
   if (!m || !b || !h_out) IGMC_FAIL("null argument");
   if (which < 0 || which > 1) IGMC_FAIL("no such array");
-  const int64_t per = which == 0 ? 2 * (G2_NR + 2) * 32 : 2 * 128 * 32;
+  if (which == 1) return igmc_debug_layer_rows(m, b, 2, 0, h_out, n);      // (its own checks and synchronisation)
+  const int64_t per = 2 * (G2_NR + 2) * 32;
   if (n < 0 || n % per != 0 || n / per > (int64_t)m->d.graph_cap || n / per > (int64_t)b->d.graph_cap) IGMC_FAIL("size out of range");
   HIPCHECK(hipDeviceSynchronize());
-  if (which == 0) {
-    if (!m->d.l3_vec) IGMC_FAIL("array not allocated");
-    HIPCHECK(hipMemcpy(h_out, m->d.l3_vec, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  if (!m->d.l3_vec) IGMC_FAIL("array not allocated");
+  HIPCHECK(hipMemcpy(h_out, m->d.l3_vec, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// debug aid (tests): host copy of the rows h_layer (layer 0..2; h_3 of the centres is in feat: igmc_debug_head_array) the last
+// TRAINING launch stored for its backward.  form 0: per subgraph slot of the arena `b`, as the subgraph kernel addresses them --
+// [graphs][2 sides][128 rows][32], rows past a side's capacity left as the caller set them, n floats = a whole number of
+// subgraphs; form 1: by collated node index, as the dense-layer and the per-layer kernels address them -- the first n floats
+// (whole rows) of the array.  Synchronises the device.
+extern "C" int igmc_debug_layer_rows(const igmc_model* m, const igmc_batch* b, int layer, int form, float* h_out, int64_t n) {
+  if (!m || !b || !h_out) IGMC_FAIL("null argument");
+  if (layer < 0 || layer > 2) IGMC_FAIL("no such layer");
+  if (form < 0 || form > 1) IGMC_FAIL("no such form");
+  if (form == 1) {
+    if (n < 0 || n % 32 != 0 || n / 32 > (int64_t)m->d.node_cap || n / 32 > (int64_t)b->d.node_cap) IGMC_FAIL("size out of range");
+    HIPCHECK(hipDeviceSynchronize());
+    if (n) HIPCHECK(hipMemcpy(h_out, m->d.h[layer], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
   }
+  const int64_t per = 2 * 128 * 32;
+  if (n < 0 || n % per != 0 || n / per > (int64_t)m->d.graph_cap || n / per > (int64_t)b->d.graph_cap) IGMC_FAIL("size out of range");
   if ((int64_t)b->d.graph_cap * b->d.slot > (int64_t)m->d.node_cap) IGMC_FAIL("the arena's slots exceed the workspace");
+  HIPCHECK(hipDeviceSynchronize());
   for (int64_t g = 0; g < n / per; ++g)
     for (int sd = 0; sd < 2; ++sd) {
       const int rows = std::min(sd ? b->d.cap_v : b->d.cap_u, 128);
-      HIPCHECK(hipMemcpy(h_out + (g * 2 + sd) * 128 * 32, m->d.h[2] + ((size_t)g * b->d.slot + (sd ? b->d.cap_u : 0)) * 32,
+      HIPCHECK(hipMemcpy(h_out + (g * 2 + sd) * 128 * 32, m->d.h[layer] + ((size_t)g * b->d.slot + (sd ? b->d.cap_u : 0)) * 32,
                          (size_t)rows * 32 * sizeof(float), hipMemcpyDeviceToHost));
     }
   return 0;

@@ -42,7 +42,9 @@ __device__ __forceinline__ uint32_t g2_pk_bf16(float x, float y) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, g2_bf16x2));
 #endif
 }
-// the three bf16 terms of two f32 values: hi + mid + lo == x to 24 bits (each residual is exact in f32)
+// the three bf16 terms of two f32 values: hi + mid + lo == x EXACTLY for 2^-100 <= |x| < 2^127 (each residual is exact in f32 and
+// the third one fits 8 bits; below, a residual is an f32 subnormal, above, a term may overflow) -- held bit for bit against a
+// restatement of the rounding on both forms (tests/prims_checks.py, check_split; observed: profiles/prims_observed.txt)
 __device__ __forceinline__ void g2_split2(float x, float y, uint32_t& h, uint32_t& mi, uint32_t& lo) {
   h = g2_pk_bf16(x, y);
   const float rx = x - __uint_as_float(h << 16), ry = y - __uint_as_float(h & 0xFFFF0000u);

@@ -1,8 +1,11 @@
 // g2_prims.h -- the gfx950 primitives of graphstep2.hip: matrix-core step, byte-compare expansion, fast tanh, tagged
 // exchange words (sc1 stores / compiler-tracked sc1 buffer loads, polled), launch-sequence and clock helpers -- each with
 // its stand-in for the CPU emulation build (tools/hipemu, IGMC_HIPEMU: test infrastructure for the kernel LOGIC; what the
-// stand-ins replace is verified by the GPU suite only).  The kernels in graphstep2.hip are written against these names and
-// carry no build switch themselves.  (internal; included once, by graphstep2.hip, after g_g2_clk / g_g2_wg)
+// stand-ins replace is verified by the GPU suite only -- the arithmetic ones, g2_tanh, g2_mfma_bf16, g2_expand4 / g2_bytemask /
+// g2_mask_frag and g2_image.h's g2_pk_bf16 / g2_split2, one at a time through igmc_debug_g2_prims: g2_probe.h,
+// tests/test_gpu_prims.py; the stand-ins against the same restatements: tests/test_emu_prims.py).  The kernels in graphstep2.hip
+// are written against these names and carry no build switch themselves.  (internal; included once, by graphstep2.hip, after
+// g_g2_clk / g_g2_wg)
 #pragma once
 
 #ifdef IGMC_HIPEMU
@@ -93,6 +96,12 @@ __device__ __forceinline__ u32x4 g2_mask_frag(uint32_t m0, uint32_t m1) {
   return f;
 }
 
+// tanh on the device: 1 - 2 rcp(1 + exp(2x)) (v_exp_f32 behind the argument's scaling by log2 e, v_rcp_f32).  ABSOLUTE error
+// <= 8 * 2^-24: 3.0 * 2^-24 with correctly rounded operations (worst near x = -3.55) + one ulp of each instruction + the scaling
+// (derivation and check: tests/prims_checks.py, check_tanh).  Its results are multiples of 2^-24 around 0: exactly 0 for |x| < 3e-8
+// and a RELATIVE error above 1 below |x| ~ 1e-6; g2_tanh(+-0) = 0, |g2_tanh| <= 1, exactly +-1 from |x| = 10 and for +-inf, NaN
+// for NaN.  The emulation build calls tanhf (within an ulp of tanh): the two agree to the bound above and no closer, and only
+// tests/test_gpu_prims.py sees the device form.  Observed on both: profiles/prims_observed.txt.
 __device__ __forceinline__ float g2_tanh(float x) {
 #ifdef IGMC_HIPEMU
   return tanhf(x);

@@ -5,7 +5,7 @@
 // (extract.hip: k_relm).  With at most 128 nodes per side the per-relation aggregate of a 16-row bundle
 //     T_r[i] = sum_{j : rel(i,j) = r, edge j -> i kept} x[j]          (reference models.py:199-202 -> PyG RGCNConv, aggr = add)
 // is the dense product  T_r = A_r X  with A_r the 16 x K 0/1 block of relation r:  A_r is EXACT in bf16 and X splits
-// into three bf16 terms (hi + mid + lo = x to 24 bits; every product 1.0 * bf16 is exact and the sums are f32), so the
+// into three bf16 terms (hi + mid + lo = x exactly: g2_image.h; every product 1.0 * bf16 is exact and the sums are f32), so the
 // gather runs as v_mfma_f32_16x16x32_bf16 at f32 accuracy: 5 relations x 4 k-steps x 3 terms x 2 feature tiles = 120
 // MFMAs (~2 k cycles) per bundle and layer pass instead of ~11 k cycles of LDS row gathers (graphstep.hip).
 //
@@ -228,6 +228,7 @@ __device__ __forceinline__ void g2_transform(const f32x4 (&acc)[G2_NR][2], const
   }
 }
 
+#include "g2_probe.h"      // igmc_debug_g2_prims: the primitives one at a time (tests)
 #include "g2_subgraph.h"
 #include "g2_compose.h"
 #include "dl_kernels.h"
